@@ -28,7 +28,15 @@ causal multi-query attention on MFMA -- and reports its throughput too;
 then decode at positions up to ctx - 1.  Weights are seeded synthetic GPT-2
 (no checkpoints offline).
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the --steps steps and prints the result
+line.  --full adds what takes runs of its own after the timed steps: the
+attention kernel's roofline timing (--prof-steps) and the CPU baseline
+(--cpu-baseline); without it `roofline` and `cpu_baseline` are null.
+--dump-outputs DIR writes what the last timed step returned (rank 0's logits
+and next token ids) as DIR/<name>.npy; with the same arguments the inputs are
+seeded alike, so two builds can be compared output for output.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
 Multi-GPU: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 Rank 0 prints ONE JSON line.
 """
@@ -48,6 +56,7 @@ METRIC = "decode tokens/sec GPT-2 124M paged-attn, B=64 T=1024, 1/2/4/8 MI355X"
 # --scaling weak at N > 1 is BASELINE configs[3] (64 sequences per GPU), not the headline metric
 METRIC_WEAK = "decode tokens/sec GPT-2 124M paged-attn, B=64 per GPU (B=512 at 8 GPUs), T=1024, N MI355X"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LOGITS_MAX_BYTES = 60 << 20  # --dump-outputs: the whole dump stays under 64 MB
 
 
 def pmc_traffic(kernel_prefix, batch_per_gpu, ctx, page_size, dtype):
@@ -144,9 +153,17 @@ def parse():
     ap.add_argument("--gather", default="logits", choices=["ids", "logits", "none"],
                     help="end-of-step gather to rank 0 (N>1)")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the attention "
+                         "roofline timing (--prof-steps) and the CPU baseline (--cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them returned on rank 0 as DIR/<name>.npy: "
+                         "logits (rows x V, float32) and next_ids (rows, float64); beyond 60 MB of logits a "
+                         "fixed seeded sample of the rows, their indices in logits_rows")
     ap.add_argument("--prof-steps", type=int, default=4,
-                    help="attention roofline timing: prof_steps x L back-to-back launches (0 = off)")
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "on", "off"])
+                    help="--full: attention roofline timing, prof_steps x L back-to-back launches (0 = off)")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "on", "off"],
+                    help="--full: the CPU baseline (auto: on a single-GPU run)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="per CPU run (-Ofast all cores, -Ofast at OMP_NUM_THREADS, strict all cores)")
     ap.add_argument("--attn-waves", type=int, default=0,
@@ -175,7 +192,29 @@ def parse():
     ap.add_argument("--gemm-waves", default="", help="fused GEMM waves qkv,attproj,fc,fcproj,logits (0 = auto)")
     ap.add_argument("--gemm-rows", default="", help="fused GEMM 16-row blocks per workgroup, same order")
     ap.add_argument("--gemm-cols", default="", help="fused GEMM 16-column tiles per workgroup, same order")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.cpu_baseline == "on" and not args.full:
+        ap.error("--cpu-baseline on needs --full")
+    return args
+
+
+def dump_outputs(out_dir, model, pagedattn):
+    """--dump-outputs: what a caller of the timed step receives after the last
+    timed step -- the logits and the chosen next token ids of this rank's
+    rows -- as float32 / float64 .npy files.  Logits beyond
+    DUMP_LOGITS_MAX_BYTES are cut to a fixed seeded sample of the rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    logits = model.logits()
+    ids = np.empty(model.B, np.int32)
+    pagedattn.check(pagedattn.lib().hpa_memcpy(ids.ctypes.data, model.next_ptr(), ids.nbytes), "next ids download")
+    row_bytes = logits.shape[1] * logits.itemsize
+    keep = DUMP_LOGITS_MAX_BYTES // row_bytes
+    if logits.shape[0] > keep:
+        rows = np.sort(np.random.default_rng(2024).choice(logits.shape[0], keep, replace=False))
+        logits = logits[rows]
+        np.save(os.path.join(out_dir, "logits_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "logits.npy"), np.ascontiguousarray(logits, np.float32))
+    np.save(os.path.join(out_dir, "next_ids.npy"), ids.astype(np.float64))
 
 
 def cpu_baseline(cfgd, B, P, start_ctx, end_ctx, budget_s, kv_bf16=False, w_bf16=False):
@@ -426,12 +465,14 @@ def main():
     ms_per_step = 1000.0 * elapsed / max(args.steps, 1)
     # whole job: every rank's sequences (--emulate-rank: this one GPU's rows)
     tokens_per_s = (B_local if emulate else B) * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, pagedattn)
 
     # ---- live attention-kernel timing: HIP events on the launch stream around
     # back-to-back launches of the step's attention kernel over the layers, on
-    # the engine's own pool at the last step's positions
+    # the engine's own pool at the last step's positions (--full only)
     attn = None
-    if args.prof_steps > 0:
+    if args.full and args.prof_steps > 0:
         iters = args.prof_steps * cfgd["L"]
         avg_ms, per_launch_bytes = model.time_attention(iters)
         attn = dict(avg_ms=avg_ms, launches=iters, per_launch_bytes=per_launch_bytes,
@@ -439,7 +480,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        want_cpu = args.cpu_baseline == "on" or (args.cpu_baseline == "auto" and world == 1)
+        want_cpu = args.full and (args.cpu_baseline == "on" or (args.cpu_baseline == "auto" and world == 1))
         if want_cpu:
             try:
                 # bounded sample: the oracle keeps an fp32 pool of B*ctx*C*L*2 floats, so
@@ -475,6 +516,7 @@ def main():
             "value": round(tokens_per_s, 1),
             "unit": "tokens/s",
             "n_gpus": world,
+            "full": args.full,
             "steps": args.steps,
             "warmup": args.warmup,
             "spinup_s": args.spinup,

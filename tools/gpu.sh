@@ -9,7 +9,8 @@
 #   smoke              __graft_entry__.smoke()
 #   suite[:K]          pytest -m gpu (K: a -k expression)
 #   build              make the library in-tree (normally built before the call)
-#   bench:CFG          python bench.py <CFG args>            -> bench_CFG.txt (+ .json line)
+#   bench:CFG          python bench.py --full <CFG args>     -> bench_CFG.txt (+ .json line; with the
+#                      attention roofline and the CPU baseline)
 #   kstats:CFG         rocprofv3 --kernel-trace --stats of the bench command (spin-up on)
 #                      -> prof_CFG/ + kstats_CFG.txt (per-kernel averages)
 #   pmc:CFG            FETCH_SIZE / WRITE_SIZE, separate --pmc passes -> pmc_CFG/traffic.txt
@@ -61,7 +62,7 @@ for st in "$@"; do
         run suite 1100 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
       fi ;;
     bench)
-      run "bench_$a" 600 python -u bench.py $(cfg_args "$a")
+      run "bench_$a" 600 python -u bench.py --full $(cfg_args "$a")
       grep "^{" "$o/bench_$a.txt" > "$o/bench_$a.json" || true ;;
     kstats)
       run "kstats_run_$a" 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$o/prof_$a" -o run -- \
