@@ -60,6 +60,8 @@ def lib(fast=False):
                                       ctypes.c_ulonglong]
     L.oracle_paged_set_kv.restype = ctypes.c_int
     L.oracle_paged_set_kv.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _F, _F]
+    L.oracle_paged_get_kv.restype = ctypes.c_int
+    L.oracle_paged_get_kv.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _F, _F]
     L.oracle_paged_step.restype = ctypes.c_int
     L.oracle_paged_step.argtypes = [ctypes.c_void_p, _I, _F, _I]
     L.oracle_paged_step_ex.restype = ctypes.c_int
@@ -190,6 +192,15 @@ class PagedDecoder:
         v = np.ascontiguousarray(v, np.float32)
         if self.L.oracle_paged_set_kv(self.h, int(layer), int(b), k.shape[0], fp(k), fp(v)) != 0:
             raise RuntimeError("oracle_paged_set_kv failed")
+
+    def get_kv(self, layer, b, n):
+        """K, V of positions [0, n) of sequence b at `layer` as the cache
+        holds them, token-major (n, C); n <= pos(b)"""
+        k = np.zeros((n, self.c.channels), np.float32)
+        v = np.zeros((n, self.c.channels), np.float32)
+        if self.L.oracle_paged_get_kv(self.h, int(layer), int(b), int(n), fp(k), fp(v)) != 0:
+            raise RuntimeError("oracle_paged_get_kv failed")
+        return k, v
 
     def fill_random(self, ctx, seed=1):
         self.L.oracle_paged_fill_random(self.h, ctx, seed)

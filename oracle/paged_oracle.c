@@ -514,6 +514,21 @@ int oracle_paged_set_kv(OraclePaged* o, int layer, int b, int n, const float* k,
     return 0;
 }
 
+/* parity tests: the K/V rows of positions [0, n) of sequence b at layer l as
+ * the cache holds them (token-major [n][C]); n <= pos[b] */
+int oracle_paged_get_kv(const OraclePaged* o, int layer, int b, int n, float* k, float* v) {
+    const int C = o->cfg.channels;
+    if (layer < 0 || layer >= o->cfg.num_layers || b < 0 || b >= o->B || n < 0 || n > o->pos[b]) return -1;
+    for (int p = 0; p < n; p++) {
+        const int page = o->block_table[(size_t)b * o->max_pages + p / o->P];
+        if (page < 0) return -1;
+        const size_t at = ((size_t)layer * o->num_pages + page) * o->P * C + (size_t)(p % o->P) * C;
+        memcpy(k + (size_t)p * C, o->kpool + at, (size_t)C * 4);
+        memcpy(v + (size_t)p * C, o->vpool + at, (size_t)C * 4);
+    }
+    return 0;
+}
+
 int oracle_paged_step(OraclePaged* o, const int* tokens, float* logits, int* next) {
     return oracle_paged_step_ex(o, tokens, NULL, NULL, logits, next);
 }

@@ -105,6 +105,9 @@ int  oracle_paged_pos(const OraclePaged* o, int b);
 /* parity tests: the K/V of positions [0, n) of sequence b at layer l
  * (token-major [n][C]); pos[b] becomes n */
 int  oracle_paged_set_kv(OraclePaged* o, int layer, int b, int n, const float* k, const float* v);
+/* parity tests: reads positions [0, n) of sequence b at layer l back
+ * (token-major [n][C]); n <= pos[b]; 0 or -1 */
+int  oracle_paged_get_kv(const OraclePaged* o, int layer, int b, int n, float* k, float* v);
 /* bf16 KV pool semantics (BASELINE config 5): appended K/V are rounded to
  * bf16 (nearest even) and read back exactly; all arithmetic stays fp32 */
 void oracle_paged_set_kv_bf16(OraclePaged* o, int on);

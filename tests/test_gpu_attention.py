@@ -85,7 +85,7 @@ def _run_case(hip, P, ctxs, NH, waves=4, seed=0, q_scale=2.0, kv=None, splits=0,
     return out, ref
 
 
-@pytest.mark.parametrize("P", [8, 16, 32])
+@pytest.mark.parametrize("P", [8, 16, 32, 64])
 def test_decode_attention_ragged(hip, P):
     ctxs = [1, 2, 5, 63, 64, 65, 127, 200, 257, 1024]
     out, ref = _run_case(hip, P, ctxs, NH=3, seed=P)
@@ -163,7 +163,7 @@ def test_decode_attention_full_size_subset_and_determinism(hip):
         assert np.abs(o1[b] - ref).max() <= TOL
 
 
-@pytest.mark.parametrize("P", [8, 16, 32])
+@pytest.mark.parametrize("P", [8, 16, 32, 64])
 @pytest.mark.parametrize("splits", [1, 2, 3, 4, 8, 16])
 def test_split_context_attention(hip, P, splits):
     """flash-decoding form: each (sequence, head) cut into
@@ -246,7 +246,7 @@ def test_split_context_attention_strong_scaling_shapes(hip, B):
         assert np.abs(outs[0][b] - ref).max() <= TOL, b
 
 
-@pytest.mark.parametrize("P", [8, 16, 32])
+@pytest.mark.parametrize("P", [8, 16, 32, 64])
 @pytest.mark.parametrize("waves", [1, 4, 8])
 def test_bf16_pool_attention(hip, P, waves):
     """bf16 KV storage (BASELINE config 5), fp32 arithmetic: exact same

@@ -237,6 +237,7 @@ def _layer_pinned_run(hip, cfgd, params, B, P, ctx0, steps, seed, kv_bf16=False,
 # (measured: 1.9e-3 at layer 0, whose stream is the small embedding, 2.5e-4 to
 # 8e-4 after; logits 2.7e-4; 2 of 320 rows near-ties -- profiles/r3/pinned_c5.txt)
 BF16_LAYER_RTOL = 4e-3
+FP32_LAYER_RTOL = 1e-5  # fp32 weights: a layer's output against the oracle, relative to max |x|
 BF16_PINNED_LOGIT_TOL = 2e-3
 
 
@@ -319,4 +320,5 @@ def test_config2_layer_pinned_full_context(hip):
     """the fp32 headline path (its default layer form) layer by layer: B=64,
     page 16, positions ~1014-1023"""
     params = _params(hip, CFG_124M, 57)
-    _layer_pinned_run(hip, CFG_124M, params, B=64, P=16, ctx0=1024 - 10, steps=10, seed=57, layer_rtol=1e-5)
+    _layer_pinned_run(hip, CFG_124M, params, B=64, P=16, ctx0=1024 - 10, steps=10, seed=57,
+                      layer_rtol=FP32_LAYER_RTOL)

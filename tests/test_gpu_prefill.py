@@ -74,15 +74,16 @@ def _attn_case(hip, P, starts, T, NH, bf16=False, seed=0):
     return worst
 
 
-@pytest.mark.parametrize("P", [8, 16, 32])
+@pytest.mark.parametrize("P", [8, 16, 32, 64])
 def test_prefill_attention_matches_oracle(hip, P):
     """ragged starts (fresh, mid-page, past a 64-token block), T not a
     multiple of 64 or 16"""
     assert _attn_case(hip, P, [0, 5, 70], 83, NH=3, seed=P) <= TOL
 
 
-def test_prefill_attention_bf16_pool(hip):
-    assert _attn_case(hip, 16, [0, 17], 50, NH=2, bf16=True, seed=3) <= TOL
+@pytest.mark.parametrize("P", [8, 16, 64])
+def test_prefill_attention_bf16_pool(hip, P):
+    assert _attn_case(hip, P, [0, 17], 50, NH=2, bf16=True, seed=3) <= TOL
 
 
 def test_prefill_attention_single_token(hip):
