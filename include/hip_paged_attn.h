@@ -104,22 +104,46 @@ int   hpa_device_info(char* name, int name_len, int* num_cus, size_t* total_mem)
  * fp32): K tiles [head_size/8][page_size][8] (one 16-byte chunk per
  * lane-per-token load), V tiles [page_size][head_size] (128-byte rows);
  * values are rounded to nearest-even when appended.  Page size multiple of 8.
+ * fp8 pools (HPA_FP8; storage only, lossy -- 3 mantissa bits -- all
+ * arithmetic fp32): one byte per element in the OCP e4m3fn encoding (bias 7,
+ * max 448, no infinities, NaN = 0x7f / 0xff, subnormals down to 2^-9: the
+ * encoding of torch.float8_e4m3fn, not the MI300 fnuz form).  K tiles
+ * [head_size/16][page_size][16] bytes (one 16-byte chunk per lane-per-token
+ * load: a 64-token tile is 4 loads per lane), V tiles [page_size][head_size]
+ * bytes (64-byte rows).  Page size 16, 32 or 64.  page_elems / layer_elems
+ * stay element counts (for fp8 also the byte counts).
+ * One fp32 scale per (layer, K|V, head): `scales`, device memory
+ * [num_layers][2][num_heads][2] = (scale, inv), 1.0 / 1.0 after
+ * hpa_pool_create; NULL for fp32 and bf16 pools.  A stored value is
+ *   code = e4m3fn_rne(clamp(x * inv, -448, 448))
+ * (fp32 product; the clamp in fp32 before the convert, so overflow saturates
+ * to +-448; NaN stays NaN) and a code stands for decode(code) * scale (fp32
+ * product).  Kernels read the scales from device memory at run time, so a
+ * captured graph stays valid when they change.  Calibration is the caller's
+ * job (per-head max |K|, max |V| of an fp32-pool run, divided by 448).
  * A page id names the same slot in every layer's pool (vLLM-style shared
  * block table), so the block table is [seq][logical page] int32. */
 typedef struct HpaKVPool {
     void*  base;          /* device pointer */
     int    num_layers, num_heads, head_size, page_size, num_pages;
-    int    dtype;         /* HPA_F32 or HPA_BF16 */
+    int    dtype;         /* HPA_F32, HPA_BF16 or HPA_FP8 */
     size_t elem_bytes;
     size_t page_elems;    /* elements of one page of one layer (K and V, all heads) */
     size_t layer_elems;   /* num_pages * page_elems */
     size_t bytes;
     int    managed;
+    float* scales;        /* fp8 pools: device [num_layers][2][num_heads][2] (scale, inv); else NULL */
 } HpaKVPool;
-enum { HPA_F32 = 0, HPA_BF16 = 1 };
+enum { HPA_F32 = 0, HPA_BF16 = 1, HPA_FP8 = 2 };
 int  hpa_pool_create(HpaKVPool* pool, int num_layers, int num_heads, int head_size, int page_size,
                      int num_pages, int dtype, int managed);
 void hpa_pool_destroy(HpaKVPool* pool);
+/* fp8 pools: the per-head scales of K and V, host arrays [num_layers][num_heads]
+ * each, every entry finite and > 0 (else nonzero, nothing stored).  Stores
+ * (scale, inv = 1.0f / scale), inv computed once here in fp32.  Codes already
+ * in the pool keep their bytes and change their meaning: set the scales
+ * before anything is appended.  Nonzero on an fp32 / bf16 pool. */
+int  hpa_pool_set_scales(const HpaKVPool* pool, const float* host_k_scale, const float* host_v_scale);
 /* device address of the K (kv=0) or V (kv=1) tile of (layer, page, head) */
 void* hpa_pool_tile(const HpaKVPool* pool, int layer, int page, int kv, int head);
 /* host-side layout helpers (tests / compat copies) */

@@ -154,8 +154,15 @@ float* gpt2_acts_probs(GPT2* model);
  * Uses model->manager when it was set by the caller (its block_size becomes
  * the page size), otherwise creates one sized B x ceil(max_ctx/page_size). */
 int  gpt2_decode_init(GPT2* model, int B, int page_size, int max_ctx);
-/* the same with the KV pool's storage type: HPA_F32 (0, default) or HPA_BF16
- * (1: BASELINE config 5; page size a multiple of 8) */
+/* the same with the KV pool's storage type: HPA_F32 (0, default), HPA_BF16
+ * (1: BASELINE config 5; page size a multiple of 8) or HPA_FP8 (2: OCP e4m3fn
+ * codes with one fp32 scale per (layer, K|V, head), hip_paged_attn.h; page
+ * size 16, 32 or 64, else the call fails with a message).  fp8 storage is
+ * lossy (3 mantissa bits) and halves the bf16 pool's bytes again; the scales
+ * start at 1.0 (gpt2_decode_set_kv_scales).  With an fp8 pool the layer loop
+ * runs chain form 6 where it applies (auto and form 5: C = 768, 12 heads,
+ * B <= 64, fp32 weights) and five launches per layer for every other pick
+ * (bf16 weights included: gpt2_decode_layer_kernel() then reports 0). */
 int  gpt2_decode_init_ex(GPT2* model, int B, int page_size, int max_ctx, int kv_dtype);
 /* ... and the weights' storage type: HPA_F32 (0, default) or HPA_BF16 (1:
  * "bf16 decode" -- the layer and logits weights packed bf16 in HBM, GEMM
@@ -251,8 +258,21 @@ int    gpt2_decode_batch(GPT2* model);
  * position 0 and must be prefilled again); mask (nullable, [B]) marks them.
  * Returns how many. */
 int    gpt2_decode_evicted(GPT2* model, int* mask);
+/* fp8 pools (HPA_FP8): the per-head scales of K and V, host arrays
+ * [num_layers][num_heads], every entry finite and > 0.  A value x is stored
+ * as the e4m3fn code of clamp(x / scale, +-448) and read back as
+ * decode(code) * scale.  Nonzero on an fp32 / bf16 engine, on a bad scale, and
+ * unless every sequence is at position 0 (a fresh engine, or after
+ * gpt2_decode_reset): cached codes would change their meaning.  A captured
+ * graph stays valid (the kernels read the scales from device memory).
+ * Calibration is the caller's job: the per-head max |K| and max |V| of
+ * gpt2_decode_read_kv on an fp32-pool run, divided by 448. */
+int    gpt2_decode_set_kv_scales(GPT2* model, const float* k_scale, const float* v_scale);
+/* the scales in use (either array may be NULL); nonzero on a non-fp8 engine */
+int    gpt2_decode_kv_scales(GPT2* model, float* k_scale, float* v_scale);
 /* K/V of positions [0, n) of sequence b at layer l, token-major [n][C] host
- * arrays (the reference page layout, block_manager.c:145-146) */
+ * arrays (the reference page layout, block_manager.c:145-146); bf16 / fp8
+ * pools: the values the stored codes stand for (fp8: decode(code) * scale) */
 int    gpt2_decode_read_kv(GPT2* model, int layer, int b, int n, float* k, float* v);
 /* fused GEMM launch shapes [qkv, attproj, fc, fcproj, logits]: waves per
  * workgroup (4/8/16), 16-row blocks (1/2/4) and 16-column tiles (1/2/4) per

@@ -5,7 +5,8 @@
 // of positions 0..pos[b] gathered through the sequence's block table.
 //
 // Layout (HpaKVPool, hip_paged_attn.h): per (layer, page) K tiles
-// [head][16 chunks][P tokens][4 floats] and V tiles [head][P tokens][64].
+// [head][16 chunks][P tokens][4 floats] and V tiles [head][P tokens][64]
+// (bf16 and fp8 pools: 8 / 4 chunks of 16 bytes, hpa_attn_body.h).
 //
 // Work decomposition: one workgroup of NW waves per (sequence, head); the
 // context is cut into 64-token tiles, tile `it` goes to wave it % NW.
@@ -43,11 +44,15 @@ namespace {
 using namespace hpa_attn;
 
 
-template <int P, int NW, bool FRAG, bool BF16>
+// DT: the pool's dtype (HPA_F32, HPA_BF16, HPA_FP8); scales: the layer's
+// [2][NH][2] (scale, inv) of an fp8 pool (device memory, read here at run
+// time: a captured graph follows hpa_pool_set_scales), else unused
+template <int P, int NW, bool FRAG, int DT>
 __global__ __launch_bounds__(NW * 64, 3) void paged_attn_decode_f32(
     const float* __restrict__ q, const void* __restrict__ layer_base, size_t page_elems, int NH,
     const int* __restrict__ block_table, int bt_stride, const int* __restrict__ pos,
-    float* __restrict__ out, float qscale, float m_init, int S, float* __restrict__ ws) {
+    float* __restrict__ out, float qscale, float m_init, int S, float* __restrict__ ws,
+    const float* __restrict__ scales) {
     constexpr int TILE = P * HS;
     __shared__ float s_m[NW];
     __shared__ float s_l[NW];
@@ -74,7 +79,26 @@ __global__ __launch_bounds__(NW * 64, 3) void paged_attn_decode_f32(
     int* cnt = S == 1 ? nullptr : reinterpret_cast<int*>(ws + (size_t)gridDim.x * kRec) + bh;
     float m = m_init;
     float l = 0.f;
-    if constexpr (BF16) {
+    if constexpr (DT == HPA_FP8) {
+        const unsigned char* base = reinterpret_cast<const unsigned char*>(layer_base);
+        const float k_scale = scales[2 * h], v_scale = scales[2 * (NH + h)];
+        float4 acc[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        // the raw codes' dot, scaled once by qscale * k_scale
+        attn_tiles_fp8<P, NW>(qh, base + (size_t)h * TILE, base + (size_t)(NH + h) * TILE, page_elems, bt, bt_stride, ctx,
+                              it0, n_it, qscale * k_scale, m, l, acc);
+        if (!attn_fold_fp8<NW>(m, l, acc, s_m, s_l, s_acc)) return;
+        if (S > 1 && !split_merge<4>(rec_bh, cnt, S, sr, m, l, acc, true)) return;
+        const float inv = (l == 0.f ? 0.f : 1.f / l) * v_scale;  // the raw codes' sum, scaled once
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {  // dims 16*lane + 4k .. +3
+            const int col = h * HS + 16 * lane + 4 * k;
+            const size_t oi = FRAG ? hpa::frag_index(b, col, NH * HS) : (size_t)b * NH * HS + col;
+            *reinterpret_cast<float4*>(out + oi) =
+                make_float4(acc[k].x * inv, acc[k].y * inv, acc[k].z * inv, acc[k].w * inv);
+        }
+    } else if constexpr (DT == HPA_BF16) {
         const unsigned short* base = reinterpret_cast<const unsigned short*>(layer_base);
         float4 acc[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
         attn_tiles_bf16<P, NW>(qh, base + (size_t)h * TILE, base + (size_t)(NH + h) * TILE, page_elems, bt, bt_stride, ctx,
@@ -105,7 +129,7 @@ __global__ __launch_bounds__(NW * 64, 3) void paged_attn_decode_f32(
     }
 }
 
-template <int P, bool FRAG, bool BF16>
+template <int P, bool FRAG, int DT>
 int launch_decode(const float* q, const HpaKVPool* pool, int layer, const int* bt, int bt_stride,
                   const int* pos, float* out, int B, int nw, int S, float* ws) {
     const void* base = (const char*)pool->base + (size_t)layer * pool->layer_elems * pool->elem_bytes;
@@ -113,22 +137,23 @@ int launch_decode(const float* q, const HpaKVPool* pool, int layer, const int* b
     const float qscale = (float)(1.0 / sqrt((double)HS)) * log2e;
     const float m_init = -10000.0f * log2e;
     dim3 grid(B * pool->num_heads * S);
+    const float* sc = DT == HPA_FP8 ? pool->scales + (size_t)layer * 4 * pool->num_heads : nullptr;
     switch (nw) {
         case 1:
-            paged_attn_decode_f32<P, 1, FRAG, BF16><<<grid, 64, 0, hpa_stream()>>>(
-                q, base, pool->page_elems, pool->num_heads, bt, bt_stride, pos, out, qscale, m_init, S, ws);
+            paged_attn_decode_f32<P, 1, FRAG, DT><<<grid, 64, 0, hpa_stream()>>>(
+                q, base, pool->page_elems, pool->num_heads, bt, bt_stride, pos, out, qscale, m_init, S, ws, sc);
             break;
         case 2:
-            paged_attn_decode_f32<P, 2, FRAG, BF16><<<grid, 128, 0, hpa_stream()>>>(
-                q, base, pool->page_elems, pool->num_heads, bt, bt_stride, pos, out, qscale, m_init, S, ws);
+            paged_attn_decode_f32<P, 2, FRAG, DT><<<grid, 128, 0, hpa_stream()>>>(
+                q, base, pool->page_elems, pool->num_heads, bt, bt_stride, pos, out, qscale, m_init, S, ws, sc);
             break;
         case 8:
-            paged_attn_decode_f32<P, 8, FRAG, BF16><<<grid, 512, 0, hpa_stream()>>>(
-                q, base, pool->page_elems, pool->num_heads, bt, bt_stride, pos, out, qscale, m_init, S, ws);
+            paged_attn_decode_f32<P, 8, FRAG, DT><<<grid, 512, 0, hpa_stream()>>>(
+                q, base, pool->page_elems, pool->num_heads, bt, bt_stride, pos, out, qscale, m_init, S, ws, sc);
             break;
         default:
-            paged_attn_decode_f32<P, 4, FRAG, BF16><<<grid, 256, 0, hpa_stream()>>>(
-                q, base, pool->page_elems, pool->num_heads, bt, bt_stride, pos, out, qscale, m_init, S, ws);
+            paged_attn_decode_f32<P, 4, FRAG, DT><<<grid, 256, 0, hpa_stream()>>>(
+                q, base, pool->page_elems, pool->num_heads, bt, bt_stride, pos, out, qscale, m_init, S, ws, sc);
             break;
     }
     HPA_LAUNCH_CHECK();
@@ -164,31 +189,38 @@ static int attn_dispatch(const float* q, const HpaKVPool* pool, int layer, const
                          int bt_stride, const int* pos, float* out, int B, bool frag, int S, void* ws,
                          int waves = 0) {
     HPA_REQUIRE(pool && pool->base, "pool not created");
-    HPA_REQUIRE(pool->dtype == HPA_F32 || pool->dtype == HPA_BF16, "decode attention: fp32 or bf16 pool");
+    HPA_REQUIRE(pool->dtype == HPA_F32 || pool->dtype == HPA_BF16 || pool->dtype == HPA_FP8,
+                "decode attention: fp32, bf16 or fp8 pool");
+    HPA_REQUIRE(pool->dtype != HPA_FP8 || (pool->scales && pool->page_size % 16 == 0),
+                "decode attention: fp8 pools need scales and a page size of 16, 32 or 64");
     HPA_REQUIRE(pool->head_size == HS, "decode attention requires head_size 64");
     HPA_REQUIRE(layer >= 0 && layer < pool->num_layers, "layer out of range");
     HPA_REQUIRE(B > 0 && q && out && block_table && pos, "bad arguments");
     HPA_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)out & 15) == 0, "q/out must be 16-byte aligned");
     HPA_REQUIRE(S >= 1 && S <= HPA_ATTN_MAX_SPLITS && (S == 1 || ws), "decode attention: splits 1..16, workspace");
-    const bool bf = pool->dtype == HPA_BF16;
+    const bool bf = pool->dtype == HPA_BF16, f8 = pool->dtype == HPA_FP8;
     float* w = (float*)ws;
     HPA_REQUIRE(waves == 0 || waves == 1 || waves == 2 || waves == 4 || waves == 8, "attention waves 1, 2, 4, 8");
     const int nw = g_attn_waves ? g_attn_waves : waves ? waves : 4;
-#define HPA_ATTN_CASE(PS)                                                                                      \
-    case PS:                                                                                                    \
-        if (bf)                                                                                                 \
-            return frag ? launch_decode<PS, true, true>(q, pool, layer, block_table, bt_stride, pos, out, B, nw, S, w) \
-                        : launch_decode<PS, false, true>(q, pool, layer, block_table, bt_stride, pos, out, B, nw, S, w); \
-        return frag ? launch_decode<PS, true, false>(q, pool, layer, block_table, bt_stride, pos, out, B, nw, S, w)     \
-                    : launch_decode<PS, false, false>(q, pool, layer, block_table, bt_stride, pos, out, B, nw, S, w);
+#define HPA_ATTN_DT(PS, DT)                                                                                 \
+    (frag ? launch_decode<PS, true, DT>(q, pool, layer, block_table, bt_stride, pos, out, B, nw, S, w)      \
+          : launch_decode<PS, false, DT>(q, pool, layer, block_table, bt_stride, pos, out, B, nw, S, w))
+#define HPA_ATTN_CASE(PS)                      \
+    case PS:                                   \
+        if (f8) return HPA_ATTN_DT(PS, HPA_FP8); \
+        if (bf) return HPA_ATTN_DT(PS, HPA_BF16); \
+        return HPA_ATTN_DT(PS, HPA_F32);
     switch (pool->page_size) {
-        HPA_ATTN_CASE(8)
+        case 8:  // no fp8 pages of 8 (checked above)
+            if (bf) return HPA_ATTN_DT(8, HPA_BF16);
+            return HPA_ATTN_DT(8, HPA_F32);
         HPA_ATTN_CASE(16)
         HPA_ATTN_CASE(32)
         HPA_ATTN_CASE(64)
         default: return hpa_fail(__FILE__, __LINE__, "page size must be 8, 16, 32 or 64");
     }
 #undef HPA_ATTN_CASE
+#undef HPA_ATTN_DT
 }
 
 int hpa_paged_attention_decode(const float* q, const HpaKVPool* pool, int layer,

@@ -1,5 +1,5 @@
 // hpa_attn_body.h -- device pieces of the paged decode attention (design
-// notes in hpa_attn.hip): the per-wave tile loops (fp32 and bf16 pools) and
+// notes in hpa_attn.hip): the per-wave tile loops (fp32, bf16 and fp8 pools) and
 // the in-workgroup folds of the online-softmax state.
 #pragma once
 #include <math.h>
@@ -382,6 +382,192 @@ __device__ __forceinline__ bool attn_fold_bf16(float& m, float& l, float4* acc, 
     }
 }
 
+// ---- fp8 KV pool (HPA_FP8, OCP e4m3fn codes): storage only, codes decoded
+// exactly to fp32 (v_cvt_pk_f32_fp8), every product and sum in fp32.  K tile
+// [4 chunks][P][16 dims] bytes (a lane-per-token chunk is one 16-B load: 4
+// loads per lane and tile), V tile [P][64] bytes (64 B per token: 4 lanes per
+// row, one wave instruction reads 16 consecutive rows = 1 KiB).  The raw
+// decoded values are accumulated; the per-head scales multiply the finished
+// dot (kq = qscale * k_scale) here and the output once in the caller.
+// A tile is 8 KiB per wave round trip (fp32: 32 KiB), and a CU's stream is
+// bound by round trips (hpa_attn.hip), so the loop can keep U tiles in flight
+// per wave trip: its tiles it, it + NW, .. it + (U-1) NW are issued together
+// (32 VGPRs of codes each) and then folded in order, so the online-softmax
+// state sees the tiles in the same order for every U (bit-identical).
+// Measured (profiles/r7/kv_fp8.txt, ctx 1020, attention us at B = 8 / 16 /
+// 32 / 64): U = 1 9.06 / 8.98 / 14.32 / 19.49, U = 2 9.30 / 9.27 / 14.68 /
+// 20.71, U = 4 11.56 / 12.47 / 21.41 / 30.72.  One tile per trip wins (not
+// isolated further; with 3 waves per SIMD resident, the other waves' trips
+// may already fill the pipe, while a longer trip delays a wave's own fold).
+// The product runs U = 1; 2 and 4 are A/B builds (-DHPA_ATTN_FP8_TILES=2).
+#ifndef HPA_ATTN_FP8_TILES
+#define HPA_ATTN_FP8_TILES 1  // tiles in flight per wave trip (A/B builds: 2 or 4)
+#endif
+constexpr int kFp8Tiles = HPA_ATTN_FP8_TILES;
+
+__device__ __forceinline__ uint4 load_stream8(const unsigned char* ptr) {
+    typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+    const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(ptr));
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+__device__ __forceinline__ float dot4_e4m3(const float* __restrict__ q4, unsigned w, float s) {
+    const float4 k = hpa::e4m3x4_to_f32(w);
+    s = fmaf(q4[0], k.x, s);
+    s = fmaf(q4[1], k.y, s);
+    s = fmaf(q4[2], k.z, s);
+    return fmaf(q4[3], k.w, s);
+}
+__device__ __forceinline__ void axpy4_e4m3(float p, unsigned w, float4& a) {
+    const float4 v = hpa::e4m3x4_to_f32(w);
+    a.x = fmaf(p, v.x, a.x);
+    a.y = fmaf(p, v.y, a.y);
+    a.z = fmaf(p, v.z, a.z);
+    a.w = fmaf(p, v.w, a.w);
+}
+
+// acc[0..3]: lane (g = lane>>2, d16 = lane&3) holds dims 16*d16..+15 summed
+// over tokens t0 + 16i + g
+template <int P, int NW, int U = kFp8Tiles>
+__device__ __forceinline__ void attn_tiles_fp8(const float* __restrict__ qh, const unsigned char* __restrict__ kbase,
+                                               const unsigned char* __restrict__ vbase, size_t page_elems,
+                                               const int* __restrict__ bt, int bt_len, int ctx, int it_begin,
+                                               int it_end, float kq, float& m, float& l, float4* acc,
+                                               int w = (int)(threadIdx.x >> 6)) {
+    static_assert(P % 16 == 0 && 64 % P == 0, "fp8 pages: page size 16, 32 or 64");
+    static_assert(U >= 1 && U <= 4, "fp8 tiles in flight: 1..4");
+    const int lane = threadIdx.x & 63;
+    const int g = lane >> 2;
+    const int v_lane_off = lane * 16;  // (g rows of 64 B) + (d16 chunks of 16 B)
+    int it = it_begin + w;
+    int pid[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) pid[u] = first_tile_pid<P>(bt, bt_len, ctx, it + u * NW, it_end);
+    for (; it < it_end; it += U * NW) {
+        uint4 kv[U][4], vv[U][4];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int itu = it + u * NW;
+            if (itu < it_end) {  // wave-uniform
+                const unsigned t0 = (unsigned)itu << 6;
+                const unsigned tok = t0 + lane;
+                const unsigned char* kt = kbase + (size_t)(unsigned)pid[u] * page_elems + (tok % P) * 16;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) kv[u][c] = load_stream8(kt + c * P * 16);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int vpid = __builtin_amdgcn_readlane(pid[u], 16 * i);
+                    const unsigned char* vrow = vbase + (size_t)(unsigned)vpid * page_elems + ((16 * i) % P) * HS;
+                    vv[u][i] = (t0 + 16 * i + g) < (unsigned)ctx ? load_stream8(vrow + v_lane_off)
+                                                                : make_uint4(0, 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {  // the next trip's page ids
+            const int itn = it + (U + u) * NW;
+            const unsigned t0n = (unsigned)itn << 6, tokn = t0n + lane;
+            if (itn < it_end) pid[u] = bt[(tokn < (unsigned)ctx ? tokn : t0n) / P];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int itu = it + u * NW;
+            if (itu < it_end) {
+                const bool valid = (((unsigned)itu << 6) + lane) < (unsigned)ctx;
+                float s = 0.f;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    s = dot4_e4m3(qh + 16 * c + 0, kv[u][c].x, s);
+                    s = dot4_e4m3(qh + 16 * c + 4, kv[u][c].y, s);
+                    s = dot4_e4m3(qh + 16 * c + 8, kv[u][c].z, s);
+                    s = dot4_e4m3(qh + 16 * c + 12, kv[u][c].w, s);
+                }
+                s = valid ? s * kq : -INFINITY;
+                const float mt = hpa::wave_max(s);
+                const float mn = fmaxf(m, mt);
+                const float alpha = exp2f(m - mn);
+                const float p = exp2f(s - mn);
+                l = fmaf(l, alpha, p);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    acc[k].x *= alpha;
+                    acc[k].y *= alpha;
+                    acc[k].z *= alpha;
+                    acc[k].w *= alpha;
+                }
+                m = mn;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float pi = __shfl(p, 16 * i + g, 64);
+                    axpy4_e4m3(pi, vv[u][i].x, acc[0]);
+                    axpy4_e4m3(pi, vv[u][i].y, acc[1]);
+                    axpy4_e4m3(pi, vv[u][i].z, acc[2]);
+                    axpy4_e4m3(pi, vv[u][i].w, acc[3]);
+                }
+            }
+        }
+    }
+}
+
+// fold for the fp8 layout: the 16 token groups (lane bits 2..5), then the
+// waves through LDS (s_acc: [NW][4 lanes][4]); result in wave 0, lanes 0..3
+// (chunk k of lane j: dims 4*(4j + k)..+3)
+template <int NW>
+__device__ __forceinline__ bool attn_fold_fp8(float& m, float& l, float4* acc, float* s_m, float* s_l,
+                                              float4* s_acc) {
+    const int lane = threadIdx.x & 63;
+    const int w = threadIdx.x >> 6;
+#pragma unroll
+    for (int o = 4; o <= 32; o <<= 1)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            acc[k].x += __shfl_xor(acc[k].x, o, 64);
+            acc[k].y += __shfl_xor(acc[k].y, o, 64);
+            acc[k].z += __shfl_xor(acc[k].z, o, 64);
+            acc[k].w += __shfl_xor(acc[k].w, o, 64);
+        }
+    l = hpa::wave_sum(l);
+    if constexpr (NW == 1) {
+        return lane < 4;
+    } else {
+        if (lane == 0) {
+            s_m[w] = m;
+            s_l[w] = l;
+        }
+        if (lane < 4) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s_acc[(w * 4 + lane) * 4 + k] = acc[k];
+        }
+        __syncthreads();
+        if (w != 0 || lane >= 4) return false;
+        float M = s_m[0];
+#pragma unroll
+        for (int i = 1; i < NW; ++i) M = fmaxf(M, s_m[i]);
+        float L = 0.f;
+        float4 O[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) O[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const float f = exp2f(s_m[i] - M);
+            L = fmaf(s_l[i], f, L);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float4 a = s_acc[(i * 4 + lane) * 4 + k];
+                O[k].x = fmaf(a.x, f, O[k].x);
+                O[k].y = fmaf(a.y, f, O[k].y);
+                O[k].z = fmaf(a.z, f, O[k].z);
+                O[k].w = fmaf(a.w, f, O[k].w);
+            }
+        }
+        m = M;
+        l = L;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = O[k];
+        return true;
+    }
+}
+
 // Fold the 4 token groups and the per-lane sums of every wave, then the
 // waves (fixed order, through LDS: s_m[NW], s_l[NW], s_acc[NW*16]).  The
 // combined state lands in wave 0, lanes 0..15 (returns true there): lane
@@ -437,7 +623,8 @@ constexpr int kRec = 68;
 
 // Range s of S: publish this workgroup's folded state (K float4 chunks per
 // lane in wave 0: chunk k of lane j holds dims 4*(K*j + k)..+3 -- K = 1 for
-// the fp32 fold, lanes 0..15; K = 2 for the bf16 fold, lanes 0..7); the last
+// the fp32 fold, lanes 0..15; K = 2 for the bf16 fold, lanes 0..7; K = 4 for
+// the fp8 fold, lanes 0..3); the last
 // arriver merges every range in order and returns true with the merged state
 // (rewind: it also zeroes the counter for the next launch).
 // Memory model: gfx950 only.  The hand-off is MI355X_MICROARCH.md "Valid
@@ -476,15 +663,16 @@ __device__ __forceinline__ bool split_merge(float* __restrict__ rec_bh, int* __r
     float4 O[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) O[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int i0 = 0; i0 < S; i0 += 8) {  // ranges in order: independent of arrival order
-        float4 a[8][K];
+    constexpr int QN = K <= 2 ? 8 : 4;    // ranges per batch of loads (K = 4: 16 float4 in flight, as K = 2)
+    for (int i0 = 0; i0 < S; i0 += QN) {  // ranges in order: independent of arrival order
+        float4 a[QN][K];
 #pragma unroll
-        for (int q = 0; q < 8; ++q)
+        for (int q = 0; q < QN; ++q)
 #pragma unroll
             for (int k = 0; k < K; ++k)
                 a[q][k] = hpa::load_wt16(rec_bh + (size_t)min(i0 + q, S - 1) * kRec, (4 + 4 * (K * lane + k)) * 4);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
+        for (int q = 0; q < QN; ++q) {
             if (i0 + q >= S) break;
             float hm = head[0].x, hl = head[0].y;
 #pragma unroll

@@ -26,8 +26,9 @@ struct FG {
     const float* res_in;
     float* stats_out;
     float* part_out;
-    float* kv_base;  // layer base of the KV pool (bf16 pools: reinterpreted)
-    int kv_bf16;
+    float* kv_base;  // layer base of the KV pool (bf16 / fp8 pools: reinterpreted)
+    int kv_dtype;    // the pool's dtype (HPA_F32, HPA_BF16, HPA_FP8)
+    const float* kv_scales;  // fp8 pools: the layer's [2][NH][2] (scale, inv), device memory
     size_t page_elems;
     int NH, P;
     const int* bt;
@@ -203,7 +204,12 @@ struct Epi {
                             if (page < 0) continue;  // no page (host bug): never write below the pool
                             const int slot = ps % p.P;
                             const size_t toff = (size_t)page * p.page_elems + ((size_t)kv * p.NH + hh) * p.P * 64;
-                            if (p.kv_bf16) {  // bf16 pool: K [chunk of 8][slot][8], V [slot][64], RNE
+                            if (p.kv_dtype == HPA_FP8) {  // fp8 pool: K [chunk of 16][slot][16], V [slot][64], e4m3fn codes
+                                unsigned char* kvt = reinterpret_cast<unsigned char*>(p.kv_base) + toff;
+                                const float inv = p.kv_scales[((size_t)kv * p.NH + hh) * 2 + 1];
+                                kvt[kv == 0 ? ((d >> 4) * p.P + slot) * 16 + (d & 15) : slot * 64 + d] =
+                                    hpa::f32_to_e4m3(val, inv);
+                            } else if (p.kv_dtype == HPA_BF16) {  // bf16 pool: K [chunk of 8][slot][8], V [slot][64], RNE
                                 unsigned short* kvt = reinterpret_cast<unsigned short*>(p.kv_base) + toff;
                                 kvt[kv == 0 ? ((d >> 3) * p.P + slot) * 8 + (d & 7) : slot * 64 + d] =
                                     hpa::f32_to_bf16(val);
@@ -665,7 +671,8 @@ static inline int fused_prepare(const HpaFusedGemm* g, FG* p) {
     p->stats_out = g->stats_out;
     p->part_out = g->part_out;
     p->kv_base = nullptr;
-    p->kv_bf16 = 0;
+    p->kv_dtype = HPA_F32;
+    p->kv_scales = nullptr;
     p->page_elems = 0;
     p->NH = 0;
     p->P = 1;
@@ -683,14 +690,16 @@ static inline int fused_prepare(const HpaFusedGemm* g, FG* p) {
     HPA_REQUIRE(!g->ln_fold_c1 || g->epilogue != HPA_FEPI_LOGITS, "gemm_fused: ln_fold_c1 with LOGITS");
     if (g->epilogue == HPA_FEPI_QKV) {
         const HpaKVPool* pool = g->pool;
-        HPA_REQUIRE(pool && pool->base && (pool->dtype == HPA_F32 || pool->dtype == HPA_BF16) &&
-                        pool->head_size == 64,
-                    "gemm_fused QKV: fp32/bf16 pool with head_size 64");
+        HPA_REQUIRE(pool && pool->base && pool->head_size == 64 &&
+                        (pool->dtype == HPA_F32 || pool->dtype == HPA_BF16 ||
+                         (pool->dtype == HPA_FP8 && pool->scales && pool->page_size % 16 == 0)),
+                    "gemm_fused QKV: fp32/bf16/fp8 pool with head_size 64");
         HPA_REQUIRE(g->N == 3 * pool->num_heads * 64, "gemm_fused QKV: N != 3*C");
         HPA_REQUIRE(g->layer >= 0 && g->layer < pool->num_layers, "gemm_fused QKV: layer");
         HPA_REQUIRE(g->block_table && g->pos, "gemm_fused QKV: block table / positions");
         p->kv_base = (float*)((char*)pool->base + (size_t)g->layer * pool->layer_elems * pool->elem_bytes);
-        p->kv_bf16 = pool->dtype == HPA_BF16;
+        p->kv_dtype = pool->dtype;
+        if (pool->dtype == HPA_FP8) p->kv_scales = pool->scales + (size_t)g->layer * 4 * pool->num_heads;
         p->page_elems = pool->page_elems;
         p->NH = pool->num_heads;
         p->P = pool->page_size;

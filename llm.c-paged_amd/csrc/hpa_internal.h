@@ -89,6 +89,40 @@ __device__ __host__ __forceinline__ unsigned short f32_to_bf16(float f) {
     return (unsigned short)(u >> 16);
 }
 
+// fp8 KV storage (HPA_FP8): OCP e4m3fn codes on gfx950's hardware converts.
+// code = e4m3fn_rne(clamp(x * inv, -448, 448)): the product and the clamp in
+// fp32 before the convert (overflow saturates to +-448), NaN -> sign | 0x7f.
+// v_cvt_pk_fp8_f32 was checked against the integer-arithmetic definition on
+// every fp32 bit pattern (DESIGN.md "fp8 KV pool"): equal on every non-NaN
+// input, subnormal results included; it gives 0xff for every NaN, so the sign
+// of a NaN is put back here.
+__device__ __forceinline__ float e4m3_prep(float x, float inv) {
+    const float y = __fmul_rn(x, inv);
+    return y != y ? y : fminf(fmaxf(y, -448.0f), 448.0f);
+}
+__device__ __forceinline__ unsigned e4m3_nan_sign(float y, int byte) {  // bit to clear in a packed word
+    return (y != y && !(__float_as_uint(y) >> 31)) ? 0x80u << (8 * byte) : 0u;
+}
+// four values -> four codes, value i in byte i
+__device__ __forceinline__ unsigned f32x4_to_e4m3(float a, float b, float c, float d, float inv) {
+    const float y0 = e4m3_prep(a, inv), y1 = e4m3_prep(b, inv), y2 = e4m3_prep(c, inv), y3 = e4m3_prep(d, inv);
+    int w = __builtin_amdgcn_cvt_pk_fp8_f32(y0, y1, 0, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(y2, y3, w, true);
+    return (unsigned)w & ~(e4m3_nan_sign(y0, 0) | e4m3_nan_sign(y1, 1) | e4m3_nan_sign(y2, 2) | e4m3_nan_sign(y3, 3));
+}
+__device__ __forceinline__ unsigned char f32_to_e4m3(float x, float inv) {
+    const float y = e4m3_prep(x, inv);
+    const unsigned w = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(y, y, 0, false);
+    return (unsigned char)((w & ~e4m3_nan_sign(y, 0)) & 0xffu);
+}
+// a packed word of four codes -> their exact fp32 values (v_cvt_pk_f32_fp8)
+typedef float e4m3_f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float4 e4m3x4_to_f32(unsigned w) {
+    const e4m3_f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+    const e4m3_f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+    return make_float4(lo.x, lo.y, hi.x, hi.y);
+}
+
 // GELU of the reference (paged_infer.c:243-251): 0.5 x (1 + tanh(sqrt(2/pi)(x + 0.044715 x^3)))
 __device__ __forceinline__ float gelu_ref(float x) {
     // sqrtf(2.0f / M_PI) as the reference computes it: float(2/pi) then sqrtf

@@ -103,6 +103,10 @@ struct KA {
     const float *wte, *wpe;
     int4* zero;
     int zero_n4;
+    // fp8 pool (chain form 6 and the first launch only): the (scale, inv)
+    // pairs [2][NH][2] of the layer at kv_next, device memory read at run time;
+    // NULL: an fp32 / bf16 pool
+    const float* kv_scales_next;
 };
 
 // diagnostic build (-DHPA_LAYER_TRACE, tools/pl_trace.py): s_memrealtime of
@@ -1004,7 +1008,9 @@ __device__ __forceinline__ int qkv_page6(const KA& a, bool ep, int row, int col,
 // qkv epilogue store of 4 columns col..col+3 of `row` (NH = 12): q row-major,
 // or K / V of this token (position ps, page `page` from qkv_pos6 / qkv_page6)
 // into the sequence's page of the layer at kv_next (add_to_cache,
-// paged_infer.c:505-573)
+// paged_infer.c:505-573).  An fp8 pool runs the BF = false instantiation and
+// branches here on a uniform (kv_scales_next): the four columns become one
+// 4-byte store of e4m3fn codes (no third set of chain kernels to build).
 template <int P, bool BF>
 __device__ __forceinline__ void qkv_store6(const KA& a, int row, int col, int ps, int page, float4 v) {
     constexpr int NH = 12, C = 768;
@@ -1025,6 +1031,15 @@ __device__ __forceinline__ void qkv_store6(const KA& a, int row, int col, int ps
         const unsigned hi = hpa::f32_to_bf16(v.z) | ((unsigned)hpa::f32_to_bf16(v.w) << 16);
         *reinterpret_cast<uint2*>(kvt) = make_uint2(lo, hi);
     } else {
+        if (a.kv_scales_next) {  // fp8 pool: K [chunk of 16][slot][16], V [slot][64] bytes
+            if constexpr (P % 16 == 0) {
+                unsigned char* kvt = reinterpret_cast<unsigned char*>(a.kv_next) + toff +
+                                     (kv == 0 ? ((d >> 4) * P + pslot) * 16 + (d & 15) : pslot * 64 + d);
+                const float inv = a.kv_scales_next[(kv * NH + hh) * 2 + 1];
+                *reinterpret_cast<unsigned*>(kvt) = hpa::f32x4_to_e4m3(v.x, v.y, v.z, v.w, inv);
+            }
+            return;
+        }
         float* kvt = reinterpret_cast<float*>(a.kv_next) + toff + (kv == 0 ? ((d >> 2) * P + pslot) * 4 : pslot * 64 + d);
         *reinterpret_cast<float4*>(kvt) = v;
     }
@@ -1848,6 +1863,9 @@ void fill_ka(const HpaLayerArgs* h, int G, KA& a) {
     a.ctr = h->counters;
     a.err = h->err;
     a.err_sticky = h->err_sticky;
+    a.kv_scales_next = pool->dtype == HPA_FP8 && !h->last
+                           ? pool->scales + (size_t)(h->layer + 1) * 4 * pool->num_heads
+                           : nullptr;
 }
 
 // blocks per CU of a 768-thread instantiation (occupancy API), cached per kernel
@@ -1883,6 +1901,7 @@ int launch_first6(const HpaLayerArgs* h, int G, const int* tokens, const float* 
     fill_ka(h, G, a);
     a.last = 0;
     a.kv_next = h->pool->base;  // layer 0's pages
+    a.kv_scales_next = h->pool->dtype == HPA_FP8 ? h->pool->scales : nullptr;
     a.tokens = tokens;
     a.wte = wte;
     a.wpe = wpe;
@@ -2120,7 +2139,7 @@ int hpa_decode_layer_trace(unsigned long long* host, int layers) {
 }
 
 // the chain forms 6 (C = 768) and 8 (C = 768, 1024, 1280 or 1600): B <= 64, fp32 or
-// bf16 pool, a unit per workgroup in every phase
+// bf16 pool (form 6: fp8 too), a unit per workgroup in every phase
 int hpa_decode_chain_eligible(int B, int C, int num_heads, int form) {
     const int G = num_cus();
     if (G <= 0 || C != 64 * num_heads || B < 1 || B > 64) return 0;
@@ -2141,7 +2160,9 @@ int hpa_decode_first(const HpaLayerArgs* h, const int* tokens, const float* wte,
                      size_t zero_bytes) {
     HPA_REQUIRE(h && h->pool && h->pool->base && tokens && wte && wpe, "decode first: null operand");
     const HpaKVPool* pool = h->pool;
-    HPA_REQUIRE(pool->dtype == HPA_F32 || pool->dtype == HPA_BF16, "decode first: fp32 or bf16 pool");
+    HPA_REQUIRE(pool->dtype == HPA_F32 || pool->dtype == HPA_BF16 ||
+                    (pool->dtype == HPA_FP8 && pool->scales && pool->page_size % 16 == 0),
+                "decode first: fp32, bf16 or fp8 (pages of 16, 32, 64) pool");
     HPA_REQUIRE(h->num_heads == 12 && h->C == 768 && pool->head_size == HS && pool->num_heads == 12,
                 "decode first: C = 768, 12 heads of 64");
     HPA_REQUIRE(h->B >= 1 && h->B <= 64, "decode first: 1..64 rows");
@@ -2167,7 +2188,10 @@ int hpa_decode_first(const HpaLayerArgs* h, const int* tokens, const float* wte,
 int hpa_decode_layer(const HpaLayerArgs* h) {
     HPA_REQUIRE(h && h->pool && h->pool->base, "decode layer: pool");
     const HpaKVPool* pool = h->pool;
-    HPA_REQUIRE(pool->dtype == HPA_F32 || pool->dtype == HPA_BF16, "decode layer: fp32 or bf16 pool");
+    // fp8 pools: chain form 6 only (its qkv epilogue stores the codes); the other forms are fp32 / bf16
+    HPA_REQUIRE(pool->dtype == HPA_F32 || pool->dtype == HPA_BF16 ||
+                    (pool->dtype == HPA_FP8 && h->chain_only == 6 && pool->scales && pool->page_size % 16 == 0),
+                "decode layer: fp32 or bf16 pool (fp8: chain form 6, pages of 16, 32, 64)");
     HPA_REQUIRE(pool->head_size == HS && h->C == h->num_heads * HS, "decode layer: head size 64");
     HPA_REQUIRE(h->layer >= 0 && h->layer < pool->num_layers && (h->last || h->layer + 1 < pool->num_layers),
                 "decode layer: layer out of range");

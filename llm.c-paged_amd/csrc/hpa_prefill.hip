@@ -38,7 +38,8 @@ struct PrefillArgs {
     const float* q;        // [rows][C] row-major (row = row0[b] + t)
     const void* layer_base;
     size_t page_elems;
-    int NH, P, bf16;
+    int NH, P, dtype;      // dtype: the pool's (HPA_F32, HPA_BF16, HPA_FP8)
+    const float* scales;   // fp8 pools: the layer's [2][NH][2] (scale, inv)
     const int* bt;
     int bt_stride;
     const int* start;      // [B] position of row t = 0
@@ -55,7 +56,16 @@ __device__ __forceinline__ void load_kv4(const PrefillArgs& a, const int* bt, in
     const int page = bt[key / a.P];
     const int slot = key % a.P;
     const size_t tile = (size_t)a.P * HS;
-    if (a.bf16) {
+    if (a.dtype == HPA_FP8) {  // K [chunk of 16][slot][16], V [slot][64] bytes: decode(code) * scale
+        const unsigned char* base = reinterpret_cast<const unsigned char*>(a.layer_base) + (size_t)page * a.page_elems;
+        const unsigned char* kp = base + (size_t)h * tile + ((size_t)(c >> 2) * a.P + slot) * 16 + (c & 3) * 4;
+        const unsigned char* vp = base + (size_t)(a.NH + h) * tile + (size_t)slot * HS + 4 * c;
+        const float ks = a.scales[2 * h], vs = a.scales[2 * (a.NH + h)];
+        k4 = hpa::e4m3x4_to_f32(*reinterpret_cast<const unsigned*>(kp));
+        v4 = hpa::e4m3x4_to_f32(*reinterpret_cast<const unsigned*>(vp));
+        k4 = make_float4(k4.x * ks, k4.y * ks, k4.z * ks, k4.w * ks);
+        v4 = make_float4(v4.x * vs, v4.y * vs, v4.z * vs, v4.w * vs);
+    } else if (a.dtype == HPA_BF16) {
         const unsigned short* base = reinterpret_cast<const unsigned short*>(a.layer_base) + (size_t)page * a.page_elems;
         const unsigned short* kp = base + (size_t)h * tile + ((size_t)(c >> 1) * a.P + slot) * 8 + (c & 1) * 4;
         const unsigned short* vp = base + (size_t)(a.NH + h) * tile + (size_t)slot * HS + 4 * c;
@@ -218,8 +228,11 @@ int hpa_paged_attention_prefill_ragged(const float* q, const HpaKVPool* pool, in
                                        int bt_stride, const int* start, const int* row0, const int* len, int B,
                                        int T, float* out_frag) {
     HPA_REQUIRE(pool && pool->base && pool->head_size == HS, "prefill attention: pool with head_size 64");
-    HPA_REQUIRE(pool->dtype == HPA_F32 || pool->dtype == HPA_BF16, "prefill attention: fp32 or bf16 pool");
-    HPA_REQUIRE(pool->dtype == HPA_F32 || pool->page_size % 8 == 0, "prefill attention: bf16 pages need P % 8");
+    HPA_REQUIRE(pool->dtype == HPA_F32 || pool->dtype == HPA_BF16 || pool->dtype == HPA_FP8,
+                "prefill attention: fp32, bf16 or fp8 pool");
+    HPA_REQUIRE(pool->dtype != HPA_BF16 || pool->page_size % 8 == 0, "prefill attention: bf16 pages need P % 8");
+    HPA_REQUIRE(pool->dtype != HPA_FP8 || (pool->page_size % 16 == 0 && pool->scales),
+                "prefill attention: fp8 pages need P % 16 and scales");
     HPA_REQUIRE(layer >= 0 && layer < pool->num_layers, "prefill attention: layer out of range");
     HPA_REQUIRE(q && block_table && start && out_frag && B > 0 && T > 0, "prefill attention: bad arguments");
     HPA_REQUIRE(!row0 == !len, "prefill attention: row0 and len go together");
@@ -229,7 +242,8 @@ int hpa_paged_attention_prefill_ragged(const float* q, const HpaKVPool* pool, in
     a.page_elems = pool->page_elems;
     a.NH = pool->num_heads;
     a.P = pool->page_size;
-    a.bf16 = pool->dtype == HPA_BF16;
+    a.dtype = pool->dtype;
+    a.scales = pool->dtype == HPA_FP8 ? pool->scales + (size_t)layer * 4 * pool->num_heads : nullptr;
     a.bt = block_table;
     a.bt_stride = bt_stride;
     a.start = start;

@@ -1,7 +1,8 @@
 // hpa_rows.hip -- synthetic K/V fill of the page pool (the bench's
 // synthetic prefill and the attention microbench): every (layer, sequence,
 // position) token row of K and V gets U(-1, 1) from a counter-based hash, in
-// the pool's fp32 or bf16 layout (hip_paged_attn.h).
+// the pool's fp32, bf16 or fp8 layout (hip_paged_attn.h; fp8: the codes of
+// the same values under the pool's scales).
 #include "hpa_internal.h"
 
 namespace {
@@ -14,7 +15,8 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t z) {
 }
 
 // grid (ctx, B, L): every (layer, sequence, position) token row of K and V
-__global__ __launch_bounds__(256) void pool_fill_random_kernel(void* __restrict__ base_v, int bf16,
+__global__ __launch_bounds__(256) void pool_fill_random_kernel(void* __restrict__ base_v, int dtype,
+                                                               const float* __restrict__ scales,
                                                                size_t layer_elems, size_t page_elems,
                                                                int NH, int P, const int* __restrict__ bt,
                                                                int bt_stride, uint64_t seed, int seq0) {
@@ -32,7 +34,11 @@ __global__ __launch_bounds__(256) void pool_fill_random_kernel(void* __restrict_
         const uint64_t r = splitmix64(seed ^ (key * 2654435761ull + (uint64_t)i));
         const float u = (float)(r >> 40) * (1.0f / 16777216.0f) * 2.0f - 1.0f;
         const size_t tile = off + ((size_t)kv * NH + hh) * P * 64;
-        if (bf16) {
+        if (dtype == HPA_FP8) {  // scales: [L][2][NH][2] (scale, inv)
+            unsigned char* t = reinterpret_cast<unsigned char*>(base_v) + tile;
+            const float inv = scales[(((size_t)l * 2 + kv) * NH + hh) * 2 + 1];
+            t[kv == 0 ? ((d >> 4) * P + slot) * 16 + (d & 15) : slot * 64 + d] = hpa::f32_to_e4m3(u, inv);
+        } else if (dtype == HPA_BF16) {
             unsigned short* t = reinterpret_cast<unsigned short*>(base_v) + tile;
             t[kv == 0 ? ((d >> 3) * P + slot) * 8 + (d & 7) : slot * 64 + d] = hpa::f32_to_bf16(u);
         } else {
@@ -48,13 +54,14 @@ extern "C" {
 
 int hpa_pool_fill_random_ex(const HpaKVPool* pool, const int* block_table, int bt_stride, int B, int ctx,
                             uint64_t seed, int seq_offset) {
-    HPA_REQUIRE(pool && pool->base && (pool->dtype == HPA_F32 || pool->dtype == HPA_BF16) && pool->head_size == 64,
-                "fill_random: fp32/bf16 pool with head_size 64 expected");
+    HPA_REQUIRE(pool && pool->base && pool->head_size == 64 &&
+                    (pool->dtype == HPA_F32 || pool->dtype == HPA_BF16 || (pool->dtype == HPA_FP8 && pool->scales)),
+                "fill_random: fp32/bf16/fp8 pool with head_size 64 expected");
     HPA_REQUIRE(B > 0 && seq_offset >= 0 && seq_offset + B <= 4096 && ctx >= 0 && ctx < 1048576,
                 "fill_random: bad shape");
     if (ctx == 0) return 0;
     dim3 grid(ctx, B, pool->num_layers);
-    pool_fill_random_kernel<<<grid, 256, 0, hpa_stream()>>>(pool->base, pool->dtype == HPA_BF16, pool->layer_elems,
+    pool_fill_random_kernel<<<grid, 256, 0, hpa_stream()>>>(pool->base, pool->dtype, pool->scales, pool->layer_elems,
                                                             pool->page_elems, pool->num_heads,
                                                             pool->page_size, block_table, bt_stride,
                                                             seed, seq_offset);

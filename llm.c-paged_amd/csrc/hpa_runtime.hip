@@ -1,4 +1,5 @@
 // hpa_runtime.hip -- device selection, stream, memory, events, page pool.
+#include <float.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -314,9 +315,12 @@ int hpa_pool_create(HpaKVPool* pool, int num_layers, int num_heads, int head_siz
                     int num_pages, int dtype, int managed) {
     HPA_REQUIRE(pool, "pool is NULL");
     memset(pool, 0, sizeof(*pool));
-    HPA_REQUIRE(dtype == HPA_F32 || dtype == HPA_BF16, "pool dtype must be HPA_F32 or HPA_BF16");
+    HPA_REQUIRE(dtype == HPA_F32 || dtype == HPA_BF16 || dtype == HPA_FP8,
+                "pool dtype must be HPA_F32, HPA_BF16 or HPA_FP8");
     HPA_REQUIRE(head_size % 8 == 0, "head_size must be a multiple of 8");
-    HPA_REQUIRE(dtype == HPA_F32 || page_size % 8 == 0, "bf16 pages need a page size multiple of 8");
+    HPA_REQUIRE(dtype != HPA_BF16 || page_size % 8 == 0, "bf16 pages need a page size multiple of 8");
+    HPA_REQUIRE(dtype != HPA_FP8 || (page_size % 16 == 0 && head_size % 16 == 0),
+                "fp8 pages need a page size and a head size multiple of 16");
     HPA_REQUIRE(page_size > 0 && num_pages > 0 && num_layers > 0 && num_heads > 0, "bad pool shape");
     pool->num_layers = num_layers;
     pool->num_heads = num_heads;
@@ -324,7 +328,7 @@ int hpa_pool_create(HpaKVPool* pool, int num_layers, int num_heads, int head_siz
     pool->page_size = page_size;
     pool->num_pages = num_pages;
     pool->dtype = dtype;
-    pool->elem_bytes = dtype == HPA_BF16 ? 2 : 4;
+    pool->elem_bytes = dtype == HPA_FP8 ? 1 : dtype == HPA_BF16 ? 2 : 4;
     pool->page_elems = (size_t)2 * num_heads * page_size * head_size;
     pool->layer_elems = (size_t)num_pages * pool->page_elems;
     pool->bytes = (size_t)num_layers * pool->layer_elems * pool->elem_bytes;
@@ -334,14 +338,65 @@ int hpa_pool_create(HpaKVPool* pool, int num_layers, int num_heads, int head_siz
     // defined contents: a masked-out lane never multiplies garbage (NaN) pages
     HPA_CHECK(hipMemsetAsync(pool->base, 0, pool->bytes, g_stream));
     HPA_CHECK(hipStreamSynchronize(g_stream));
+    if (dtype == HPA_FP8) {  // per (layer, K|V, head): (scale, inv) = (1, 1)
+        const size_t n = (size_t)num_layers * 2 * num_heads * 2;
+        pool->scales = (float*)hpa_malloc(n * sizeof(float));
+        float* ones = (float*)malloc(n * sizeof(float));
+        if (!pool->scales || !ones) {
+            free(ones);
+            hpa_pool_destroy(pool);
+            return hpa_fail(__FILE__, __LINE__, "page pool scales allocation failed");
+        }
+        for (size_t i = 0; i < n; ++i) ones[i] = 1.0f;
+        const hipError_t e = hipMemcpy(pool->scales, ones, n * sizeof(float), hipMemcpyHostToDevice);
+        free(ones);
+        if (e != hipSuccess) {
+            hpa_pool_destroy(pool);
+            return hpa_fail(__FILE__, __LINE__, hipGetErrorString(e));
+        }
+    }
     return 0;
 }
 
 void hpa_pool_destroy(HpaKVPool* pool) {
+    if (pool && pool->scales) {
+        hpa_free(pool->scales);
+        pool->scales = nullptr;
+    }
     if (pool && pool->base) {
         hpa_free(pool->base);
         pool->base = nullptr;
     }
+}
+
+int hpa_pool_set_scales(const HpaKVPool* pool, const float* host_k_scale, const float* host_v_scale) {
+    HPA_REQUIRE(pool && pool->base && pool->dtype == HPA_FP8 && pool->scales, "set_scales: fp8 pool expected");
+    HPA_REQUIRE(host_k_scale && host_v_scale, "set_scales: NULL scales");
+    const int L = pool->num_layers, NH = pool->num_heads;
+    const size_t n = (size_t)L * 2 * NH * 2;
+    for (int i = 0; i < L * NH; ++i) {
+        const float k = host_k_scale[i], v = host_v_scale[i];
+        HPA_REQUIRE(k > 0.f && v > 0.f && k <= FLT_MAX && v <= FLT_MAX && 1.0f / k <= FLT_MAX &&
+                        1.0f / v <= FLT_MAX,
+                    "set_scales: every scale (and its inverse) finite and > 0");
+    }
+    float* h = (float*)malloc(n * sizeof(float));
+    HPA_REQUIRE(h, "set_scales: out of memory");
+    for (int l = 0; l < L; ++l)
+        for (int hd = 0; hd < NH; ++hd) {
+            const float k = host_k_scale[l * NH + hd], v = host_v_scale[l * NH + hd];
+            float* e = h + ((size_t)l * 2 * NH + hd) * 2;
+            e[0] = k;
+            e[1] = 1.0f / k;  // inv: once, here, in fp32
+            e[2 * NH] = v;
+            e[2 * NH + 1] = 1.0f / v;
+        }
+    // after the stream's earlier work (kernels read the scales at run time)
+    hipError_t e = hipStreamSynchronize(g_stream);
+    if (e == hipSuccess) e = hipMemcpy(pool->scales, h, n * sizeof(float), hipMemcpyHostToDevice);
+    free(h);
+    HPA_CHECK(e);
+    return 0;
 }
 
 void* hpa_pool_tile(const HpaKVPool* p, int layer, int page, int kv, int head) {
@@ -354,6 +409,7 @@ void* hpa_pool_tile(const HpaKVPool* p, int layer, int page, int kv, int head) {
 size_t hpa_pool_k_index(const HpaKVPool* p, int layer, int page, int head, int slot, int d) {
     size_t tile = (size_t)p->page_size * p->head_size;
     size_t base = (size_t)layer * p->layer_elems + (size_t)page * p->page_elems + (size_t)head * tile;
+    if (p->dtype == HPA_FP8) return base + ((size_t)(d >> 4) * p->page_size + slot) * 16 + (d & 15);
     if (p->dtype == HPA_BF16) return base + ((size_t)(d >> 3) * p->page_size + slot) * 8 + (d & 7);
     return base + ((size_t)(d >> 2) * p->page_size + slot) * 4 + (d & 3);
 }

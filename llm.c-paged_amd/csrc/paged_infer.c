@@ -616,6 +616,7 @@ struct GPT2Decode {
     int* d_next;      /* [B] */
     int* h_pos;       /* host mirror of d_pos */
     char* h_evicted;  /* [B] sequences paged out by the LRU policy since the last query */
+    float* h_kv_scale; /* fp8 pool: host copy of the per-head scales, K [L][NH] then V [L][NH]; else NULL */
     /* pinned staging, double-buffered: a buffer is rewritten only after the
      * event recorded behind its previous upload has completed (no stream sync) */
     int* h_tok[2];
@@ -782,6 +783,7 @@ static void dec_free(GPT2Decode* d) {
     }
     if (d->graph) hpa_graph_destroy(d->graph);
     hpa_pool_destroy(&d->pool);
+    free(d->h_kv_scale);
     hpa_free(d->d_bt); hpa_free(d->d_pos); hpa_free(d->d_tokens); hpa_free(d->d_next);
     hpa_free(d->d_q); hpa_free(d->d_logits);
     hpa_free(d->res); hpa_free(d->res2); hpa_free(d->att); hpa_free(d->fch);
@@ -890,6 +892,18 @@ static int dec_pick_B(const GPT2Decode* d) {
  * the first code of any step also sticks in d_next[B] for gpt2_decode_status) */
 #define DEC_ERR_INTS 32
 
+/* the attention's context ranges by shape (hpa_attn_pick_splits); an fp8 pool
+ * runs the single pass from 96 (sequence, head) workgroups up: a range's
+ * stream is a quarter of the fp32 one's, so the merge's extra round trip shows
+ * where fp32 and bf16 still gain from two ranges (tools/attn_scan_kv.py
+ * --sweep, profiles/r7/kv_fp8.txt: B = 8 8.41 us against 9.34 at two ranges,
+ * B = 32 13.40 against 14.75; B = 16 and 64 are single-pass by the shape
+ * rule).  Fewer workgroups were not measured and keep the shape rule. */
+static int dec_pick_splits(const GPT2Decode* d, int B, int ncu) {
+    if (d->pool.dtype == HPA_FP8 && (long)B * d->pool.num_heads >= 96) return 1;
+    return hpa_attn_pick_splits(B, d->pool.num_heads, d->max_ctx, ncu);
+}
+
 /* the attention's context ranges and their workspace (zeroed whenever the
  * split count changes: the counters sit after the records of that count) */
 static int dec_set_splits(GPT2Decode* d, int splits) {
@@ -908,7 +922,9 @@ static int dec_set_splits(GPT2Decode* d, int splits) {
         /* bf16 pools with >= 8 (sequence, head, range) workgroups per CU: 8 waves (a workgroup
          * moves half the bytes per tile; config 5: 3.287-3.291 vs 3.298-3.305 ms per step,
          * paired runs, profiles/r5/experiments/c5_attention_waves.txt) */
-        if (d->pool.dtype == HPA_BF16 && ncu > 0 &&
+        /* fp8 pools: the same rule (a quarter of the bytes per tile): measured best at B = 8,
+         * 16 (8 waves) and 32, 64 (4 waves), profiles/r7/kv_fp8.txt */
+        if ((d->pool.dtype == HPA_BF16 || d->pool.dtype == HPA_FP8) && ncu > 0 &&
             (long)dec_pick_B(d) * d->pool.num_heads * splits >= 8L * ncu)
             d->attn_waves = 8;
     }
@@ -996,6 +1012,12 @@ static int dec_layer_setup(GPT2* model, GPT2Decode* d) {
     d->pl_on = 0;
     /* bf16 weights (BASELINE config 5): the bf16 chain (hpa_chain_b16.hip),
      * B <= 256, in place of four GEMM launches per layer */
+    /* an fp8 pool's K/V are appended by chain form 6 (with the step's first
+     * launch) and by the GEMM launches' shared epilogue only: auto and form 5
+     * give chain form 6 where it applies, every other pick -- the bf16 chain
+     * included -- runs five launches per layer */
+    const int kv_fp8 = d->pool.dtype == HPA_FP8;
+    if (kv_fp8 && (d->w_bf16 || (d->pl_want != 1 && d->pl_want != 5) || c.num_heads != 12)) return 0;
     if (d->pl_want && d->w_bf16) return dec_chain_b16_setup(model, d);
     if (!d->pl_want || d->w_bf16 || !d->d_fold) return 0;
     const int Bg = dec_pick_B(d); /* the batch the picks follow */
@@ -1180,8 +1202,8 @@ int gpt2_decode_init_ex(GPT2* model, int B, int page_size, int max_ctx, int kv_d
 
 int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dtype, int w_dtype) {
     ensure_device();
-    if (kv_dtype != HPA_F32 && kv_dtype != HPA_BF16) {
-        fprintf(stderr, "[paged_infer] kv dtype must be HPA_F32 or HPA_BF16\n");
+    if (kv_dtype != HPA_F32 && kv_dtype != HPA_BF16 && kv_dtype != HPA_FP8) {
+        fprintf(stderr, "[paged_infer] kv dtype must be HPA_F32, HPA_BF16 or HPA_FP8\n");
         return 1;
     }
     if (w_dtype != HPA_F32 && w_dtype != HPA_BF16) {
@@ -1215,6 +1237,11 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
         free(d);
         return 1;
     }
+    if (kv_dtype == HPA_FP8 && page_size % 16 != 0) {
+        fprintf(stderr, "[paged_infer] an fp8 KV pool needs a page size of 16, 32 or 64\n");
+        free(d);
+        return 1;
+    }
     d->B = B;
     d->P = page_size;
     d->max_ctx = max_ctx;
@@ -1237,6 +1264,15 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
     if (hpa_pool_create(&d->pool, c.num_layers, c.num_heads, 64, page_size, num_pages, kv_dtype, 0)) {
         dec_free(d);
         return 1;
+    }
+    if (kv_dtype == HPA_FP8) { /* the pool starts at scale 1.0 everywhere */
+        const size_t n = (size_t)2 * c.num_layers * c.num_heads;
+        d->h_kv_scale = (float*)malloc(n * sizeof(float));
+        if (!d->h_kv_scale) {
+            dec_free(d);
+            return 1;
+        }
+        for (size_t i = 0; i < n; i++) d->h_kv_scale[i] = 1.0f;
     }
     /* pages of this manager are views into the pool from now on */
     for (int p = 0; p < d->bm->max_prompts; p++)
@@ -1318,7 +1354,7 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
     d->w_bf16 = w_dtype == HPA_BF16;
     int ncu = 0;
     hpa_device_info(NULL, 0, &ncu, NULL);
-    if (dec_init_weights(model, d) || dec_set_splits(d, hpa_attn_pick_splits(B, c.num_heads, max_ctx, ncu))) {
+    if (dec_init_weights(model, d) || dec_set_splits(d, dec_pick_splits(d, B, ncu))) {
         dec_free(d);
         return 1;
     }
@@ -1728,7 +1764,7 @@ int gpt2_decode_set_attn_splits(GPT2* model, int splits) {
     if (splits == 0) {
         int ncu = 0;
         hpa_device_info(NULL, 0, &ncu, NULL);
-        splits = hpa_attn_pick_splits(dec_pick_B(d), d->pool.num_heads, d->max_ctx, ncu);
+        splits = dec_pick_splits(d, dec_pick_B(d), ncu);
     }
     if (hpa_synchronize()) return 1;
     return dec_set_splits(d, splits);
@@ -2127,6 +2163,38 @@ int gpt2_decode_fill_random_ex(GPT2* model, int ctx, unsigned long long seed, in
     return 0;
 }
 
+/* fp8 pools: the per-head scales of K and V, host arrays [L][NH] (every entry
+ * finite and > 0).  Only while every sequence is at position 0 (a fresh engine
+ * or after gpt2_decode_reset): cached codes would change their meaning.  The
+ * kernels read the scales from device memory, so a captured graph stays valid. */
+int gpt2_decode_set_kv_scales(GPT2* model, const float* k_scale, const float* v_scale) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d || !k_scale || !v_scale) return 1;
+    if (d->pool.dtype != HPA_FP8) {
+        fprintf(stderr, "[paged_infer] set_kv_scales: the engine's KV pool is not fp8\n");
+        return 1;
+    }
+    for (int b = 0; b < d->B; b++)
+        if (d->h_pos[b] != 0) {
+            fprintf(stderr, "[paged_infer] set_kv_scales: sequence %d holds cached tokens (gpt2_decode_reset first)\n", b);
+            return 1;
+        }
+    if (hpa_pool_set_scales(&d->pool, k_scale, v_scale)) return 1;
+    const size_t n = (size_t)model->config.num_layers * model->config.num_heads;
+    memcpy(d->h_kv_scale, k_scale, n * sizeof(float));
+    memcpy(d->h_kv_scale + n, v_scale, n * sizeof(float));
+    return 0;
+}
+
+int gpt2_decode_kv_scales(GPT2* model, float* k_scale, float* v_scale) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d || d->pool.dtype != HPA_FP8) return 1;
+    const size_t n = (size_t)model->config.num_layers * model->config.num_heads;
+    if (k_scale) memcpy(k_scale, d->h_kv_scale, n * sizeof(float));
+    if (v_scale) memcpy(v_scale, d->h_kv_scale + n, n * sizeof(float));
+    return 0;
+}
+
 float* gpt2_decode_logits(GPT2* model) { return model->decode ? model->decode->d_logits : NULL; }
 int* gpt2_decode_next(GPT2* model) { return model->decode ? model->decode->d_next : NULL; }
 int gpt2_decode_batch(GPT2* model) { return model->decode ? model->decode->B : 0; }
@@ -2146,6 +2214,13 @@ int gpt2_decode_read_kv(GPT2* model, int l, int b, int n, float* k, float* v) {
     if (!d || l < 0 || l >= model->config.num_layers || b < 0 || b >= d->B || n < 0 || n > d->h_pos[b]) return 1;
     const int C = model->config.channels, NH = model->config.num_heads, P = d->P;
     const size_t tile = (size_t)P * 64, eb = d->pool.elem_bytes;
+    float e4m3[256]; /* fp8 pools: the value of every code (OCP e4m3fn) */
+    if (eb == 1)
+        for (int code = 0; code < 256; code++) {
+            const int e = (code >> 3) & 15, m = code & 7;
+            const float a = e == 15 && m == 7 ? NAN : e == 0 ? ldexpf((float)m, -9) : ldexpf(1.0f + m / 8.0f, e - 7);
+            e4m3[code] = code & 0x80 ? -a : a;
+        }
     unsigned char* buf = (unsigned char*)malloc(2 * NH * tile * eb);
     if (!buf || hpa_synchronize()) { free(buf); return 1; }
     int rc = 0;
@@ -2156,15 +2231,20 @@ int gpt2_decode_read_kv(GPT2* model, int l, int b, int n, float* k, float* v) {
             for (int h = 0; h < NH; h++)
                 for (int x = 0; x < 64; x++) {
                     const int s = t - p0;
-                    /* K [chunk][slot][4|8], V [slot][64] (hip_paged_attn.h pool layout) */
-                    const size_t ki = eb == 4 ? ((size_t)(x >> 2) * P + s) * 4 + (x & 3)
-                                              : ((size_t)(x >> 3) * P + s) * 8 + (x & 7);
+                    /* K [chunk][slot][4|8|16], V [slot][64] (hip_paged_attn.h pool layout) */
+                    const size_t ki = eb == 4   ? ((size_t)(x >> 2) * P + s) * 4 + (x & 3)
+                                      : eb == 2 ? ((size_t)(x >> 3) * P + s) * 8 + (x & 7)
+                                                : ((size_t)(x >> 4) * P + s) * 16 + (x & 15);
                     const size_t vi = (size_t)s * 64 + x;
                     const size_t kt = (size_t)h * tile, vt = (size_t)(NH + h) * tile;
                     float kf, vf;
                     if (eb == 4) {
                         kf = ((const float*)buf)[kt + ki];
                         vf = ((const float*)buf)[vt + vi];
+                    } else if (eb == 1) { /* decode(code) * scale, an fp32 product */
+                        const size_t LN = (size_t)model->config.num_layers * NH;
+                        kf = e4m3[buf[kt + ki]] * d->h_kv_scale[(size_t)l * NH + h];
+                        vf = e4m3[buf[vt + vi]] * d->h_kv_scale[LN + (size_t)l * NH + h];
                     } else {
                         const unsigned ku = (unsigned)((const unsigned short*)buf)[kt + ki] << 16;
                         const unsigned vu = (unsigned)((const unsigned short*)buf)[vt + vi] << 16;
@@ -2311,7 +2391,7 @@ double gpt2_decode_step_bytes(GPT2* model, double* attn_bytes) {
     if (!d) return 0.0;
     const GPT2Config c = model->config;
     const double C = c.channels, L = c.num_layers, V = c.vocab_size, w = 4.0;
-    const double wkv = (double)d->pool.elem_bytes; /* fp32 or bf16 KV storage */
+    const double wkv = (double)d->pool.elem_bytes; /* fp32, bf16 or fp8 KV storage */
     const double wm = d->w_bf16 ? 2.0 : 4.0; /* GEMM weight matrices: bf16 or fp32 */
     const double weights = (L * 12 * C * C + V * C) * wm + (L * 13 * C + 2 * C) * w;
     double kv = 0.0;
@@ -2348,7 +2428,7 @@ int gpt2_decode_set_global_batch(GPT2* model, int total) {
     hpa_device_info(NULL, 0, &ncu, NULL);
     d->pl_global_B = total;
     if (hpa_synchronize() ||
-        dec_set_splits(d, hpa_attn_pick_splits(dec_pick_B(d), model->config.num_heads, d->max_ctx, ncu)) ||
+        dec_set_splits(d, dec_pick_splits(d, dec_pick_B(d), ncu)) ||
         dec_layer_setup(model, d))
         return 1;
     if (d->graph) {

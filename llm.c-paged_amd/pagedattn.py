@@ -47,7 +47,7 @@ class HpaKVPool(ctypes.Structure):
                 ("num_pages", ctypes.c_int), ("dtype", ctypes.c_int),
                 ("elem_bytes", ctypes.c_size_t), ("page_elems", ctypes.c_size_t),
                 ("layer_elems", ctypes.c_size_t), ("bytes", ctypes.c_size_t),
-                ("managed", ctypes.c_int)]
+                ("managed", ctypes.c_int), ("scales", _F)]
 
 
 class HpaFusedGemm(ctypes.Structure):
@@ -176,6 +176,7 @@ def lib():
     # pool + kernels
     _sig(L, "hpa_pool_create", i, [P, i, i, i, i, i, i, i])
     _sig(L, "hpa_pool_destroy", None, [P])
+    _sig(L, "hpa_pool_set_scales", i, [P, _F, _F])
     _sig(L, "hpa_pool_tile", v, [P, i, i, i, i])
     _sig(L, "hpa_pool_k_index", sz, [P, i, i, i, i, i])
     _sig(L, "hpa_pool_v_index", sz, [P, i, i, i, i, i])
@@ -274,6 +275,8 @@ def lib():
     _sig(L, "hpa_logits_trace", i, [v])
     _sig(L, "gpt2_decode_evicted", i, [v, _I])
     _sig(L, "gpt2_decode_read_kv", i, [v, i, i, i, _F, _F])
+    _sig(L, "gpt2_decode_set_kv_scales", i, [v, _F, _F])
+    _sig(L, "gpt2_decode_kv_scales", i, [v, _F, _F])
     _sig(L, "gpt2_decode_batch", i, [v])
     _sig(L, "gpt2_decode_shard", i, [v, _I, i])
     _sig(L, "gpt2_decode_gather", i, [v, i])
@@ -398,31 +401,88 @@ def round_bf16(a):
     return from_bf16_bits(to_bf16_bits(a))
 
 
-HPA_F32, HPA_BF16 = 0, 1
+# fp8 KV storage (HPA_FP8): OCP e4m3fn -- 1 sign, 4 exponent (bias 7), 3
+# mantissa bits; max 448, no infinities, NaN = 0x7f / 0xff, subnormals m * 2^-9
+# (the encoding of torch.float8_e4m3fn, not the MI300 fnuz form).  numpy only.
+def to_fp8_bits(a):
+    """fp32 -> e4m3fn codes: round to nearest even of clamp(a, -448, 448);
+    NaN -> sign | 0x7f (hpa::f32_to_e4m3 at inv = 1)"""
+    u = np.ascontiguousarray(a, np.float32).view(np.uint32)
+    sign = ((u >> 24) & 0x80).astype(np.uint8)
+    mag = u & np.uint32(0x7FFFFFFF)
+    nan = mag > 0x7F800000
+    mag = np.minimum(mag, np.uint32(0x43E00000))  # |x| <= 448: overflow saturates
+    # normal results (|x| >= 2^-6): keep 3 mantissa bits, ties to even, rebias 127 -> 7
+    norm = ((mag.astype(np.uint64) + 0x7FFFF + ((mag >> 20) & 1)) >> 20).astype(np.int64) - 960
+    # subnormal results: multiples of 2^-9, rounded by an fp32 addition (ulp(2^14) = 2^-9)
+    sub = (mag.view(np.float32) + np.float32(16384.0)).astype(np.float32).view(np.uint32).astype(np.int64) - 0x46800000
+    code = np.where((mag >> 23) >= 121, norm, sub)
+    code = np.where(nan, 0x7F, code).astype(np.uint8)
+    return code | sign
+
+
+def from_fp8_bits(b):
+    """e4m3fn codes -> the fp32 values they stand for (exact)"""
+    b = np.asarray(b, np.uint8).astype(np.int32)
+    e, m = (b >> 3) & 15, b & 7
+    mag = np.where(e == 0, np.ldexp(m.astype(np.float32), -9),
+                   np.ldexp((1.0 + m / 8.0).astype(np.float32), e - 7)).astype(np.float32)
+    mag = np.where((e == 15) & (m == 7), np.float32(np.nan), mag)
+    return np.where(b & 0x80, -mag, mag).astype(np.float32)
+
+
+def round_fp8(a, scale=1.0):
+    """the fp32 value an fp8 KV pool holds for `a` under `scale` (broadcast
+    against a): decode(code(a * inv)) * scale with inv = fp32(1 / scale), every
+    product an fp32 product (hip_paged_attn.h)"""
+    scale = np.asarray(scale, np.float32)
+    inv = (np.float32(1.0) / scale).astype(np.float32)
+    a = np.asarray(a, np.float32)
+    return (from_fp8_bits(to_fp8_bits((a * inv).astype(np.float32))) * scale).astype(np.float32)
+
+
+HPA_F32, HPA_BF16, HPA_FP8 = 0, 1, 2
 
 
 class Pool:
-    """HpaKVPool: the HBM page pool in the fast layout (fp32 or bf16)."""
+    """HpaKVPool: the HBM page pool in the fast layout (fp32, bf16 or fp8)."""
 
     def __init__(self, num_layers, num_heads, page_size, num_pages, head_size=64, managed=False, dtype=HPA_F32):
         self.s = HpaKVPool()
         check(lib().hpa_pool_create(ctypes.byref(self.s), num_layers, num_heads, head_size, page_size,
                                     num_pages, int(dtype), int(managed)), "pool_create")
+        # fp8 pools: host copy of the per-head scales, (L, NH) each
+        self.k_scale = np.ones((num_layers, num_heads), np.float32)
+        self.v_scale = np.ones((num_layers, num_heads), np.float32)
 
     @property
     def ref(self):
         return ctypes.byref(self.s)
 
     def _k_chunk(self):
-        return 8 if self.s.dtype == HPA_BF16 else 4
+        return {HPA_BF16: 8, HPA_FP8: 16}.get(self.s.dtype, 4)
+
+    def set_scales(self, k_scale, v_scale):
+        """fp8 pools: per-head scales of K and V, (L, NH) each (or scalars),
+        finite and > 0; set them before anything is written"""
+        shape = (self.s.num_layers, self.s.num_heads)
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(k_scale, np.float32), shape))
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(v_scale, np.float32), shape))
+        check(lib().hpa_pool_set_scales(self.ref, k.ctypes.data_as(_F), v.ctypes.data_as(_F)), "pool_set_scales")
+        self.k_scale, self.v_scale = k, v
 
     def write_tokens(self, layer, pages, k, v):
         """host helper: k, v (ntok, C) -> logical positions 0..ntok-1 of the
         sequence whose page list is `pages` (uploads whole pages; bf16 pools
-        store the round-to-nearest-even values)."""
+        store the round-to-nearest-even values, fp8 pools the e4m3fn codes of
+        the values over the head's scale)."""
         s = self.s
         P, NH, HS, ch = s.page_size, s.num_heads, s.head_size, self._k_chunk()
-        bf = s.dtype == HPA_BF16
+        bf, f8 = s.dtype == HPA_BF16, s.dtype == HPA_FP8
+        if f8:
+            one = np.float32(1.0)
+            k_inv = (one / self.k_scale[layer]).astype(np.float32)
+            v_inv = (one / self.v_scale[layer]).astype(np.float32)
         ntok = k.shape[0]
         for lp, page in enumerate(pages):
             t0 = lp * P
@@ -435,6 +495,9 @@ class Pool:
             vt[:, :n, :] = v[t0:t0 + n].reshape(n, NH, HS).transpose(1, 0, 2)
             if bf:
                 kt, vt = to_bf16_bits(kt), to_bf16_bits(vt)
+            if f8:
+                kt = to_fp8_bits(kt * k_inv[:, None, None, None])
+                vt = to_fp8_bits(vt * v_inv[:, None, None])
             page_k = lib().hpa_pool_tile(self.ref, layer, int(page), 0, 0)
             page_v = lib().hpa_pool_tile(self.ref, layer, int(page), 1, 0)
             check(lib().hpa_memcpy(page_k, kt.ctypes.data, kt.nbytes), "pool write K")
@@ -443,8 +506,8 @@ class Pool:
     def read_tokens(self, layer, pages, ntok):
         s = self.s
         P, NH, HS, ch = s.page_size, s.num_heads, s.head_size, self._k_chunk()
-        bf = s.dtype == HPA_BF16
-        et = np.uint16 if bf else np.float32
+        bf, f8 = s.dtype == HPA_BF16, s.dtype == HPA_FP8
+        et = np.uint16 if bf else np.uint8 if f8 else np.float32
         k = np.zeros((ntok, NH * HS), np.float32)
         v = np.zeros((ntok, NH * HS), np.float32)
         for lp, page in enumerate(pages):
@@ -460,6 +523,9 @@ class Pool:
                                    vt.nbytes), "pool read V")
             if bf:
                 kt, vt = from_bf16_bits(kt), from_bf16_bits(vt)
+            if f8:
+                kt = from_fp8_bits(kt) * self.k_scale[layer][:, None, None, None]
+                vt = from_fp8_bits(vt) * self.v_scale[layer][:, None, None]
             k[t0:t0 + n] = kt[:, :, :n, :].transpose(2, 0, 1, 3).reshape(n, NH * HS)
             v[t0:t0 + n] = vt[:, :n, :].transpose(1, 0, 2).reshape(n, NH * HS)
         return k, v
@@ -690,6 +756,21 @@ class Model:
         v = np.zeros((n, C), np.float32)
         check(lib().gpt2_decode_read_kv(self.h, int(layer), int(b), int(n), k.ctypes.data_as(_F),
                                         v.ctypes.data_as(_F)), "read_kv")
+        return k, v
+
+    def set_kv_scales(self, k_scale, v_scale):
+        """fp8 KV pool: per-head scales of K and V, (L, NH) each (or scalars),
+        finite and > 0; only while every sequence is at position 0"""
+        shape = (self.cfg.num_layers, self.cfg.num_heads)
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(k_scale, np.float32), shape))
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(v_scale, np.float32), shape))
+        check(lib().gpt2_decode_set_kv_scales(self.h, k.ctypes.data_as(_F), v.ctypes.data_as(_F)), "set_kv_scales")
+
+    def kv_scales(self):
+        """fp8 KV pool: (k_scale, v_scale), (L, NH) each"""
+        shape = (self.cfg.num_layers, self.cfg.num_heads)
+        k, v = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        check(lib().gpt2_decode_kv_scales(self.h, k.ctypes.data_as(_F), v.ctypes.data_as(_F)), "kv_scales")
         return k, v
 
     def shard(self, rows_per_rank, root=0):
