@@ -373,7 +373,10 @@ int hpa_fused_pick_waves(int M, int N, int K);
 typedef struct {
     int B, C, num_heads, splits;  /* splits: context ranges of the attention */
     int last;                     /* 1: no qkv(l+1) phase (last layer) */
-    int chain_only;               /* 1: no attention phase -- the caller launched the decode
+    int chain_only;               /* 0..6 or 8; the engine's value is DecPlan.chain
+                                     (gpt2_decode_layer_plan, paged_infer.h).  0: the full layer,
+                                     attention phase first (A/B builds only, like 2..5);
+                                     1: no attention phase -- the caller launched the decode
                                      attention (frag output into att) before: the launch is
                                      attproj -> fc -> fcproj -> qkv(l+1); 2..5: the same with wide
                                      units (C = 768), waves per unit of (attproj, fc / fcproj,
@@ -417,12 +420,19 @@ typedef struct {
                                      step (gpt2_decode_status reads and clears it) */
     int stats_mp;                 /* row stride of stats_out; 0: this launch's Mp */
 } HpaLayerArgs;
-/* 1 if the persistent layer applies (shape, CU count, residency), else 0 */
+/* The eligibility predicates and the split pick come in two forms: *_cus
+ * takes the CU count as an argument and reads no device (num_cus <= 0: not
+ * eligible; the plan function gpt2_decode_layer_plan calls only these); the
+ * plain name passes the current device's CU count. */
+/* 1 if the persistent layer (chain_only 0..5) applies (C = 128 or 768, shape, CU count), else 0 */
+int hpa_decode_layer_eligible_cus(int B, int C, int num_heads, int splits, int num_cus);
 int hpa_decode_layer_eligible(int B, int C, int num_heads, int splits);
-/* 1 if chain form `form` (HpaLayerArgs.chain_only 6, 7: C = 768; 8: C = 768,
- * 1024, 1280 or 1600) applies to B rows on this device's CU count, else 0 */
+/* 1 if chain form `form` (HpaLayerArgs.chain_only 6: C = 768; 8: C = 768,
+ * 1024, 1280 or 1600) applies to B rows on num_cus CUs, else 0 (any other form: 0) */
+int hpa_decode_chain_eligible_cus(int B, int C, int num_heads, int form, int num_cus);
 int hpa_decode_chain_eligible(int B, int C, int num_heads, int form);
-/* splits the persistent layer uses by default for this batch */
+/* splits the full persistent layer uses by default for this batch (num_cus <= 0: 1) */
+int hpa_decode_layer_pick_splits_cus(int B, int num_heads, int max_ctx, int num_cus);
 int hpa_decode_layer_pick_splits(int B, int num_heads, int max_ctx);
 /* sizes: out[0] = rec floats, out[1] = slab floats, out[2] = counter ints per layer */
 int hpa_decode_layer_sizes(int B, int C, int num_heads, int splits, size_t* out3);
@@ -479,6 +489,7 @@ typedef struct {
     int g_cus;                    /* CUs of the GEMM role (multiple of 8; 0: 64) */
 } HpaPipeArgs;
 /* 1 if the pipelined-halves launch applies to B rows (C, heads, pool dtype, CU count) */
+int hpa_decode_pipe_eligible_cus(int B, int C, int num_heads, int kv_dtype, int num_cus);
 int hpa_decode_pipe_eligible(int B, int C, int num_heads, int kv_dtype);
 /* out2 = {slab floats, counter ints per layer} */
 int hpa_decode_pipe_sizes(int B, size_t* out2);
@@ -520,6 +531,8 @@ typedef struct {
     int* err;                     /* as HpaLayerArgs.err / err_sticky */
     int* err_sticky;
 } HpaChainB16Args;
+/* 1 if the bf16 chain applies (C = 768, 12 heads, 1..256 rows, a unit per workgroup), else 0 */
+int hpa_decode_chain_b16_eligible_cus(int B, int C, int num_heads, int num_cus);
 int hpa_decode_chain_b16_eligible(int B, int C, int num_heads);
 /* out2 = {slab floats, counter ints per layer} */
 int hpa_decode_chain_b16_sizes(int B, size_t* out2);

@@ -214,33 +214,58 @@ int  gpt2_decode_set_attn_splits(GPT2* model, int splits);
 int  gpt2_decode_attn_splits(GPT2* model);
 /* waves per attention workgroup the engine picked for its batch (hpa_attn_pick_waves) */
 int  gpt2_decode_attn_waves(GPT2* model);
-/* the layer loop's form: 0 five launches per layer; 2 one persistent launch
- * per layer (hpa_decode_layer: attention -> attproj -> fc -> fcproj -> next
- * qkv); 3 the decode attention's own launch + one persistent launch of the
- * GEMM chain (attproj -> fc -> fcproj -> next qkv) in 4-wave units; 4 the
- * chain in round 3's wide units (C = 768); 5 chain form 6: every phase in
- * 12-wave units of T tiles, one per workgroup, 16-byte epilogues, waits per
- * row block (C = 768); 6 chain form 8: streamed-weight units for MFMA-bound
- * wide layers (C = 768 / 1024 / 1280 / 1600: GPT-2 124M to XL); 1 (default, "auto") the form
- * measured fastest (profiles/r4: 5 at C = 768, 6 at C >= 1024, else 3).
- * The persistent forms need fp32 weights and B <= 64 (else five launches).
- * HPA_LAYER_KERNEL=0..6 in the environment
- * sets the default.  A persistent launch needs every CU for its 12-wave
- * workgroups: a GPU shared with another process's persistent kernels should
- * use 0. */
+/* the layer loop's form, as a request 0..7 (clamped): 0 five launches per
+ * layer; 1 (default, "auto") the form measured fastest (profiles/r4: 5 at
+ * C = 768, 6 at C >= 1024, else 3); 2 one persistent launch per layer
+ * (hpa_decode_layer: attention -> attproj -> fc -> fcproj -> next qkv); 3 the
+ * decode attention's own launch + one persistent launch of the GEMM chain
+ * (attproj -> fc -> fcproj -> next qkv) in 4-wave units; 4 the chain in round
+ * 3's wide units (C = 768, else 3); 5 chain form 6: every phase in 12-wave
+ * units of T tiles, one per workgroup, 16-byte epilogues, waits per row block
+ * (C = 768, else 3); 6 chain form 8: streamed-weight units for MFMA-bound
+ * wide layers (C = 768 / 1024 / 1280 / 1600: GPT-2 124M to XL); 7 the
+ * pipelined halves (hpa_decode_pipe, hpa_pipe.hip): the step's first launch,
+ * ONE persistent launch of every layer with the batch in two halves (the GEMM
+ * chain of one half on g_cus CUs beside the attention of the other on the
+ * rest), the logits; bit-identical to 5, which runs where they do not apply
+ * (they need GPT-2 124M shapes, fp32 weights and pool, 17..64 rows) and in
+ * traced steps.  2, 4 and 7 are in A/B builds (-DHPA_AB) only: the product
+ * build runs five launches for 2 and 4, and 5 for 7.  With bf16 weights every
+ * request but 0 is the bf16-weight chain (C = 768, B <= 256); with an fp8 pool
+ * only 1 and 5 leave five launches (gpt2_decode_init_ex).  A request that
+ * does not apply to the shape or the device runs five launches.  What a
+ * request becomes is decided by gpt2_decode_layer_plan alone.
+ * HPA_LAYER_KERNEL=0..7 in the environment sets the default.  A persistent
+ * launch needs every CU for its 12-wave workgroups: a GPU shared with another
+ * process's persistent kernels should use 0. */
 int  gpt2_decode_set_layer_kernel(GPT2* model, int enable);
-/* 7: the pipelined halves (hpa_decode_pipe, hpa_pipe.hip): the step's first
- * launch, ONE persistent launch of every layer with the batch in two halves
- * (the GEMM chain of one half on g_cus CUs beside the attention of the other
- * on the rest), the logits; bit-identical to form 5.  GPT-2 124M shapes, fp32
- * weights and pool, 17..64 rows (else form 5).  Traced steps run form 5. */
 /* CUs of the pipelined halves' GEMM role (multiple of 8; 0: the default, 64) */
 int  gpt2_decode_set_pipe_split(GPT2* model, int g_cus);
-/* the form in use: 0 five launches, 1 full persistent layer, 2 attention
- * launch + persistent chain of 4-wave units, 3 the chain in wide / multi-tile
- * units (forms 4..6 of gpt2_decode_set_layer_kernel), 4 the bf16-weight
- * chain, 5 the pipelined halves (form 7) */
+/* the form in use (the plan's `form`): 0 five launches, 1 full persistent
+ * layer, 2 attention launch + persistent chain of 4-wave units, 3 attention
+ * launch + the chain in wide / multi-tile / streamed-weight units (requests
+ * 4..6, and 7 where the halves do not apply), 4 the bf16-weight chain, 5 the
+ * pipelined halves */
 int  gpt2_decode_layer_kernel(GPT2* model);
+/* The plan of a decode step's layer loop: the one function that decides what
+ * a request becomes, pure (every input by value; no device, allocation or
+ * global), so every routing rule can be checked without a GPU.  request 0..7
+ * as gpt2_decode_set_layer_kernel; B the engine's batch (eligibility) and
+ * pick_B the batch its shape picks follow (gpt2_decode_set_global_batch, else
+ * B); kv_dtype HPA_F32 / HPA_BF16 / HPA_FP8; w_bf16 1 for bf16 weights (fp32
+ * weights are taken to have their LN-fold pack, as gpt2_decode_init* makes
+ * it); num_cus the device's CU count (hpa_device_info).  out5:
+ *   [0] form         what gpt2_decode_layer_kernel reports (0..5, above)
+ *   [1] chain        HpaLayerArgs.chain_only of forms 1..3, 5 (0, 1, 2..6, 8)
+ *   [2] splits       attention ranges inside the layer launch (1 unless form 1)
+ *   [3] first        the step's first launch: 0 the embed kernel (+ the qkv(0)
+ *                    GEMM), 1 hpa_decode_first, 2 hpa_decode_chain_b16_first
+ *   [4] attn_launch  1: the decode attention is its own launch before each
+ *                    layer launch (forms 2..5)
+ * Returns 0 (1: out5 NULL).  The answer is the build's: an A/B build also
+ * yields forms 1 and 5 and chains 2..5. */
+int  gpt2_decode_layer_plan(int request, int B, int pick_B, int C, int num_heads, int max_ctx, int kv_dtype,
+                            int w_bf16, int num_cus, int out5[5]);
 /* waits for the queued work; 0, or the code of a timed-out in-launch wait of
  * the persistent layer (the step's outputs are then invalid), which it clears */
 int  gpt2_decode_status(GPT2* model);

@@ -664,30 +664,11 @@ __global__ __launch_bounds__(512) void decode_chain_b16_kernel(cb::Args args) {
     CB_MARK(11);
 }
 
-int g_ncu_b16 = 0;
-int num_cus_b16() {
-    if (!g_ncu_b16) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
-        g_ncu_b16 = pr.multiProcessorCount;
-    }
-    return g_ncu_b16;
-}
-
 template <int P, bool BF, bool FIRST = false>
 int launch_b16(const HpaChainB16Args* h, int G, const int* tokens = nullptr, const float* wte = nullptr,
                const float* wpe = nullptr, void* zero = nullptr, size_t zero_bytes = 0) {
-    static int resident = -1;
-    if (resident < 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, decode_chain_b16_kernel<P, BF, FIRST>, 512, 0) !=
-            hipSuccess)
-            nb = 0;
-        resident = nb;
-    }
-    HPA_REQUIRE(resident >= 1, "decode chain bf16: the workgroup does not fit a CU");
+    HPA_REQUIRE((hpa::resident_blocks<decode_chain_b16_kernel<P, BF, FIRST>>(512) >= 1),
+                "decode chain bf16: the workgroup does not fit a CU");
     const HpaKVPool* pool = h->pool;
     cb::Args a;
     a.B = h->B;
@@ -737,8 +718,7 @@ int launch_b16(const HpaChainB16Args* h, int G, const int* tokens = nullptr, con
 
 extern "C" {
 
-int hpa_decode_chain_b16_eligible(int B, int C, int num_heads) {
-    const int G = num_cus_b16();
+int hpa_decode_chain_b16_eligible_cus(int B, int C, int num_heads, int G) {
     const int R = (B + 15) / 16;
     const int RH = (R + 1) / 2, RQ = (R + 3) / 4;
     // every phase's units on a workgroup each
@@ -746,6 +726,9 @@ int hpa_decode_chain_b16_eligible(int B, int C, int num_heads) {
                    RQ * 4 * cb::NG_D <= G
                ? 1
                : 0;
+}
+int hpa_decode_chain_b16_eligible(int B, int C, int num_heads) {
+    return hpa_decode_chain_b16_eligible_cus(B, C, num_heads, hpa::num_cus());
 }
 
 int hpa_decode_chain_b16_sizes(int B, size_t* out2) {
@@ -788,19 +771,10 @@ int hpa_decode_chain_b16_first(const HpaChainB16Args* h, const int* tokens, cons
     HpaChainB16Args f = *h;
     f.layer = -1;  // K/V into layer 0's pages (layer + 1)
     f.last = 0;
-    const int G = num_cus_b16();
-    const bool bf = pool->dtype == HPA_BF16;
-    switch (pool->page_size) {
-        case 8: return bf ? launch_b16<8, true, true>(&f, G, tokens, wte, wpe, zero, zero_bytes)
-                          : launch_b16<8, false, true>(&f, G, tokens, wte, wpe, zero, zero_bytes);
-        case 16: return bf ? launch_b16<16, true, true>(&f, G, tokens, wte, wpe, zero, zero_bytes)
-                           : launch_b16<16, false, true>(&f, G, tokens, wte, wpe, zero, zero_bytes);
-        case 32: return bf ? launch_b16<32, true, true>(&f, G, tokens, wte, wpe, zero, zero_bytes)
-                           : launch_b16<32, false, true>(&f, G, tokens, wte, wpe, zero, zero_bytes);
-        case 64: return bf ? launch_b16<64, true, true>(&f, G, tokens, wte, wpe, zero, zero_bytes)
-                           : launch_b16<64, false, true>(&f, G, tokens, wte, wpe, zero, zero_bytes);
-        default: return hpa_fail(__FILE__, __LINE__, "decode chain bf16 first: page size must be 8, 16, 32 or 64");
-    }
+    const int G = hpa::num_cus();
+    return hpa::with_page_dtype(pool, "decode chain bf16 first: page size must be 8, 16, 32 or 64", [&](auto p, auto bf) {
+        return launch_b16<decltype(p)::value, decltype(bf)::value, true>(&f, G, tokens, wte, wpe, zero, zero_bytes);
+    });
 }
 
 int hpa_decode_chain_b16(const HpaChainB16Args* h) {
@@ -816,15 +790,10 @@ int hpa_decode_chain_b16(const HpaChainB16Args* h) {
                 "decode chain bf16: null operand");
     HPA_REQUIRE(h->last || (h->w_qkv && h->b_qkv && h->ln1_w && h->ln1_b && h->q_out),
                 "decode chain bf16: qkv(l+1) operands");
-    const int G = num_cus_b16();
-    const bool bf = pool->dtype == HPA_BF16;
-    switch (pool->page_size) {
-        case 8: return bf ? launch_b16<8, true>(h, G) : launch_b16<8, false>(h, G);
-        case 16: return bf ? launch_b16<16, true>(h, G) : launch_b16<16, false>(h, G);
-        case 32: return bf ? launch_b16<32, true>(h, G) : launch_b16<32, false>(h, G);
-        case 64: return bf ? launch_b16<64, true>(h, G) : launch_b16<64, false>(h, G);
-        default: return hpa_fail(__FILE__, __LINE__, "decode chain bf16: page size must be 8, 16, 32 or 64");
-    }
+    const int G = hpa::num_cus();
+    return hpa::with_page_dtype(pool, "decode chain bf16: page size must be 8, 16, 32 or 64", [&](auto p, auto bf) {
+        return launch_b16<decltype(p)::value, decltype(bf)::value>(h, G);
+    });
 }
 
 }  // extern "C"

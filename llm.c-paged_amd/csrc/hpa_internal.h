@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "hip_paged_attn.h"
 
 // Returns a nonzero status after reporting; exits when HPA_FATAL=1
@@ -28,6 +30,38 @@ hipStream_t hpa_stream();
 
 namespace hpa {
 constexpr int kWave = 64;
+
+// CUs of the current device (0: no device), read once per process
+int num_cus();
+
+// blocks per CU of Kernel at `threads` per block (occupancy API), cached per kernel
+template <auto Kernel>
+int resident_blocks(int threads) {
+    static int resident = -1;
+    if (resident < 0) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, Kernel, threads, 0) != hipSuccess) nb = 0;
+        resident = nb;
+    }
+    return resident;
+}
+
+// the launchers' template arguments from a pool: f(std::integral_constant<int, P>,
+// std::bool_constant<BF>) with P the page size (8, 16, 32 or 64) and BF = bf16
+// pool (fp32 and fp8 pools: false); any other page size fails with msg
+template <typename F>
+int with_page_dtype(const HpaKVPool* pool, const char* msg, F&& f) {
+    auto by_dtype = [&](auto p) {
+        return pool->dtype == HPA_BF16 ? f(p, std::true_type{}) : f(p, std::false_type{});
+    };
+    switch (pool->page_size) {
+        case 8: return by_dtype(std::integral_constant<int, 8>{});
+        case 16: return by_dtype(std::integral_constant<int, 16>{});
+        case 32: return by_dtype(std::integral_constant<int, 32>{});
+        case 64: return by_dtype(std::integral_constant<int, 64>{});
+        default: return hpa_fail(__FILE__, __LINE__, msg);
+    }
+}
 
 // 16-byte write-through (sc1) store / L1-bypassing (sc1) load at
 // base + byte_off (base wave-uniform, byte_off per lane, 16-B aligned): the

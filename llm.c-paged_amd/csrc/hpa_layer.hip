@@ -1800,19 +1800,6 @@ __global__ __launch_bounds__(768) void decode_chainx_kernel(KA args) {
     PL_MARK(11);
 }
 
-int g_ncu = 0;
-
-int num_cus() {
-    if (!g_ncu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
-        g_ncu = pr.multiProcessorCount;
-    }
-    return g_ncu;
-}
-
 template <int NH>
 bool shape_ok(int B, int S, int G) {
     // one unit per slot in every phase: attention B*NH*S, fc and fcproj
@@ -1868,21 +1855,9 @@ void fill_ka(const HpaLayerArgs* h, int G, KA& a) {
                            : nullptr;
 }
 
-// blocks per CU of a 768-thread instantiation (occupancy API), cached per kernel
-template <typename K>
-int resident_blocks(K kernel) {
-    static int resident = -1;
-    if (resident < 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 768, 0) != hipSuccess) nb = 0;
-        resident = nb;
-    }
-    return resident;
-}
-
 template <int NH, int P, bool BF, bool ATTN, int NB = 4, int NCD = 4, int NE = 4>
 int launch(const HpaLayerArgs* h, int G) {
-    HPA_REQUIRE(resident_blocks(decode_layer_kernel<NH, P, BF, ATTN, NB, NCD, NE>) >= 1,
+    HPA_REQUIRE((hpa::resident_blocks<decode_layer_kernel<NH, P, BF, ATTN, NB, NCD, NE>>(768) >= 1),
                 "decode layer: the persistent workgroup does not fit a CU");
     KA a;
     fill_ka(h, G, a);
@@ -1894,7 +1869,8 @@ int launch(const HpaLayerArgs* h, int G) {
 template <int P, bool BF, int TE>
 int launch_first6(const HpaLayerArgs* h, int G, const int* tokens, const float* wte, const float* wpe, void* zero,
                   size_t zero_bytes) {
-    HPA_REQUIRE(resident_blocks(decode_first6_kernel<P, BF, TE>) >= 1, "decode first: the workgroup does not fit a CU");
+    HPA_REQUIRE((hpa::resident_blocks<decode_first6_kernel<P, BF, TE>>(768) >= 1),
+                "decode first: the workgroup does not fit a CU");
     const int R = (h->B + 15) / 16;
     HPA_REQUIRE(R * 144 / TE <= G, "decode first: a unit per workgroup");
     KA a;
@@ -1926,7 +1902,7 @@ int dispatch_first6_t(const HpaLayerArgs* h, int G, const int* tokens, const flo
 
 template <int P, bool BF, int TC, int TD, int TE>
 int launch6(const HpaLayerArgs* h, int G) {
-    HPA_REQUIRE(resident_blocks(decode_chain6_kernel<P, BF, TC, TD, TE>) >= 1,
+    HPA_REQUIRE((hpa::resident_blocks<decode_chain6_kernel<P, BF, TC, TD, TE>>(768) >= 1),
                 "decode layer: the chain-6 workgroup does not fit a CU");
     const int R = (h->B + 15) / 16;
     HPA_REQUIRE(R * 48 <= G && R * 192 / TC <= G && 4 * R * 48 / TD <= G && R * 144 / TE <= G,
@@ -1963,7 +1939,7 @@ int chainx_shape(int B, int NH, int G, int xt[4], int xng[4]) {
 
 template <int NH, int P, bool BF>
 int launchx(const HpaLayerArgs* h, int G) {
-    HPA_REQUIRE(resident_blocks(decode_chainx_kernel<NH, P, BF>) >= 1,
+    HPA_REQUIRE((hpa::resident_blocks<decode_chainx_kernel<NH, P, BF>>(768) >= 1),
                 "decode layer: the chain-8 workgroup does not fit a CU");
     KA a;
     fill_ka(h, G, a);
@@ -1975,14 +1951,9 @@ int launchx(const HpaLayerArgs* h, int G) {
 
 template <int NH>
 int dispatchx(const HpaLayerArgs* h, int G) {
-    const bool bf = h->pool->dtype == HPA_BF16;
-    switch (h->pool->page_size) {
-        case 8: return bf ? launchx<NH, 8, true>(h, G) : launchx<NH, 8, false>(h, G);
-        case 16: return bf ? launchx<NH, 16, true>(h, G) : launchx<NH, 16, false>(h, G);
-        case 32: return bf ? launchx<NH, 32, true>(h, G) : launchx<NH, 32, false>(h, G);
-        case 64: return bf ? launchx<NH, 64, true>(h, G) : launchx<NH, 64, false>(h, G);
-        default: return hpa_fail(__FILE__, __LINE__, "decode layer: page size must be 8, 16, 32 or 64");
-    }
+    return hpa::with_page_dtype(h->pool, "decode layer: page size must be 8, 16, 32 or 64", [&](auto p, auto bf) {
+        return launchx<NH, decltype(p)::value, decltype(bf)::value>(h, G);
+    });
 }
 
 // tiles per unit of fc, fcproj, qkv by row blocks R: the fewest with every
@@ -1999,26 +1970,16 @@ int dispatch6_t(const HpaLayerArgs* h, int G) {
 }
 
 int dispatch6(const HpaLayerArgs* h, int G) {
-    const bool bf = h->pool->dtype == HPA_BF16;
-    switch (h->pool->page_size) {
-        case 8: return bf ? dispatch6_t<8, true>(h, G) : dispatch6_t<8, false>(h, G);
-        case 16: return bf ? dispatch6_t<16, true>(h, G) : dispatch6_t<16, false>(h, G);
-        case 32: return bf ? dispatch6_t<32, true>(h, G) : dispatch6_t<32, false>(h, G);
-        case 64: return bf ? dispatch6_t<64, true>(h, G) : dispatch6_t<64, false>(h, G);
-        default: return hpa_fail(__FILE__, __LINE__, "decode layer: page size must be 8, 16, 32 or 64");
-    }
+    return hpa::with_page_dtype(h->pool, "decode layer: page size must be 8, 16, 32 or 64", [&](auto p, auto bf) {
+        return dispatch6_t<decltype(p)::value, decltype(bf)::value>(h, G);
+    });
 }
 
 template <int NH, bool ATTN, int NB = 4, int NCD = 4, int NE = 4>
 int dispatch_p(const HpaLayerArgs* h, int G) {
-    const bool bf = h->pool->dtype == HPA_BF16;
-    switch (h->pool->page_size) {
-        case 8: return bf ? launch<NH, 8, true, ATTN, NB, NCD, NE>(h, G) : launch<NH, 8, false, ATTN, NB, NCD, NE>(h, G);
-        case 16: return bf ? launch<NH, 16, true, ATTN, NB, NCD, NE>(h, G) : launch<NH, 16, false, ATTN, NB, NCD, NE>(h, G);
-        case 32: return bf ? launch<NH, 32, true, ATTN, NB, NCD, NE>(h, G) : launch<NH, 32, false, ATTN, NB, NCD, NE>(h, G);
-        case 64: return bf ? launch<NH, 64, true, ATTN, NB, NCD, NE>(h, G) : launch<NH, 64, false, ATTN, NB, NCD, NE>(h, G);
-        default: return hpa_fail(__FILE__, __LINE__, "decode layer: page size must be 8, 16, 32 or 64");
-    }
+    return hpa::with_page_dtype(h->pool, "decode layer: page size must be 8, 16, 32 or 64", [&](auto p, auto bf) {
+        return launch<NH, decltype(p)::value, decltype(bf)::value, ATTN, NB, NCD, NE>(h, G);
+    });
 }
 
 template <int NH>
@@ -2070,23 +2031,27 @@ int dispatch(const HpaLayerArgs* h, int G) {
 
 extern "C" {
 
-int hpa_decode_layer_eligible(int B, int C, int num_heads, int splits) {
-    const int G = num_cus();
+int hpa_decode_layer_eligible_cus(int B, int C, int num_heads, int splits, int G) {
     if (G <= 0 || C != 64 * num_heads) return 0;
     if (num_heads == 12) return shape_ok<12>(B, splits, G) ? 1 : 0;
     if (num_heads == 2) return shape_ok<2>(B, splits, G) ? 1 : 0;
     return 0;
 }
+int hpa_decode_layer_eligible(int B, int C, int num_heads, int splits) {
+    return hpa_decode_layer_eligible_cus(B, C, num_heads, splits, hpa::num_cus());
+}
 
 // the split count measured best for the stand-alone attention
 // (hpa_attn_pick_splits: a range of >= 4 tiles per 4-wave unit; short ranges
 // pay the merge), halved until every unit has a slot (B*NH*S <= 3 x CUs)
-int hpa_decode_layer_pick_splits(int B, int num_heads, int max_ctx) {
-    const int G = num_cus();
+int hpa_decode_layer_pick_splits_cus(int B, int num_heads, int max_ctx, int G) {
     if (G <= 0 || B <= 0 || num_heads <= 0) return 1;
     int s = hpa_attn_pick_splits(B, num_heads, max_ctx, G);
     while (s > 1 && (long)B * num_heads * s > 3L * G) s /= 2;
     return s;
+}
+int hpa_decode_layer_pick_splits(int B, int num_heads, int max_ctx) {
+    return hpa_decode_layer_pick_splits_cus(B, num_heads, max_ctx, hpa::num_cus());
 }
 
 int hpa_decode_layer_sizes(int B, int C, int num_heads, int splits, size_t* out3) {
@@ -2140,8 +2105,7 @@ int hpa_decode_layer_trace(unsigned long long* host, int layers) {
 
 // the chain forms 6 (C = 768) and 8 (C = 768, 1024, 1280 or 1600): B <= 64, fp32 or
 // bf16 pool (form 6: fp8 too), a unit per workgroup in every phase
-int hpa_decode_chain_eligible(int B, int C, int num_heads, int form) {
-    const int G = num_cus();
+int hpa_decode_chain_eligible_cus(int B, int C, int num_heads, int form, int G) {
     if (G <= 0 || C != 64 * num_heads || B < 1 || B > 64) return 0;
     if (form == 6) {
         if (num_heads != 12) return 0;
@@ -2154,6 +2118,9 @@ int hpa_decode_chain_eligible(int B, int C, int num_heads, int form) {
         return chainx_shape(B, num_heads, G, xt, xng) == 0 ? 1 : 0;
     }
     return 0;
+}
+int hpa_decode_chain_eligible(int B, int C, int num_heads, int form) {
+    return hpa_decode_chain_eligible_cus(B, C, num_heads, form, hpa::num_cus());
 }
 
 int hpa_decode_first(const HpaLayerArgs* h, const int* tokens, const float* wte, const float* wpe, void* zero,
@@ -2170,19 +2137,10 @@ int hpa_decode_first(const HpaLayerArgs* h, const int* tokens, const float* wte,
                 "decode first: null operand");
     HPA_REQUIRE(zero_bytes % 16 == 0 && ((size_t)zero & 15) == 0 && zero_bytes / 16 <= 0x7fffffff,
                 "decode first: the zeroed block must be whole 16-byte granules");
-    const int G = num_cus();
-    const bool bf = pool->dtype == HPA_BF16;
-    switch (pool->page_size) {
-        case 8: return bf ? dispatch_first6_t<8, true>(h, G, tokens, wte, wpe, zero, zero_bytes)
-                          : dispatch_first6_t<8, false>(h, G, tokens, wte, wpe, zero, zero_bytes);
-        case 16: return bf ? dispatch_first6_t<16, true>(h, G, tokens, wte, wpe, zero, zero_bytes)
-                           : dispatch_first6_t<16, false>(h, G, tokens, wte, wpe, zero, zero_bytes);
-        case 32: return bf ? dispatch_first6_t<32, true>(h, G, tokens, wte, wpe, zero, zero_bytes)
-                           : dispatch_first6_t<32, false>(h, G, tokens, wte, wpe, zero, zero_bytes);
-        case 64: return bf ? dispatch_first6_t<64, true>(h, G, tokens, wte, wpe, zero, zero_bytes)
-                           : dispatch_first6_t<64, false>(h, G, tokens, wte, wpe, zero, zero_bytes);
-        default: return hpa_fail(__FILE__, __LINE__, "decode first: page size must be 8, 16, 32 or 64");
-    }
+    const int G = hpa::num_cus();
+    return hpa::with_page_dtype(pool, "decode first: page size must be 8, 16, 32 or 64", [&](auto p, auto bf) {
+        return dispatch_first6_t<decltype(p)::value, decltype(bf)::value>(h, G, tokens, wte, wpe, zero, zero_bytes);
+    });
 }
 
 int hpa_decode_layer(const HpaLayerArgs* h) {
@@ -2201,7 +2159,7 @@ int hpa_decode_layer(const HpaLayerArgs* h) {
                 "decode layer: null operand");
     HPA_REQUIRE(h->last || (h->w_qkv && h->qkv_c1 && h->qkv_c2 && h->q_out), "decode layer: qkv(l+1) operands");
     HPA_REQUIRE(h->splits >= 1 && h->splits <= HPA_ATTN_MAX_SPLITS, "decode layer: splits 1..16");
-    const int G = num_cus();
+    const int G = hpa::num_cus();
     if (h->chain_only == 6 || h->chain_only == 8) {
         HPA_REQUIRE(hpa_decode_chain_eligible(h->B, h->C, h->num_heads, h->chain_only),
                     "decode layer: chain form not supported for this shape");

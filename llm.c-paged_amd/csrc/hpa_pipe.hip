@@ -702,35 +702,12 @@ __global__ __launch_bounds__(768) void decode_pipe_kernel(PA args) {
         a_role<P, HR, T>(a, sm);
 }
 
-int g_ncu = 0;
-int num_cus() {
-    if (!g_ncu) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return 0;
-        hipDeviceProp_t pr;
-        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
-        g_ncu = pr.multiProcessorCount;
-    }
-    return g_ncu;
-}
-
-template <typename K>
-int resident_blocks(K kernel) {
-    static int resident = -1;
-    if (resident < 0) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, 768, 0) != hipSuccess) nb = 0;
-        resident = nb;
-    }
-    return resident;
-}
-
 constexpr int kT = 3;  // tiles per unit of fc / fcproj / qkv: 64 / 64 / 48 units
 
 template <int P, int HR>
 int launch_pipe(PA& a) {
-    auto k = decode_pipe_kernel<P, HR, kT>;
-    HPA_REQUIRE(resident_blocks(k) >= 1, "decode pipe: the workgroup does not fit a CU");
+    HPA_REQUIRE((hpa::resident_blocks<decode_pipe_kernel<P, HR, kT>>(768) >= 1),
+                "decode pipe: the workgroup does not fit a CU");
     decode_pipe_kernel<P, HR, kT><<<a.NG + a.NA, 768, 0, hpa_stream()>>>(a);
     HPA_LAUNCH_CHECK();
     return 0;
@@ -752,7 +729,7 @@ bool pipe_shape(int B, int ncu, int g_cus, int* HR) {
 
 extern "C" {
 
-int hpa_decode_pipe_eligible(int B, int C_, int num_heads, int kv_dtype) {
+int hpa_decode_pipe_eligible_cus(int B, int C_, int num_heads, int kv_dtype, int ncu) {
 #ifndef HPA_AB
     // measured slower than chain form 6 at every batch (profiles/r6/pipe/):
     // A/B builds only, like the other forms that lost
@@ -760,11 +737,14 @@ int hpa_decode_pipe_eligible(int B, int C_, int num_heads, int kv_dtype) {
     (void)C_;
     (void)num_heads;
     (void)kv_dtype;
+    (void)ncu;
     return 0;
 #endif
     int hr = 0;
-    const int ncu = num_cus();
     return C_ == C && num_heads == NH && kv_dtype == HPA_F32 && ncu > 0 && pipe_shape(B, ncu, kDefaultG, &hr) ? 1 : 0;
+}
+int hpa_decode_pipe_eligible(int B, int C_, int num_heads, int kv_dtype) {
+    return hpa_decode_pipe_eligible_cus(B, C_, num_heads, kv_dtype, hpa::num_cus());
 }
 
 // trace build only: the stamps of the last launch ([2 * layers][256][12] u64,
@@ -810,7 +790,7 @@ int hpa_decode_pipe(const HpaPipeArgs* h) {
     HPA_REQUIRE(h->layer_ctr_ints >= (size_t)kLayerInts, "decode pipe: counter block per layer too small");
     const size_t layer_bytes = pool->layer_elems * pool->elem_bytes;
     HPA_REQUIRE(layer_bytes < 0x7fffffffull, "decode pipe: a layer's pages must be < 2 GiB (32-bit offsets)");
-    const int ncu = num_cus();
+    const int ncu = hpa::num_cus();
     const int g = h->g_cus > 0 ? h->g_cus : kDefaultG;
     int HR = 0;
     HPA_REQUIRE(pipe_shape(h->B, ncu, g, &HR), "decode pipe: shape (17..64 rows in two halves, CU split)");
@@ -842,17 +822,9 @@ int hpa_decode_pipe(const HpaPipeArgs* h) {
     a.ctr = h->counters;
     a.err = h->err;
     a.err_sticky = h->err_sticky;
-#define HPA_PIPE_CASE(PS)                                              \
-    case PS:                                                           \
-        return HR == 2 ? launch_pipe<PS, 2>(a) : launch_pipe<PS, 1>(a);
-    switch (pool->page_size) {
-        HPA_PIPE_CASE(8)
-        HPA_PIPE_CASE(16)
-        HPA_PIPE_CASE(32)
-        HPA_PIPE_CASE(64)
-        default: return hpa_fail(__FILE__, __LINE__, "decode pipe: page size must be 8, 16, 32 or 64");
-    }
-#undef HPA_PIPE_CASE
+    return hpa::with_page_dtype(pool, "decode pipe: page size must be 8, 16, 32 or 64", [&](auto p, auto) {
+        return HR == 2 ? launch_pipe<decltype(p)::value, 2>(a) : launch_pipe<decltype(p)::value, 1>(a);
+    });
 #endif
 }
 

@@ -30,6 +30,18 @@ constexpr int kMaxDevices = 64;
 hipStream_t g_dev_streams[kMaxDevices];
 hipStream_t hpa_stream() { return g_stream; }
 
+int hpa::num_cus() {
+    static int ncu = 0;
+    if (!ncu) {
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return 0;
+        hipDeviceProp_t pr;
+        if (hipGetDeviceProperties(&pr, dev) != hipSuccess) return 0;
+        ncu = pr.multiProcessorCount;
+    }
+    return ncu;
+}
+
 // Infinity-Cache warm-up (hpa_l3_prefetch): read [p, p + n float4) with the
 // default cache policy and drop it.  The 256 MiB die-level cache keeps those
 // lines for a later kernel while the bytes loaded or stored in between stay

@@ -604,6 +604,20 @@ typedef struct {
     int k, last, pending[2];
 } DecShard;
 
+/* how a decode step's layer loop is launched: filled by dec_plan, the one
+ * place that decides it, and read by everything that launches (dec_launch,
+ * dec_layer) or allocates for it (dec_layer_workspace) */
+typedef struct {
+    int form;        /* what gpt2_decode_layer_kernel reports: 0 five launches, 1 full persistent layer,
+                        2 attention launch + 4-wave chain, 3 attention launch + chain form `chain`,
+                        4 bf16-weight chain, 5 pipelined halves */
+    int chain;       /* HpaLayerArgs.chain_only for forms 1..3, 5 (0, 1, 2..6, 8); unused otherwise */
+    int splits;      /* attention ranges inside the layer launch (1 unless form 1) */
+    int first;       /* the step's first launch: 0 embed kernel (+ the qkv(0) GEMM), 1 hpa_decode_first,
+                        2 hpa_decode_chain_b16_first */
+    int attn_launch; /* 1: the decode attention is its own launch before each layer launch */
+} DecPlan;
+
 struct GPT2Decode {
     int B, P, max_ctx, max_pages, Mp;
     HpaKVPool pool;
@@ -640,8 +654,10 @@ struct GPT2Decode {
     float* d_wpack;   /* packed qkvw, attprojw, fcw, fcprojw of every layer, then wte */
     int w_bf16;       /* weights packed bf16 (hpa_pack_frag_bf16; offsets in elements) */
     size_t wpack_off[5]; /* per-layer offsets (0..3) and wte offset (4) */
+    size_t wpack_layer;  /* elements of one layer's four packs */
     float* d_fold;    /* LN folded into qkvw / fcw (hpa_ln_fold_pack): per layer c1, c2 of
-                         qkv [3C] [3C] then fc [4C] [4C]; NULL: LN applied on the operand path */
+                         qkv [3C] [3C] then fc [4C] [4C]; NULL: LN applied on the operand path
+                         (addresses: dec_layer_ops) */
     int fwaves[5];    /* waves per workgroup: qkv, attproj, fc, fcproj, logits */
     int frb[5];       /* 16-row blocks per workgroup, same order */
     int fct[5];       /* 16-column tiles per workgroup, same order */
@@ -662,23 +678,21 @@ struct GPT2Decode {
     double prof_ms;
     long prof_launches;
     DecShard* shard;
-    /* persistent layer (hpa_decode_layer): one launch per layer */
-    int pl_want;      /* gpt2_decode_set_layer_kernel: 0 off, 1 auto, 2 full, 3 chain, 4 chain with wide units,
+    /* the layer loop's form: the request, and what dec_plan makes of it */
+    int pl_want;      /* gpt2_decode_set_layer_kernel: 0 five launches, 1 auto, 2 full persistent layer,
+                         3 chain of 4-wave units, 4 chain of wide units (chain_only 2..5 by batch),
                          5 chain form 6 (12-wave multi-tile units), 6 chain form 8 (streamed-weight
-                         units, C = 768 / 1024 / 1280 / 1600) */
-    int pl_on;        /* in use: 0 five launches, 1 full persistent layer, 2 attention launch + chain,
-                         3 attention launch + chain of wide units (hpa_layer.hip NWU = pl_nwu),
-                         4 attention launch + the bf16-weight chain (hpa_chain_b16.hip) */
-    int pl_wform;     /* wide-unit form of the chain (HpaLayerArgs.chain_only 2..6, 8), else 1 */
-    int pl_splits;
+                         units, C = 768 / 1024 / 1280 / 1600), 7 the pipelined halves */
+    DecPlan plan;     /* in use (dec_layer_setup); five launches while a step is profiled */
     int pl_global_B;  /* gpt2_decode_set_global_batch: the batch the picks follow (<= 64); else 0 */
-    float* pl_rec;
+    float* pl_rec;    /* the full persistent layer's split records, sized for pl_rec_splits ranges */
+    int pl_rec_splits;
     float* pl_slab;   /* [pl_slab_n] */
     size_t pl_slab_n;
     int* pl_ctr;      /* the step's error word (DEC_ERR_INTS), then [L][pl_ctr_ints]; zeroed at the start of
                          every step */
     size_t pl_ctr_ints;
-    /* pipelined halves (hpa_decode_pipe, pl_on 5): the per-layer operand
+    /* pipelined halves (hpa_decode_pipe, plan.form 5): the per-layer operand
      * table on the device, the fcproj partials, the GEMM role's CUs */
     HpaPipeLayer* d_pipe_lay;
     float* pipe_slab;
@@ -813,6 +827,48 @@ void gpt2_decode_free(GPT2* model) {
     }
 }
 
+/* packed weights at element offset off (fp32 or bf16 pack) */
+static const float* wpack_at(const GPT2Decode* d, size_t off) {
+    return d->w_bf16 ? (const float*)((const unsigned short*)d->d_wpack + off) : d->d_wpack + off;
+}
+
+/* layer l's operands: where dec_init_weights packs them and every launch
+ * reads them.  Packed weights: layer l's four packs at wpack_layer * l +
+ * wpack_off[0..3].  d_fold: per layer DEC_FOLD_C x C floats, qkv c1 [3C], c2
+ * [3C] (the folded bias), fc c1 [4C], c2 [4C]; NULL pointers without the
+ * fold pack. */
+#define DEC_FOLD_C 14 /* 3 + 3 + 4 + 4 */
+typedef struct {
+    const float *w_qkv, *w_ap, *w_fc, *w_fp;
+    const float *qkv_c1, *qkv_c2, *fc_c1, *fc_c2;
+    const float *b_qkv, *b_ap, *b_fc, *b_fp; /* checkpoint biases */
+    const float *ln1_w, *ln1_b, *ln2_w, *ln2_b;
+} DecLayerOps;
+
+static DecLayerOps dec_layer_ops(const GPT2* model, const GPT2Decode* d, int l) {
+    const ParameterTensors* w = &model->params;
+    const size_t C = model->config.channels, lc = (size_t)l * C;
+    const float* fl = d->d_fold ? d->d_fold + DEC_FOLD_C * lc : NULL;
+    DecLayerOps o;
+    o.w_qkv = wpack_at(d, d->wpack_layer * l + d->wpack_off[0]);
+    o.w_ap = wpack_at(d, d->wpack_layer * l + d->wpack_off[1]);
+    o.w_fc = wpack_at(d, d->wpack_layer * l + d->wpack_off[2]);
+    o.w_fp = wpack_at(d, d->wpack_layer * l + d->wpack_off[3]);
+    o.qkv_c1 = fl;
+    o.qkv_c2 = fl ? fl + 3 * C : NULL;
+    o.fc_c1 = fl ? fl + 6 * C : NULL;
+    o.fc_c2 = fl ? fl + 10 * C : NULL;
+    o.b_qkv = w->qkvb + 3 * lc;
+    o.b_ap = w->attprojb + lc;
+    o.b_fc = w->fcb + 4 * lc;
+    o.b_fp = w->fcprojb + lc;
+    o.ln1_w = w->ln1w + lc;
+    o.ln1_b = w->ln1b + lc;
+    o.ln2_w = w->ln2w + lc;
+    o.ln2_b = w->ln2b + lc;
+    return o;
+}
+
 /* frag-packed weights (packed once; the weights stay also in checkpoint
  * layout for the embedding gather and the reference API), frag-layout
  * activations, LN statistics, launch shapes */
@@ -822,7 +878,7 @@ static int dec_init_weights(GPT2* model, GPT2Decode* d) {
     const ParameterTensors* w = &model->params;
     const size_t e_qkv = hpa_frag_elems(3 * C, C), e_ap = hpa_frag_elems(C, C);
     const size_t e_fc = hpa_frag_elems(4 * C, C), e_fp = hpa_frag_elems(C, 4 * C);
-    const size_t e_layer = e_qkv + e_ap + e_fc + e_fp;
+    const size_t e_layer = d->wpack_layer = e_qkv + e_ap + e_fc + e_fp;
     d->wpack_off[0] = 0;
     d->wpack_off[1] = e_qkv;
     d->wpack_off[2] = e_qkv + e_ap;
@@ -832,34 +888,32 @@ static int dec_init_weights(GPT2* model, GPT2Decode* d) {
     d->d_wpack = (float*)hpa_malloc(total * (d->w_bf16 ? 2 : 4));
     if (!d->d_wpack) return 1;
     if (d->w_bf16) { /* bf16 weights: same element offsets, 2 bytes each; LN on the operand path */
-        unsigned short* b16 = (unsigned short*)d->d_wpack;
         for (int l = 0; l < L; l++) {
-            unsigned short* base = b16 + e_layer * l;
+            const DecLayerOps o = dec_layer_ops(model, d, l);
             const size_t lc = (size_t)l * C;
-            if (hpa_pack_frag_bf16(w->qkvw + lc * 3 * C, 3 * C, C, C, base + d->wpack_off[0]) ||
-                hpa_pack_frag_bf16(w->attprojw + lc * C, C, C, C, base + d->wpack_off[1]) ||
-                hpa_pack_frag_bf16(w->fcw + lc * 4 * C, 4 * C, C, C, base + d->wpack_off[2]) ||
-                hpa_pack_frag_bf16(w->fcprojw + lc * 4 * C, C, 4 * C, 4 * C, base + d->wpack_off[3]))
+            if (hpa_pack_frag_bf16(w->qkvw + lc * 3 * C, 3 * C, C, C, (unsigned short*)o.w_qkv) ||
+                hpa_pack_frag_bf16(w->attprojw + lc * C, C, C, C, (unsigned short*)o.w_ap) ||
+                hpa_pack_frag_bf16(w->fcw + lc * 4 * C, 4 * C, C, C, (unsigned short*)o.w_fc) ||
+                hpa_pack_frag_bf16(w->fcprojw + lc * 4 * C, C, 4 * C, 4 * C, (unsigned short*)o.w_fp))
                 return 1;
         }
-        if (hpa_pack_frag_bf16(w->wte, V, C, C, b16 + d->wpack_off[4])) return 1;
+        if (hpa_pack_frag_bf16(w->wte, V, C, C, (unsigned short*)wpack_at(d, d->wpack_off[4]))) return 1;
         for (int i = 0; i < 5; i++) d->fwaves[i] = d->frb[i] = d->fct[i] = 0; /* by (M, N, K) in the library */
         return 0;
     }
     /* LN1 / LN2 folded into the qkv / fc weights: the GEMM then starts on x
      * as it stands and the row statistics are needed only in its epilogue */
-    d->d_fold = (float*)hpa_malloc((size_t)L * 14 * C * 4);
+    d->d_fold = (float*)hpa_malloc((size_t)L * DEC_FOLD_C * C * 4);
     if (!d->d_fold) return 1;
     for (int l = 0; l < L; l++) {
-        float* base = d->d_wpack + e_layer * l;
+        const DecLayerOps o = dec_layer_ops(model, d, l);
         const size_t lc = (size_t)l * C;
-        float* fl = d->d_fold + (size_t)l * 14 * C;
-        if (hpa_ln_fold_pack(w->qkvw + lc * 3 * C, 3 * C, C, w->ln1w + lc, w->ln1b + lc, w->qkvb + 3 * lc,
-                             base + d->wpack_off[0], fl, fl + 3 * C) ||
-            hpa_pack_frag(w->attprojw + lc * C, C, C, C, base + d->wpack_off[1]) ||
-            hpa_ln_fold_pack(w->fcw + lc * 4 * C, 4 * C, C, w->ln2w + lc, w->ln2b + lc, w->fcb + 4 * lc,
-                             base + d->wpack_off[2], fl + 6 * C, fl + 10 * C) ||
-            hpa_pack_frag(w->fcprojw + lc * 4 * C, C, 4 * C, 4 * C, base + d->wpack_off[3]))
+        if (hpa_ln_fold_pack(w->qkvw + lc * 3 * C, 3 * C, C, o.ln1_w, o.ln1_b, o.b_qkv, (float*)o.w_qkv,
+                             (float*)o.qkv_c1, (float*)o.qkv_c2) ||
+            hpa_pack_frag(w->attprojw + lc * C, C, C, C, (float*)o.w_ap) ||
+            hpa_ln_fold_pack(w->fcw + lc * 4 * C, 4 * C, C, o.ln2_w, o.ln2_b, o.b_fc, (float*)o.w_fc,
+                             (float*)o.fc_c1, (float*)o.fc_c2) ||
+            hpa_pack_frag(w->fcprojw + lc * 4 * C, C, 4 * C, 4 * C, (float*)o.w_fp))
             return 1;
     }
     if (hpa_pack_frag(w->wte, V, C, C, d->d_wpack + d->wpack_off[4])) return 1;
@@ -936,168 +990,171 @@ static int dec_set_splits(GPT2Decode* d, int splits) {
     return 0;
 }
 
-static const float* wpack_at(const GPT2Decode* d, size_t off);
+#ifndef DEC_FIRST_LAUNCH
+#define DEC_FIRST_LAUNCH 1 /* A/B builds: 0 = the embed kernel + the one-shot qkv(0) GEMM */
+#endif
 
-/* the bf16-weight chain's workspace (hpa_chain_b16.hip: B <= 256, C = 768,
- * 12 heads): the fcproj K-part partials and the per-layer counter blocks */
-static int dec_chain_b16_setup(GPT2* model, GPT2Decode* d) {
-    const GPT2Config c = model->config;
-    size_t sz[2];
-    if (!hpa_decode_chain_b16_eligible(d->B, c.channels, c.num_heads)) return 0;
-    if (hpa_decode_chain_b16_sizes(d->B, sz)) return 1;
-    if (!d->pl_slab || d->pl_slab_n < sz[0]) {
-        hpa_free(d->pl_slab);
-        d->pl_slab_n = sz[0];
-        d->pl_slab = (float*)hpa_malloc(sz[0] * sizeof(float));
+/* The layer loop's form for a request (gpt2_decode_set_layer_kernel, 0..7):
+ * every rule in one place, every input by value -- no device, no allocation,
+ * no global (gpt2_decode_layer_plan exports it; tests/test_layer_plan.py
+ * holds its table).  B is the engine's own batch, on which eligibility is
+ * tested; pick_B the batch the picks follow (dec_pick_B), which sets the
+ * widths.  full_splits > 0 overrides the full persistent layer's ranges. */
+static DecPlan dec_plan(int want, int B, int pick_B, int C, int num_heads, int max_ctx, int kv_dtype, int w_bf16,
+                        int have_fold, int num_cus, int ab_build, int full_splits) {
+    const DecPlan five = {0, 0, 1, 0, 0};
+    /* an fp8 pool's K/V are appended by chain form 6 (with the step's first
+     * launch) and by the GEMM launches' shared epilogue only: auto and form 5
+     * give chain form 6 where it applies, every other pick -- the bf16 chain
+     * included -- runs five launches per layer */
+    if (kv_dtype == HPA_FP8 && (w_bf16 || (want != 1 && want != 5) || num_heads != 12)) return five;
+    /* bf16 weights (BASELINE config 5): the bf16 chain (hpa_chain_b16.hip),
+     * B <= 256, in place of four GEMM launches per layer */
+    if (want && w_bf16) {
+        const DecPlan b16 = {4, 0, 1, DEC_FIRST_LAUNCH ? 2 : 0, 1};
+        return hpa_decode_chain_b16_eligible_cus(B, C, num_heads, num_cus) ? b16 : five;
     }
-    if (!d->pl_ctr || d->pl_ctr_ints < sz[1]) {
-        hpa_free(d->pl_ctr);
-        d->pl_ctr_ints = sz[1];
-        d->pl_ctr = (int*)hpa_malloc((DEC_ERR_INTS + (size_t)c.num_layers * sz[1]) * sizeof(int));
+    if (!want || w_bf16 || !have_fold) return five;
+    if (pick_B > 64) return five;
+    /* 1 = auto, the form measured fastest (round 4, profiles/r4/forms.txt):
+     * chain form 6 at C = 768 (B = 64 / 8: 1.1106 / 0.4334 ms per step
+     * against the round-3 wide units' 1.1476 / 0.4510), chain form 8 at C >=
+     * 1024 (GPT-2 XL: 9.91 vs 10.29 ms for five launches), else the chain of
+     * 4-wave units */
+    DecPlan p = {2, 1, 1, 0, 1}; /* the attention launch + the chain of 4-wave units */
+    switch (want) {
+        case 2: p.form = 1; p.chain = 0; p.attn_launch = 0; break; /* the full persistent layer */
+        case 3: break;
+        case 4: /* round 3's wide units, widths by row blocks: chain_only 2..5 */
+            if (num_heads == 12) { p.form = 3; p.chain = 1 + (pick_B + 15) / 16; }
+            break;
+        case 5: /* form 6 (12-wave multi-tile units) */
+        case 7: /* the pipelined halves over chain form 6's units (form 6 where they do not apply) */
+            if (num_heads == 12) { p.form = 3; p.chain = 6; }
+            break;
+        case 6: p.form = 3; p.chain = 8; break; /* form 8: streamed-weight units (C = 768 .. 1600) */
+        default: /* auto */
+            if (num_heads == 12) { p.form = 3; p.chain = 6; }
+            else if (C >= 1024) { p.form = 3; p.chain = 8; }
+            break;
     }
-    if (!d->pl_slab || !d->pl_ctr) return 1;
-    d->pl_on = 4;
+    /* the full persistent layer (2) and the wide-unit chains (4) measured
+     * slower than the forms picked here: A/B builds only (hpa_build_flags) */
+    if (!ab_build && (p.form == 1 || (p.chain >= 2 && p.chain <= 5))) return five;
+    if (p.form == 1) /* no attention phase otherwise: no split records */
+        p.splits = full_splits > 0 ? full_splits : hpa_decode_layer_pick_splits_cus(pick_B, num_heads, max_ctx, num_cus);
+    if (p.chain >= 6 ? !hpa_decode_chain_eligible_cus(B, C, num_heads, p.chain, num_cus)
+                     : !hpa_decode_layer_eligible_cus(B, C, num_heads, p.splits, num_cus))
+        return five;
+    /* chain form 6 (and form 8 at C = 768, which sums as form 6): embed +
+     * qkv(0) + the counter zeroing in one launch */
+    p.first = DEC_FIRST_LAUNCH && (p.chain == 6 || (p.chain == 8 && num_heads == 12));
+    if (want == 7 && p.chain == 6 && hpa_decode_pipe_eligible_cus(B, C, num_heads, kv_dtype, num_cus)) p.form = 5;
+    return p;
+}
+
+int gpt2_decode_layer_plan(int request, int B, int pick_B, int C, int num_heads, int max_ctx, int kv_dtype,
+                           int w_bf16, int num_cus, int out5[5]) {
+    if (!out5) return 1;
+    const DecPlan p = dec_plan(request < 0 ? 0 : request > 7 ? 7 : request, B, pick_B, C, num_heads, max_ctx,
+                               kv_dtype, w_bf16, !w_bf16, num_cus, hpa_build_flags() & 1, 0);
+    out5[0] = p.form; out5[1] = p.chain; out5[2] = p.splits; out5[3] = p.first; out5[4] = p.attn_launch;
     return 0;
 }
 
-/* the pipelined halves (pl_on 5) where hpa_decode_pipe applies: the
- * per-layer operand table (the pointers dec_layer hands chain form 6), the
- * fcproj partials, and counter blocks of at least its size */
-static int dec_pipe_setup(GPT2* model, GPT2Decode* d) {
+/* grow-or-keep of one workspace buffer */
+static void dec_grow_floats(float** buf, size_t* have, size_t need) {
+    if (*buf && *have >= need) return;
+    hpa_free(*buf);
+    *have = need;
+    *buf = (float*)hpa_malloc(need * sizeof(float));
+}
+
+/* the step's error word and L counter blocks of `ints` each */
+static void dec_grow_counters(GPT2Decode* d, int L, size_t ints) {
+    if (d->pl_ctr && d->pl_ctr_ints >= ints) return;
+    hpa_free(d->pl_ctr);
+    d->pl_ctr_ints = ints;
+    d->pl_ctr = (int*)hpa_malloc((DEC_ERR_INTS + (size_t)L * ints) * sizeof(int));
+}
+
+/* what plan p's launches need beside the engine's buffers: split records,
+ * K-part partials and counter blocks of the persistent forms (buffers are
+ * kept across plans and grown where a form needs more), and the pipelined
+ * halves' per-layer operand table (the pointers dec_layer hands chain form 6) */
+static int dec_layer_workspace(GPT2* model, GPT2Decode* d, const DecPlan* p) {
     const GPT2Config c = model->config;
-    const ParameterTensors* w = &model->params;
-    const int C = c.channels, L = c.num_layers;
-    if (!hpa_decode_pipe_eligible(d->B, C, c.num_heads, d->pool.dtype)) return 0; /* form 6 stays */
-    size_t sz[2];
-    if (hpa_decode_pipe_sizes(d->B, sz)) return 1;
-    if (!d->pipe_slab || d->pipe_slab_n < sz[0]) {
-        hpa_free(d->pipe_slab);
-        d->pipe_slab_n = sz[0];
-        d->pipe_slab = (float*)hpa_malloc(sz[0] * sizeof(float));
+    const int L = c.num_layers;
+    if (!p->form) return 0;
+    if (p->form == 4) {
+        size_t sz[2];
+        if (hpa_decode_chain_b16_sizes(d->B, sz)) return 1;
+        dec_grow_floats(&d->pl_slab, &d->pl_slab_n, sz[0]);
+        dec_grow_counters(d, L, sz[1]);
+        return !d->pl_slab || !d->pl_ctr;
     }
-    if (d->pl_ctr_ints < sz[1]) {
-        hpa_free(d->pl_ctr);
-        d->pl_ctr_ints = sz[1];
-        d->pl_ctr = (int*)hpa_malloc((DEC_ERR_INTS + (size_t)L * sz[1]) * sizeof(int));
+    size_t sz[3];
+    if (hpa_decode_layer_sizes(d->B, c.channels, c.num_heads, p->splits, sz)) return 1;
+    if (!d->pl_rec || d->pl_rec_splits != p->splits) { /* records depend on the split count */
+        hpa_free(d->pl_rec);
+        d->pl_rec = (float*)hpa_malloc(sz[0] * sizeof(float));
+        d->pl_rec_splits = p->splits;
     }
+    dec_grow_floats(&d->pl_slab, &d->pl_slab_n, sz[1]);
+    dec_grow_counters(d, L, sz[2]);
+    if (!d->pl_rec || !d->pl_slab || !d->pl_ctr) return 1;
+    if (p->form != 5) return 0;
+    size_t ps[2];
+    if (hpa_decode_pipe_sizes(d->B, ps)) return 1;
+    dec_grow_floats(&d->pipe_slab, &d->pipe_slab_n, ps[0]);
+    dec_grow_counters(d, L, ps[1]);
     if (!d->pipe_slab || !d->pl_ctr) return 1;
     HpaPipeLayer* h = (HpaPipeLayer*)calloc((size_t)L, sizeof(HpaPipeLayer));
     if (!h) return 1;
-    const size_t e_layer = d->wpack_off[3] + hpa_frag_elems(C, 4 * C);
     for (int l = 0; l < L; l++) {
-        const size_t lc = (size_t)l * C;
-        h[l].w_ap = wpack_at(d, e_layer * l + d->wpack_off[1]);
-        h[l].b_ap = w->attprojb + lc;
-        h[l].w_fc = wpack_at(d, e_layer * l + d->wpack_off[2]);
-        h[l].fc_c1 = d->d_fold + 14 * lc + 6 * C;
-        h[l].fc_c2 = h[l].fc_c1 + 4 * C;
-        h[l].w_fp = wpack_at(d, e_layer * l + d->wpack_off[3]);
-        h[l].b_fp = w->fcprojb + lc;
+        const DecLayerOps o = dec_layer_ops(model, d, l);
+        h[l].w_ap = o.w_ap; h[l].b_ap = o.b_ap;
+        h[l].w_fc = o.w_fc; h[l].fc_c1 = o.fc_c1; h[l].fc_c2 = o.fc_c2;
+        h[l].w_fp = o.w_fp; h[l].b_fp = o.b_fp;
         if (l + 1 < L) {
-            h[l].w_qkv = wpack_at(d, e_layer * (l + 1) + d->wpack_off[0]);
-            h[l].qkv_c1 = d->d_fold + 14 * (lc + C);
-            h[l].qkv_c2 = h[l].qkv_c1 + 3 * C;
+            const DecLayerOps n = dec_layer_ops(model, d, l + 1);
+            h[l].w_qkv = n.w_qkv; h[l].qkv_c1 = n.qkv_c1; h[l].qkv_c2 = n.qkv_c2;
         }
     }
     if (!d->d_pipe_lay) d->d_pipe_lay = (HpaPipeLayer*)hpa_malloc((size_t)L * sizeof(HpaPipeLayer));
     const int rc = !d->d_pipe_lay || hpa_memcpy(d->d_pipe_lay, h, (size_t)L * sizeof(HpaPipeLayer));
     free(h);
-    if (rc) return 1;
-    d->pl_on = 5;
-    return 0;
+    return rc;
 }
 
+/* the plan for pl_want on this engine and device, and its workspace; on
+ * failure the engine is left on five launches */
 static int dec_layer_setup(GPT2* model, GPT2Decode* d) {
     const GPT2Config c = model->config;
-    d->pl_on = 0;
-    /* bf16 weights (BASELINE config 5): the bf16 chain (hpa_chain_b16.hip),
-     * B <= 256, in place of four GEMM launches per layer */
-    /* an fp8 pool's K/V are appended by chain form 6 (with the step's first
-     * launch) and by the GEMM launches' shared epilogue only: auto and form 5
-     * give chain form 6 where it applies, every other pick -- the bf16 chain
-     * included -- runs five launches per layer */
-    const int kv_fp8 = d->pool.dtype == HPA_FP8;
-    if (kv_fp8 && (d->w_bf16 || (d->pl_want != 1 && d->pl_want != 5) || c.num_heads != 12)) return 0;
-    if (d->pl_want && d->w_bf16) return dec_chain_b16_setup(model, d);
-    if (!d->pl_want || d->w_bf16 || !d->d_fold) return 0;
-    const int Bg = dec_pick_B(d); /* the batch the picks follow */
-    if (Bg > 64) return 0;
-    /* the loop's form (gpt2_decode_set_layer_kernel).  1 = auto, the form
-     * measured fastest (round 4, profiles/r4/forms.txt): chain form 6 at C =
-     * 768 (B = 64 / 8: 1.1106 / 0.4334 ms per step against the round-3 wide
-     * units' 1.1476 / 0.4510), chain form 8 at C >= 1024 (GPT-2 XL: 9.91 vs
-     * 10.29 ms for five launches), else the chain of 4-wave units.
-     * mode: 1 the full persistent layer, 2 the attention launch + the chain
-     * of 4-wave units, 3 the attention launch + the chain form pl_wform */
-    const int Rg = (Bg + 15) / 16;
-    int mode = 2;
-    d->pl_wform = 1;
-    switch (d->pl_want) {
-        case 2: mode = 1; break;
-        case 3: break;
-        case 4: /* round 3's wide units, widths by row blocks: chain_only 2..5 */
-            if (c.num_heads == 12) { mode = 3; d->pl_wform = 1 + Rg; }
-            break;
-        case 5: /* form 6 (12-wave multi-tile units) */
-            if (c.num_heads == 12) { mode = 3; d->pl_wform = 6; }
-            break;
-        case 6: mode = 3; d->pl_wform = 8; break; /* form 8: streamed-weight units (C = 768, 1600) */
-        case 7: /* the pipelined halves over chain form 6's units (form 6 where it does not apply) */
-            if (c.num_heads == 12) { mode = 3; d->pl_wform = 6; }
-            break;
-        default: /* auto */
-            if (c.num_heads == 12) { mode = 3; d->pl_wform = 6; }
-            else if (c.channels >= 1024) { mode = 3; d->pl_wform = 8; }
-            break;
-    }
-#ifndef HPA_AB
-    /* the full persistent layer (2) and the wide-unit chains (4) measured
-     * slower than the forms picked here: A/B builds only (hpa_build_flags) */
-    if (mode == 1 || (mode == 3 && d->pl_wform >= 2 && d->pl_wform <= 5)) return 0;
-#endif
-    int splits = hpa_decode_layer_pick_splits(Bg, c.num_heads, d->max_ctx);
+    const DecPlan five = {0, 0, 1, 0, 0};
+    int ncu = 0, full_splits = 0;
+    hpa_device_info(NULL, 0, &ncu, NULL);
 #ifdef HPA_AB
     const char* env = getenv("HPA_LAYER_SPLITS"); /* the full persistent layer's attention ranges */
-    if (env && atoi(env) > 0) splits = atoi(env);
+    if (env) full_splits = atoi(env);
 #endif
-    if (mode >= 2) splits = 1; /* no attention phase: no split records */
-    if (d->pl_wform >= 6 ? !hpa_decode_chain_eligible(d->B, c.channels, c.num_heads, d->pl_wform)
-                         : !hpa_decode_layer_eligible(d->B, c.channels, c.num_heads, splits))
-        return 0;
-    size_t sz[3];
-    if (hpa_decode_layer_sizes(d->B, c.channels, c.num_heads, splits, sz)) return 1;
-    if (!d->pl_rec || d->pl_splits != splits) { /* records depend on the split count */
-        hpa_free(d->pl_rec);
-        d->pl_rec = (float*)hpa_malloc(sz[0] * sizeof(float));
-    }
-    if (!d->pl_slab) {
-        d->pl_slab_n = sz[1];
-        d->pl_slab = (float*)hpa_malloc(sz[1] * sizeof(float));
-    }
-    if (!d->pl_ctr) {
-        d->pl_ctr_ints = sz[2];
-        d->pl_ctr = (int*)hpa_malloc((DEC_ERR_INTS + (size_t)c.num_layers * sz[2]) * sizeof(int));
-    }
-    if (!d->pl_rec || !d->pl_slab || !d->pl_ctr) return 1;
-    d->pl_splits = splits;
-    d->pl_on = mode;
-    if (d->pl_want == 7 && mode == 3 && d->pl_wform == 6) return dec_pipe_setup(model, d);
+    const DecPlan p = dec_plan(d->pl_want, d->B, dec_pick_B(d), c.channels, c.num_heads, d->max_ctx, d->pool.dtype,
+                               d->w_bf16, d->d_fold != NULL, ncu, hpa_build_flags() & 1, full_splits);
+    d->plan = five;
+    if (dec_layer_workspace(model, d, &p)) return 1;
+    d->plan = p;
     return 0;
 }
 
-/* layer l's bf16 chain: attproj(l) .. fcproj(l), qkv(l+1) (pl_on 4) */
+/* layer l's bf16 chain: attproj(l) .. fcproj(l), qkv(l+1) (plan.form 4) */
 static int dec_layer_b16(GPT2* model, int l) {
     GPT2Decode* d = model->decode;
-    const GPT2Config c = model->config;
-    const int C = c.channels, L = c.num_layers;
-    const ParameterTensors* w = &model->params;
-    const size_t lc = (size_t)l * C;
-    const size_t e_layer = d->wpack_off[3] + hpa_frag_elems(C, 4 * C);
+    const DecLayerOps o = dec_layer_ops(model, d, l);
     HpaChainB16Args a;
     memset(&a, 0, sizeof(a));
     a.B = d->B;
     a.layer = l;
-    a.last = l + 1 == L;
+    a.last = l + 1 == model->config.num_layers;
     a.pool = &d->pool;
     a.block_table = d->d_bt;
     a.bt_stride = d->bt_stride;
@@ -1106,19 +1163,20 @@ static int dec_layer_b16(GPT2* model, int l) {
     a.res = d->res;
     a.res2 = d->res2;
     a.fch = d->fch;
-    a.w_ap = wpack_at(d, e_layer * l + d->wpack_off[1]);
-    a.b_ap = w->attprojb + lc;
-    a.ln2_w = w->ln2w + lc;
-    a.ln2_b = w->ln2b + lc;
-    a.w_fc = wpack_at(d, e_layer * l + d->wpack_off[2]);
-    a.b_fc = w->fcb + 4 * lc;
-    a.w_fp = wpack_at(d, e_layer * l + d->wpack_off[3]);
-    a.b_fp = w->fcprojb + lc;
+    a.w_ap = o.w_ap;
+    a.b_ap = o.b_ap;
+    a.ln2_w = o.ln2_w;
+    a.ln2_b = o.ln2_b;
+    a.w_fc = o.w_fc;
+    a.b_fc = o.b_fc;
+    a.w_fp = o.w_fp;
+    a.b_fp = o.b_fp;
     if (!a.last) {
-        a.w_qkv = wpack_at(d, e_layer * (l + 1) + d->wpack_off[0]);
-        a.b_qkv = w->qkvb + 3 * (lc + C);
-        a.ln1_w = w->ln1w + lc + C;
-        a.ln1_b = w->ln1b + lc + C;
+        const DecLayerOps n = dec_layer_ops(model, d, l + 1);
+        a.w_qkv = n.w_qkv;
+        a.b_qkv = n.b_qkv;
+        a.ln1_w = n.ln1_w;
+        a.ln1_b = n.ln1_b;
         a.q_out = d->d_q; /* every read of q(l) was the attention launch's, before this one */
     }
     a.stats_out = a.last ? d->st1 : NULL; /* LNf statistics for the logits */
@@ -1134,19 +1192,16 @@ static int dec_layer_b16(GPT2* model, int l) {
 static int dec_layer(GPT2* model, int l) {
     GPT2Decode* d = model->decode;
     const GPT2Config c = model->config;
-    const int C = c.channels, L = c.num_layers;
-    const ParameterTensors* w = &model->params;
-    const size_t lc = (size_t)l * C;
-    const size_t e_layer = d->wpack_off[3] + hpa_frag_elems(C, 4 * C);
-    if (d->pl_on == 4) return dec_layer_b16(model, l);
+    if (d->plan.form == 4) return dec_layer_b16(model, l);
+    const DecLayerOps o = dec_layer_ops(model, d, l);
     HpaLayerArgs a;
     memset(&a, 0, sizeof(a));
     a.B = d->B;
-    a.C = C;
+    a.C = c.channels;
     a.num_heads = c.num_heads;
-    a.splits = d->pl_splits;
-    a.last = l + 1 == L;
-    a.chain_only = d->pl_on == 3 || d->pl_on == 5 ? d->pl_wform : d->pl_on == 2;
+    a.splits = d->plan.splits;
+    a.last = l + 1 == c.num_layers;
+    a.chain_only = d->plan.chain;
     a.pool = &d->pool;
     a.layer = l;
     a.block_table = d->d_bt;
@@ -1157,17 +1212,18 @@ static int dec_layer(GPT2* model, int l) {
     a.res = d->res;
     a.res2 = d->res2;
     a.fch = d->fch;
-    a.w_ap = wpack_at(d, e_layer * l + d->wpack_off[1]);
-    a.b_ap = w->attprojb + lc;
-    a.w_fc = wpack_at(d, e_layer * l + d->wpack_off[2]);
-    a.fc_c1 = d->d_fold + 14 * lc + 6 * C;
-    a.fc_c2 = a.fc_c1 + 4 * C;
-    a.w_fp = wpack_at(d, e_layer * l + d->wpack_off[3]);
-    a.b_fp = w->fcprojb + lc;
+    a.w_ap = o.w_ap;
+    a.b_ap = o.b_ap;
+    a.w_fc = o.w_fc;
+    a.fc_c1 = o.fc_c1;
+    a.fc_c2 = o.fc_c2;
+    a.w_fp = o.w_fp;
+    a.b_fp = o.b_fp;
     if (!a.last) {
-        a.w_qkv = wpack_at(d, e_layer * (l + 1) + d->wpack_off[0]);
-        a.qkv_c1 = d->d_fold + 14 * (lc + C);
-        a.qkv_c2 = a.qkv_c1 + 3 * C;
+        const DecLayerOps n = dec_layer_ops(model, d, l + 1);
+        a.w_qkv = n.w_qkv;
+        a.qkv_c1 = n.qkv_c1;
+        a.qkv_c2 = n.qkv_c2;
         a.q_out = d->d_q; /* every read of q(l) is done before the first qkv(l+1) store */
     }
     a.stats_out = a.last ? d->st1 : NULL; /* LNf statistics for the logits */
@@ -1454,19 +1510,13 @@ static int dec_ensure_pages(GPT2Decode* d) {
 
 enum { G_QKV = 0, G_ATTPROJ = 1, G_FC = 2, G_FCPROJ = 3, G_LOGITS = 4 };
 
-/* packed weights at element offset off (fp32 or bf16 pack) */
-static const float* wpack_at(const GPT2Decode* d, size_t off) {
-    return d->w_bf16 ? (const float*)((const unsigned short*)d->d_wpack + off) : d->d_wpack + off;
-}
-
 /* descriptor of fused GEMM `which` of layer l over the decode rows */
 static void dec_gemm_desc(GPT2* model, int l, int which, HpaFusedGemm* g) {
     GPT2Decode* d = model->decode;
     const GPT2Config c = model->config;
     const int C = c.channels, V = c.vocab_size, ct = C / 16;
     const ParameterTensors* w = &model->params;
-    const size_t lc = (size_t)l * C;
-    const size_t e_layer = d->wpack_off[3] + hpa_frag_elems(C, 4 * C);
+    const DecLayerOps o = dec_layer_ops(model, d, l);
     memset(g, 0, sizeof(*g));
     g->M = d->B;
     g->w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
@@ -1483,23 +1533,23 @@ static void dec_gemm_desc(GPT2* model, int l, int which, HpaFusedGemm* g) {
     switch (which) {
         case G_QKV: /* LN1 (stats: embedding's 1 tile at layer 0, fcproj's C/16 after) */
             g->x = d->res; g->K = C; g->ln_stats = d->st1; g->ln_ntiles = l == 0 ? 1 : ct;
-            g->ln_w = w->ln1w + lc; g->ln_b = w->ln1b + lc; g->w = wpack_at(d, e_layer * l + d->wpack_off[0]);
-            g->N = 3 * C; g->bias = w->qkvb + 3 * lc; g->out = d->d_q;
-            if (d->d_fold) { g->ln_fold_c1 = d->d_fold + 14 * lc; g->bias = g->ln_fold_c1 + 3 * C; }
+            g->ln_w = o.ln1_w; g->ln_b = o.ln1_b; g->w = o.w_qkv;
+            g->N = 3 * C; g->bias = o.b_qkv; g->out = d->d_q;
+            if (d->d_fold) { g->ln_fold_c1 = o.qkv_c1; g->bias = o.qkv_c2; }
             break;
         case G_ATTPROJ: /* res2 = res + att . Wap^T + b (LN2 statistics only when fc needs them) */
-            g->x = d->att; g->K = C; g->w = wpack_at(d, e_layer * l + d->wpack_off[1]); g->N = C;
-            g->bias = w->attprojb + lc; g->out = d->res2; g->res_in = d->res; g->stats_out = d->d_fold ? NULL : d->st2;
+            g->x = d->att; g->K = C; g->w = o.w_ap; g->N = C;
+            g->bias = o.b_ap; g->out = d->res2; g->res_in = d->res; g->stats_out = d->d_fold ? NULL : d->st2;
             break;
         case G_FC: /* gelu(LN2(res2) . Wfc^T + b) */
-            g->x = d->res2; g->K = C; g->ln_stats = d->st2; g->ln_ntiles = ct; g->ln_w = w->ln2w + lc;
-            g->ln_b = w->ln2b + lc; g->w = wpack_at(d, e_layer * l + d->wpack_off[2]); g->N = 4 * C;
-            g->bias = w->fcb + 4 * lc; g->out = d->fch;
-            if (d->d_fold) { g->ln_fold_c1 = d->d_fold + 14 * lc + 6 * C; g->bias = g->ln_fold_c1 + 4 * C; }
+            g->x = d->res2; g->K = C; g->ln_stats = d->st2; g->ln_ntiles = ct; g->ln_w = o.ln2_w;
+            g->ln_b = o.ln2_b; g->w = o.w_fc; g->N = 4 * C;
+            g->bias = o.b_fc; g->out = d->fch;
+            if (d->d_fold) { g->ln_fold_c1 = o.fc_c1; g->bias = o.fc_c2; }
             break;
         case G_FCPROJ: /* res = res2 + fch . Wfp^T + b, next-LN statistics */
-            g->x = d->fch; g->K = 4 * C; g->w = wpack_at(d, e_layer * l + d->wpack_off[3]); g->N = C;
-            g->bias = w->fcprojb + lc; g->out = d->res; g->res_in = d->res2;
+            g->x = d->fch; g->K = 4 * C; g->w = o.w_fp; g->N = C;
+            g->bias = o.b_fp; g->out = d->res; g->res_in = d->res2;
             g->stats_out = d->d_fold && l + 1 < c.num_layers ? NULL : d->st1; /* LNf of logits: last layer */
             break;
         default: /* logits = LNf(res) . wte^T, argmax partials */
@@ -1591,9 +1641,6 @@ static int dec_attention(GPT2* model, int l) {
     return rc;
 }
 
-#ifndef DEC_FIRST_LAUNCH
-#define DEC_FIRST_LAUNCH 1 /* A/B builds: 0 = the embed kernel + the one-shot qkv(0) GEMM */
-#endif
 /* the step's first launch under chain form 6 (hpa_decode_first): the
  * embedding into res, layer 0's q and K/V (LN1 folded), and zb bytes of the
  * counter block (error word + hand-off counters) zeroed */
@@ -1601,20 +1648,20 @@ static int dec_first(GPT2* model, size_t zb) {
     GPT2Decode* d = model->decode;
     const GPT2Config c = model->config;
     const ParameterTensors* w = &model->params;
-    const int C = c.channels;
+    const DecLayerOps o = dec_layer_ops(model, d, 0);
     HpaLayerArgs a;
     memset(&a, 0, sizeof(a));
     a.B = d->B;
-    a.C = C;
+    a.C = c.channels;
     a.num_heads = c.num_heads;
     a.pool = &d->pool;
     a.block_table = d->d_bt;
     a.bt_stride = d->bt_stride;
     a.pos = d->d_pos;
     a.res = d->res;
-    a.w_qkv = wpack_at(d, d->wpack_off[0]); /* layer 0 */
-    a.qkv_c1 = d->d_fold;
-    a.qkv_c2 = d->d_fold + 3 * C;
+    a.w_qkv = o.w_qkv;
+    a.qkv_c1 = o.qkv_c1;
+    a.qkv_c2 = o.qkv_c2;
     a.q_out = d->d_q;
     return hpa_decode_first(&a, d->d_tokens, w->wte, w->wpe, d->pl_ctr, zb);
 }
@@ -1623,6 +1670,7 @@ static int dec_first(GPT2* model, size_t zb) {
 static int dec_first_b16(GPT2* model, size_t zb) {
     GPT2Decode* d = model->decode;
     const ParameterTensors* w = &model->params;
+    const DecLayerOps o = dec_layer_ops(model, d, 0);
     HpaChainB16Args a;
     memset(&a, 0, sizeof(a));
     a.B = d->B;
@@ -1631,15 +1679,15 @@ static int dec_first_b16(GPT2* model, size_t zb) {
     a.bt_stride = d->bt_stride;
     a.pos = d->d_pos;
     a.res = d->res;
-    a.w_qkv = wpack_at(d, d->wpack_off[0]); /* layer 0 */
-    a.b_qkv = w->qkvb;
-    a.ln1_w = w->ln1w;
-    a.ln1_b = w->ln1b;
+    a.w_qkv = o.w_qkv;
+    a.b_qkv = o.b_qkv;
+    a.ln1_w = o.ln1_w;
+    a.ln1_b = o.ln1_b;
     a.q_out = d->d_q;
     return hpa_decode_chain_b16_first(&a, d->d_tokens, w->wte, w->wpe, d->pl_ctr, zb);
 }
 
-/* every layer of the step as the pipelined halves' one launch (pl_on 5) */
+/* every layer of the step as the pipelined halves' one launch (plan.form 5) */
 static int dec_pipe(GPT2* model) {
     GPT2Decode* d = model->decode;
     HpaPipeArgs a;
@@ -1673,48 +1721,39 @@ static int dec_launch(GPT2* model) {
     const ParameterTensors* w = &model->params;
     const int L = model->config.num_layers;
     const int C = model->config.channels;
-    const int pl = d->pl_on && !d->profiling;
-    /* persistent layers: the embed kernel also zeroes their hand-off counters */
+    const DecPlan five = {0, 0, 1, 0, 0};
+    const DecPlan p = d->profiling ? five : d->plan; /* a profiled step times every attention launch */
+    const int pl = p.form != 0;
+    /* persistent layers: the first launch also zeroes their hand-off counters */
     const size_t zb = (DEC_ERR_INTS + (size_t)L * d->pl_ctr_ints) * sizeof(int);
-    /* chain form 6 (and form 8 at C = 768, which sums as form 6): embed +
-     * qkv(0) + the counter zeroing in one launch */
-    const int first = pl && DEC_FIRST_LAUNCH && (((d->pl_on == 3 || d->pl_on == 5) &&
-                      (d->pl_wform == 6 || (d->pl_wform == 8 && model->config.num_heads == 12))) || d->pl_on == 4);
-    int rc = first ? (d->pl_on == 4 ? dec_first_b16(model, zb) : dec_first(model, zb))
-           : !pl   ? hpa_embed_frag(d->d_tokens, d->d_pos, w->wte, w->wpe, d->res, d->st1, d->B, C)
-                   : hpa_embed_frag_zero(d->d_tokens, d->d_pos, w->wte, w->wpe, d->res, d->st1, d->B, C, d->pl_ctr, zb);
+    int rc = p.first == 2 ? dec_first_b16(model, zb)
+           : p.first == 1 ? dec_first(model, zb)
+           : !pl ? hpa_embed_frag(d->d_tokens, d->d_pos, w->wte, w->wpe, d->res, d->st1, d->B, C)
+                 : hpa_embed_frag_zero(d->d_tokens, d->d_pos, w->wte, w->wpe, d->res, d->st1, d->B, C, d->pl_ctr, zb);
 #define DEC_TRACE(i) \
     if (d->trace_x) rc |= hpa_unpack_frag(d->res, d->B, C, d->trace_x + (size_t)(i) * d->B * C, C)
     DEC_TRACE(0);
-    if (pl && d->pl_on == 5 && first && !d->trace_x) { /* the pipelined halves: every layer in one launch */
+    if (p.form == 5 && p.first && !d->trace_x) { /* the pipelined halves: every layer in one launch */
         rc |= dec_pipe(model);
-        rc |= dec_gemm(model, 0, G_LOGITS);
-        rc |= dec_pick(model, NULL);
-        return rc;
-    }
-    if (pl) { /* qkv(0), then one persistent launch per layer */
-        if (!first) rc |= dec_gemm(model, 0, G_QKV);
+    } else {
+        if (pl && !p.first) rc |= dec_gemm(model, 0, G_QKV); /* persistent layers end with qkv(l+1) */
         for (int l = 0; l < L && !rc; l++) {
-            if (d->pl_on >= 2) rc |= dec_attention(model, l); /* chain form: the attention's own launch */
-            rc |= dec_layer(model, l);
+            if (!pl) rc |= dec_gemm(model, l, G_QKV);
+            if (!pl || p.attn_launch) rc |= dec_attention(model, l);
+            if (pl) {
+                rc |= dec_layer(model, l);
+            } else {
+                rc |= dec_gemm(model, l, G_ATTPROJ);
+                rc |= dec_gemm(model, l, G_FC);
+                rc |= dec_gemm(model, l, G_FCPROJ);
+            }
             DEC_TRACE(l + 1);
         }
-        rc |= dec_gemm(model, 0, G_LOGITS);
-        rc |= dec_pick(model, NULL); /* a separate argmax launch: the in-launch pick (HpaFusedGemm.pick_next)
-                                      * measured no faster, profiles/r4/experiments/in_launch_pick.txt */
-        return rc;
-    }
-    for (int l = 0; l < L && !rc; l++) {
-        rc |= dec_gemm(model, l, G_QKV);
-        rc |= dec_attention(model, l);
-        rc |= dec_gemm(model, l, G_ATTPROJ);
-        rc |= dec_gemm(model, l, G_FC);
-        rc |= dec_gemm(model, l, G_FCPROJ);
-        DEC_TRACE(l + 1);
     }
 #undef DEC_TRACE
     rc |= dec_gemm(model, 0, G_LOGITS);
-    rc |= dec_pick(model, NULL);
+    rc |= dec_pick(model, NULL); /* a separate argmax launch: the in-launch pick (HpaFusedGemm.pick_next)
+                                  * measured no faster, profiles/r4/experiments/in_launch_pick.txt */
     return rc;
 }
 
@@ -1847,9 +1886,7 @@ static int prefill_gemm(GPT2* model, int l, int which, int R) {
     GPT2Decode* d = model->decode;
     const GPT2Config c = model->config;
     const int C = c.channels, ct = C / 16;
-    const ParameterTensors* w = &model->params;
-    const size_t lc = (size_t)l * C;
-    const size_t e_layer = d->wpack_off[3] + hpa_frag_elems(C, 4 * C);
+    const DecLayerOps o = dec_layer_ops(model, d, l);
     HpaFusedGemm g;
     memset(&g, 0, sizeof(g));
     g.M = R;
@@ -1868,24 +1905,24 @@ static int prefill_gemm(GPT2* model, int l, int which, int R) {
     switch (which) {
         case G_QKV:
             g.epilogue = HPA_FEPI_QKV; g.x = d->pf_res; g.K = C; g.ln_stats = d->pf_st1;
-            g.ln_ntiles = l == 0 ? 1 : ct; g.ln_w = w->ln1w + lc; g.ln_b = w->ln1b + lc;
-            g.w = wpack_at(d, e_layer * l + d->wpack_off[0]); g.N = 3 * C; g.bias = w->qkvb + 3 * lc; g.out = d->pf_q;
-            if (d->d_fold) { g.ln_fold_c1 = d->d_fold + 14 * lc; g.bias = g.ln_fold_c1 + 3 * C; }
+            g.ln_ntiles = l == 0 ? 1 : ct; g.ln_w = o.ln1_w; g.ln_b = o.ln1_b;
+            g.w = o.w_qkv; g.N = 3 * C; g.bias = o.b_qkv; g.out = d->pf_q;
+            if (d->d_fold) { g.ln_fold_c1 = o.qkv_c1; g.bias = o.qkv_c2; }
             break;
         case G_ATTPROJ:
-            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_att; g.K = C; g.w = wpack_at(d, e_layer * l + d->wpack_off[1]);
-            g.N = C; g.bias = w->attprojb + lc; g.out = d->pf_res2; g.res_in = d->pf_res;
+            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_att; g.K = C; g.w = o.w_ap;
+            g.N = C; g.bias = o.b_ap; g.out = d->pf_res2; g.res_in = d->pf_res;
             g.stats_out = d->d_fold ? NULL : d->pf_st2;
             break;
         case G_FC:
             g.epilogue = HPA_FEPI_GELU; g.x = d->pf_res2; g.K = C; g.ln_stats = d->pf_st2; g.ln_ntiles = ct;
-            g.ln_w = w->ln2w + lc; g.ln_b = w->ln2b + lc; g.w = wpack_at(d, e_layer * l + d->wpack_off[2]);
-            g.N = 4 * C; g.bias = w->fcb + 4 * lc; g.out = d->pf_fch;
-            if (d->d_fold) { g.ln_fold_c1 = d->d_fold + 14 * lc + 6 * C; g.bias = g.ln_fold_c1 + 4 * C; }
+            g.ln_w = o.ln2_w; g.ln_b = o.ln2_b; g.w = o.w_fc;
+            g.N = 4 * C; g.bias = o.b_fc; g.out = d->pf_fch;
+            if (d->d_fold) { g.ln_fold_c1 = o.fc_c1; g.bias = o.fc_c2; }
             break;
         default: /* G_FCPROJ */
-            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_fch; g.K = 4 * C; g.w = wpack_at(d, e_layer * l + d->wpack_off[3]);
-            g.N = C; g.bias = w->fcprojb + lc; g.out = d->pf_res; g.res_in = d->pf_res2;
+            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_fch; g.K = 4 * C; g.w = o.w_fp;
+            g.N = C; g.bias = o.b_fp; g.out = d->pf_res; g.res_in = d->pf_res2;
             g.stats_out = d->d_fold && l + 1 < c.num_layers ? NULL : d->pf_st1;
             break;
     }
@@ -2096,7 +2133,7 @@ int gpt2_decode_set_layer_kernel(GPT2* model, int enable) {
     return 0;
 }
 
-int gpt2_decode_layer_kernel(GPT2* model) { return model->decode ? model->decode->pl_on : 0; }
+int gpt2_decode_layer_kernel(GPT2* model) { return model->decode ? model->decode->plan.form : 0; }
 
 int gpt2_decode_set_pipe_split(GPT2* model, int g_cus) {
     GPT2Decode* d = model->decode;

@@ -264,6 +264,7 @@ def lib():
     _sig(L, "hpa_pool_fill_random_ex", i, [P, v, i, i, i, ctypes.c_uint64, i])
     _sig(L, "hpa_logits_kernel", i, [i, i, i])
     _sig(L, "gpt2_decode_layer_kernel", i, [v])
+    _sig(L, "gpt2_decode_layer_plan", i, [i, i, i, i, i, i, i, i, i, _I])
     _sig(L, "gpt2_decode_set_pipe_split", i, [v, i])
     _sig(L, "hpa_decode_pipe_eligible", i, [i, i, i, i])
     _sig(L, "gpt2_decode_status", i, [v])
@@ -342,6 +343,21 @@ def device_info():
     mem = ctypes.c_size_t()
     check(L.hpa_device_info(name, 256, ctypes.byref(cus), ctypes.byref(mem)), "device_info")
     return name.value.decode(), cus.value, mem.value
+
+
+PLAN_FIELDS = ("form", "chain", "splits", "first", "attn_launch")
+
+
+def layer_plan(request, B, C, num_heads, max_ctx, kv_dtype=0, w_bf16=False, num_cus=256, pick_B=None):
+    """what the engine makes of set_layer_kernel(request) for these shapes on a
+    device of num_cus CUs (gpt2_decode_layer_plan: the one place that decides
+    it; pure, needs no GPU): a dict of PLAN_FIELDS.  pick_B: the global batch
+    of a shard (default: B)."""
+    out = (ctypes.c_int * 5)()
+    check(lib().gpt2_decode_layer_plan(int(request), int(B), int(B if pick_B is None else pick_B), int(C),
+                                       int(num_heads), int(max_ctx), int(kv_dtype), int(bool(w_bf16)),
+                                       int(num_cus), out), "layer_plan")
+    return dict(zip(PLAN_FIELDS, out))
 
 
 # ---------------------------------------------------------------- device buffers
@@ -714,10 +730,14 @@ class Model:
         check(lib().gpt2_decode_set_global_batch(self.h, int(total)), "set_global_batch")
 
     def set_layer_kernel(self, on):
-        """layer loop: 0 five launches, 2 full persistent layer, 3 attention
-        launch + persistent chain, 4 the chain with wide units (B <= 16,
-        C = 768), 1 the form measured fastest for the batch (bf16 weights:
-        any nonzero value is the bf16 chain, B <= 256);
+        """the layer loop's form, a request 0..7: 0 five launches, 1 the form
+        measured fastest for the shape, 2 full persistent layer, 3 attention
+        launch + chain of 4-wave units, 4 the chain with wide units, 5 chain
+        form 6 (12-wave multi-tile units, C = 768), 6 chain form 8 (streamed
+        weights, C = 768 .. 1600), 7 the pipelined halves (else 5); 2, 4 and
+        7 in A/B builds only (bf16 weights: any nonzero value is the bf16
+        chain, B <= 256).  What a request becomes for a shape is decided by
+        layer_plan() (gpt2_decode_layer_plan, include/paged_infer.h) alone;
         returns whether a persistent form is now in use"""
         check(lib().gpt2_decode_set_layer_kernel(self.h, int(on)), "set_layer_kernel")
         return bool(lib().gpt2_decode_layer_kernel(self.h))
@@ -730,9 +750,10 @@ class Model:
         check(lib().gpt2_decode_set_pipe_split(self.h, int(g_cus)), "set_pipe_split")
 
     def layer_form(self):
-        """0 five launches per layer, 1 full persistent layer, 2 attention launch + persistent chain,
-        3 the chain with wide units, 4 the bf16-weight chain (hpa_chain_b16.hip), 5 the pipelined
-        halves (hpa_pipe.hip)"""
+        """the plan's form (layer_plan): 0 five launches per layer, 1 full persistent layer,
+        2 attention launch + chain of 4-wave units, 3 attention launch + the chain in wide /
+        multi-tile / streamed-weight units, 4 the bf16-weight chain (hpa_chain_b16.hip),
+        5 the pipelined halves (hpa_pipe.hip)"""
         return int(lib().gpt2_decode_layer_kernel(self.h))
 
     def status(self):
