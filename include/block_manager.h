@@ -85,6 +85,8 @@ typedef struct {
     BMPageBackend backend;
     int dirty_lo, dirty_hi;      /* prompt rows changed since bm_clear_dirty */
     int last_evicted_prompt;     /* prompt paged out by the last request_block, or -1 */
+    int* page_refs;              /* [max_blocks] prompts holding the page (0 = free; > 1 after bm_fork_prompt) */
+    int shared_pages;            /* pages with page_refs > 1 */
 } BlockManager;
 
 /* ---- reference API (signatures as block_manager.c) ---- */
@@ -110,6 +112,32 @@ int  bm_free_pages(const BlockManager* manager);
 void bm_clear_dirty(BlockManager* manager);
 /* the backend compiled in as default: 0 host malloc, 1 HIP managed memory */
 int  bm_default_backend_kind(void);
+
+/* ---- shared pages (prefix sharing between prompts) ----
+ * A page may be held by several prompts: page_refs counts the holders.  Shared
+ * pages are always a common prefix, so every holder has the page at the same
+ * index of its list.  Releasing a prompt (free_blocks_for_prompt, eviction)
+ * drops one reference per page; the payload is released and the page becomes
+ * free when the last holder lets go.  blocks[page].prompt_id names one holder:
+ * when that holder lets go first it moves to the lowest-numbered remaining
+ * one.  The LRU policy considers only pages with a single holder (evicting
+ * that holder frees at least that page), so request_block still evicts at most
+ * one prompt; with every page shared it returns NULL and evicts nobody.  A
+ * manager that never forks behaves exactly as before (all counts 0 or 1). */
+/* dst (which must own no pages) gets src's first n_pages pages, each with one
+ * more holder; prompt_id / lru_counter / filled of the pages do not change.
+ * Nonzero with a message on a bad argument, and then nothing has changed. */
+int  bm_fork_prompt(BlockManager* manager, int src, int dst, int n_pages);
+/* page `index` of prompt's list, when it has other holders, is replaced by a
+ * fresh page (first fit, LRU eviction as request_block, last_evicted_prompt
+ * set likewise) and its reference dropped; the caller copies the payload.
+ * Returns the page now at that index (the old one when it was private), or -1
+ * with nothing swapped: bad arguments, no page available, or the eviction took
+ * `prompt` itself (last_evicted_prompt == prompt).  *old_page (nullable)
+ * receives the page that was there. */
+int  bm_make_private(BlockManager* manager, int prompt, int index, int* old_page);
+int  bm_page_refs(const BlockManager* manager, int page); /* 0 when free or out of range */
+int  bm_shared_pages(const BlockManager* manager);
 
 #ifdef __cplusplus
 }

@@ -149,6 +149,17 @@ void* hpa_pool_tile(const HpaKVPool* pool, int layer, int page, int kv, int head
 /* host-side layout helpers (tests / compat copies) */
 size_t hpa_pool_k_index(const HpaKVPool* pool, int layer, int page, int head, int slot, int d);
 size_t hpa_pool_v_index(const HpaKVPool* pool, int layer, int page, int head, int slot, int d);
+/* whole pages copied inside the pool, every layer: for i < n the page_elems *
+ * elem_bytes contiguous bytes of page src_pages[i] (K and V, all heads) go to
+ * page dst_pages[i] in each layer's slab.  Bytes only, whatever the dtype (an
+ * fp8 pool's scales are per (layer, head), not per page).  src_pages and
+ * dst_pages are HOST arrays of pool slots, 1 <= n <= HPA_COPY_MAX_PAGES; they
+ * travel by value in the kernel arguments: ONE asynchronous launch on the
+ * current stream, no staging buffer, no sync.  Every slot must be in range,
+ * every destination distinct, and no page both a source and a destination;
+ * otherwise nonzero and nothing is launched. */
+#define HPA_COPY_MAX_PAGES 64
+int  hpa_pool_copy_pages(const HpaKVPool* pool, const int* src_pages, const int* dst_pages, int n);
 
 /* ---------------- decode-step kernels (fp32) ----------------
  * B = sequences in the batch, C = channels, NH heads of head_size 64.

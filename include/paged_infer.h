@@ -189,6 +189,31 @@ int  gpt2_decode_prefill_ragged(GPT2* model, const int* tokens, const int* lens,
 /* retire sequence seq: its pages go back to the pool (block_manager.c:78-90),
  * its position restarts at 0, so the slot can admit a new prompt */
 int  gpt2_decode_release(GPT2* model, int seq);
+/* prefix sharing: sequence dst continues from the first n_tokens cached tokens
+ * of sequence src (n_tokens in [1, pos[src]], or -1 for pos[src]) without
+ * computing or storing them again -- one system prompt for many requests, or N
+ * samples of one prompt.  dst must be fresh or released (position 0, no
+ * pages).  Any violation, src == dst and a sequence out of range included,
+ * returns nonzero with a message and changes nothing.
+ * dst shares src's n_tokens / P full pages (bm_fork_prompt: one more holder
+ * each, nothing copied); when n_tokens % P != 0 it takes ONE fresh page and the
+ * partly filled page is copied into it in every layer by one launch
+ * (hpa_pool_copy_pages; the slots beyond n_tokens carry stale bytes no kernel
+ * reads, as in any reused page).  pos[dst] = n_tokens.  When n_tokens ==
+ * pos[src], dst also inherits src's pending next id, so gpt2_decode_step(model,
+ * NULL, ...) continues both; otherwise dst has no valid next id until it is fed
+ * tokens.  dst's sampler state is untouched (seeded seed + dst), so forks of
+ * one prompt draw different tokens.  Only full pages are shared and the tail
+ * is copied here, so appends after a fork land in private pages; a sequence
+ * rewound into a shared page (gpt2_decode_set_positions) gets a private copy
+ * of it before its next append.  The LRU policy never evicts the holder of a
+ * shared page for that page (block_manager.h); if the fresh page's allocation
+ * pages out src itself the call fails.  Releasing or evicting one holder
+ * leaves the pages to the others.  gpt2_decode_fill_random* refuses while
+ * pages are shared.  Waits for queued work like gpt2_decode_release. */
+int  gpt2_decode_fork(GPT2* model, int src, int dst, int n_tokens);
+/* free pages of the engine's manager (-1 without an engine) */
+int  gpt2_decode_free_pages(GPT2* model);
 /* the same, but enqueue only (no host sync; next ids stay on device) */
 int  gpt2_decode_step_async(GPT2* model, const int* tokens);
 /* one eager step that also copies the residual stream entering every layer

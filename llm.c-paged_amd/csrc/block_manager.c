@@ -112,7 +112,8 @@ BlockManager* create_block_manager_ex(int channels, int max_prompts, int max_blo
     size_t o_count = o_rows + bm_align16(sizeof(int*) * (size_t)max_prompts);
     size_t o_table = o_count + bm_align16(sizeof(int) * (size_t)max_prompts);
     size_t o_bits = o_table + bm_align16(sizeof(int) * (size_t)max_prompts * max_blocks_per_prompt);
-    size_t total = o_bits + sizeof(unsigned long long) * (size_t)words;
+    size_t o_refs = o_bits + bm_align16(sizeof(unsigned long long) * (size_t)words);
+    size_t total = o_refs + sizeof(int) * (size_t)max_blocks;
     char* mem = (char*)calloc(1, total); /* block_manager.c:39 (one block: free(manager) works) */
     if (!mem) {
         fprintf(stderr, "create_block_manager: out of memory.\n");
@@ -125,6 +126,8 @@ BlockManager* create_block_manager_ex(int channels, int max_prompts, int max_blo
     m->prompt_block_count = (int*)(mem + o_count);
     m->block_table = (int*)(mem + o_table);
     m->free_bits = (unsigned long long*)(mem + o_bits);
+    m->page_refs = (int*)(mem + o_refs); /* calloc: every page starts free, 0 holders */
+    m->shared_pages = 0;
     m->max_prompts = max_prompts;
     m->max_blocks = max_blocks;
     m->block_size = block_size;
@@ -208,32 +211,54 @@ void bm_clear_dirty(BlockManager* m) {
     m->dirty_hi = -1;
 }
 
+/* prompt lets go of page bi, which it held at index i of its list.  The last
+ * holder releases the payload and frees the page (block_manager.c:80-86).
+ * While others still hold it, a page named after `prompt` is renamed to the
+ * lowest-numbered remaining holder: shared pages are prefixes, so a holder has
+ * the page at the same index i. */
+static void bm_drop_ref(BlockManager* m, int prompt, int i, int bi) {
+    KVBlock* b = &m->blocks[bi];
+    if (m->page_refs[bi] > 1) {
+        if (--m->page_refs[bi] == 1) m->shared_pages--;
+        if (b->prompt_id == prompt)
+            for (int q = 0; q < m->max_prompts; q++)
+                if (q != prompt && m->prompt_block_count[q] > i && m->prompt_block_list[q][i] == bi) {
+                    b->prompt_id = q;
+                    break;
+                }
+        return;
+    }
+    if (b->keys) m->backend.release(m->backend.ctx, bi, 0, b->keys);
+    if (b->values) m->backend.release(m->backend.ctx, bi, 1, b->values);
+    b->keys = NULL;
+    b->values = NULL;
+    b->filled = 0;
+    b->prompt_id = -1;
+    m->page_refs[bi] = 0;
+    bm_mark_free(m, bi);
+}
+
 /* block_manager.c:78-90 */
 void free_blocks_for_prompt(BlockManager* manager, int prompt_id) {
     if (prompt_id < 0 || prompt_id >= manager->max_prompts) return;
     if (g_bm_verbose) printf("Freeing all blocks for prompt\n");
     for (int i = 0; i < manager->prompt_block_count[prompt_id]; i++) {
         int bi = manager->prompt_block_list[prompt_id][i];
-        KVBlock* b = &manager->blocks[bi];
-        if (b->keys) manager->backend.release(manager->backend.ctx, bi, 0, b->keys);
-        if (b->values) manager->backend.release(manager->backend.ctx, bi, 1, b->values);
-        b->keys = NULL;
-        b->values = NULL;
-        b->filled = 0;
-        b->prompt_id = -1;
         manager->prompt_block_list[prompt_id][i] = -1;
-        bm_mark_free(manager, bi);
+        bm_drop_ref(manager, prompt_id, i, bi);
     }
     manager->prompt_block_count[prompt_id] = 0;
     bm_mark_dirty(manager, prompt_id);
 }
 
-/* block_manager.c:92-102: smallest lru_counter strictly below lru_epoch */
+/* block_manager.c:92-102: smallest lru_counter strictly below lru_epoch,
+ * among the pages with a single holder (a page without forks always is) */
 int find_least_recently_used_block(BlockManager* manager) {
     int lru_index = -1;
     int min_lru = manager->lru_epoch;
     for (int i = 0; i < manager->max_blocks; i++) {
-        if (manager->blocks[i].prompt_id != -1 && manager->blocks[i].lru_counter < min_lru) {
+        if (manager->blocks[i].prompt_id != -1 && manager->page_refs[i] <= 1 &&
+            manager->blocks[i].lru_counter < min_lru) {
             min_lru = manager->blocks[i].lru_counter;
             lru_index = i;
         }
@@ -252,24 +277,17 @@ void page_out_lru_block(BlockManager* manager) {
     }
 }
 
-/* block_manager.c:115-162 */
-KVBlock* request_block(BlockManager* manager, int prompt_id) {
-    manager->last_evicted_prompt = -1;
-    if (prompt_id < 0 || prompt_id >= manager->max_prompts) {
-        fprintf(stderr, "Invalid prompt ID.\n");
-        return NULL;
-    }
-    if (manager->prompt_block_count[prompt_id] >= manager->max_blocks_per_prompt) {
-        fprintf(stderr, "Prompt page list is full.\n");
-        return NULL;
-    }
+/* block_manager.c:119-153: the lowest free page, after paging out the LRU
+ * prompt when none is free, with its payload, for prompt_id alone; the caller
+ * puts it into the prompt's list.  -1 with a message when there is none. */
+static int bm_take_page(BlockManager* manager, int prompt_id) {
     int bi = bm_first_free(manager);
     if (bi == -1) {
         page_out_lru_block(manager);
         bi = bm_first_free(manager);
         if (bi == -1) {
             fprintf(stderr, "No blocks available.\n");
-            return NULL;
+            return -1;
         }
     }
     /* the reference mallocs BLOCK_SIZE*C floats each for keys and values (:145-146) */
@@ -282,18 +300,91 @@ KVBlock* request_block(BlockManager* manager, int prompt_id) {
         if (b->keys) manager->backend.release(manager->backend.ctx, bi, 0, b->keys);
         if (b->values) manager->backend.release(manager->backend.ctx, bi, 1, b->values);
         b->keys = b->values = NULL;
-        return NULL;
+        return -1;
     }
     bm_mark_used(manager, bi);
+    manager->page_refs[bi] = 1;
     b->prompt_id = prompt_id;
     b->filled = 0;
     b->lru_counter = ++manager->lru_epoch;
-    int n = manager->prompt_block_count[prompt_id];
+    return bi;
+}
+
+/* block_manager.c:115-162 */
+KVBlock* request_block(BlockManager* manager, int prompt_id) {
+    manager->last_evicted_prompt = -1;
+    if (prompt_id < 0 || prompt_id >= manager->max_prompts) {
+        fprintf(stderr, "Invalid prompt ID.\n");
+        return NULL;
+    }
+    if (manager->prompt_block_count[prompt_id] >= manager->max_blocks_per_prompt) {
+        fprintf(stderr, "Prompt page list is full.\n");
+        return NULL;
+    }
+    int bi = bm_take_page(manager, prompt_id);
+    if (bi == -1) return NULL;
+    int n = manager->prompt_block_count[prompt_id]; /* 0 again when the eviction took prompt_id itself */
     manager->prompt_block_list[prompt_id][n] = bi;
     manager->prompt_block_count[prompt_id] = n + 1;
     bm_mark_dirty(manager, prompt_id);
-    return b;
+    return &manager->blocks[bi];
 }
+
+/* ---------------- shared pages ---------------- */
+int bm_fork_prompt(BlockManager* manager, int src, int dst, int n_pages) {
+    if (src < 0 || src >= manager->max_prompts || dst < 0 || dst >= manager->max_prompts || src == dst) {
+        fprintf(stderr, "bm_fork_prompt: invalid prompt IDs.\n");
+        return 1;
+    }
+    if (manager->prompt_block_count[dst] != 0) {
+        fprintf(stderr, "bm_fork_prompt: the destination prompt owns pages.\n");
+        return 1;
+    }
+    if (n_pages < 0 || n_pages > manager->prompt_block_count[src] || n_pages > manager->max_blocks_per_prompt) {
+        fprintf(stderr, "bm_fork_prompt: page count out of range.\n");
+        return 1;
+    }
+    for (int i = 0; i < n_pages; i++) {
+        int bi = manager->prompt_block_list[src][i];
+        manager->prompt_block_list[dst][i] = bi;
+        if (++manager->page_refs[bi] == 2) manager->shared_pages++;
+    }
+    manager->prompt_block_count[dst] = n_pages;
+    bm_mark_dirty(manager, dst);
+    return 0;
+}
+
+int bm_make_private(BlockManager* manager, int prompt, int index, int* old_page) {
+    manager->last_evicted_prompt = -1;
+    if (prompt < 0 || prompt >= manager->max_prompts || index < 0 ||
+        index >= manager->prompt_block_count[prompt]) {
+        fprintf(stderr, "bm_make_private: no such page.\n");
+        return -1;
+    }
+    int old = manager->prompt_block_list[prompt][index];
+    if (old_page) *old_page = old;
+    if (manager->page_refs[old] <= 1) return old;
+    int bi = bm_take_page(manager, prompt);
+    if (bi == -1) return -1;
+    if (manager->last_evicted_prompt == prompt) { /* its list is gone: hand the fresh page back */
+        manager->prompt_block_list[prompt][0] = bi;
+        manager->prompt_block_count[prompt] = 1;
+        free_blocks_for_prompt(manager, prompt);
+        return -1;
+    }
+    manager->blocks[bi].filled = manager->blocks[old].filled;
+    manager->prompt_block_list[prompt][index] = bi;
+    bm_drop_ref(manager, prompt, index, old);
+    bm_mark_dirty(manager, prompt);
+    return bi;
+}
+
+int bm_page_refs(const BlockManager* manager, int page) {
+    if (page < 0 || page >= manager->max_blocks) return 0;
+    return manager->page_refs[page];
+}
+
+int bm_shared_pages(const BlockManager* manager) { return manager->shared_pages; }
 
 /* block_manager.c:165-201: caller frees kv[0], kv[1], kv */
 float*** collect_kv_blocks(BlockManager* manager, int prompt_id, int* num_blocks) {

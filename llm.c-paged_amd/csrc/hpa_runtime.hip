@@ -63,6 +63,38 @@ __global__ __launch_bounds__(256) void l3_prefetch_kernel(const float4* __restri
     if (acc == 1.2345e-38f && sink) *sink = acc;  // keeps the sum (never true for pool data in practice)
 }
 
+// Page copy inside the pool (hpa_pool_copy_pages): grid (16-byte chunks, layer,
+// pair), the pairs by value in the kernel arguments.  A page of one layer is
+// contiguous, so lane i of a wave moves chunk base + i: 1 KiB per load / store
+// instruction, the widest coalesced form.  4 chunks per thread, every load
+// issued before the first store.
+struct PoolCopyPairs {
+    int src[HPA_COPY_MAX_PAGES];
+    int dst[HPA_COPY_MAX_PAGES];
+};
+constexpr int kCopyThreads = 256, kCopyUnroll = 4;
+
+__global__ __launch_bounds__(kCopyThreads) void pool_copy_pages_kernel(char* __restrict__ base, size_t layer_bytes,
+                                                                       size_t page_bytes, unsigned chunks,
+                                                                       const PoolCopyPairs pairs) {
+    const size_t layer_off = (size_t)blockIdx.y * layer_bytes;
+    const uint4* __restrict__ s =
+        reinterpret_cast<const uint4*>(base + layer_off + (size_t)pairs.src[blockIdx.z] * page_bytes);
+    uint4* __restrict__ d = reinterpret_cast<uint4*>(base + layer_off + (size_t)pairs.dst[blockIdx.z] * page_bytes);
+    const unsigned i0 = blockIdx.x * (kCopyThreads * kCopyUnroll) + threadIdx.x;
+    uint4 v[kCopyUnroll];
+#pragma unroll
+    for (int u = 0; u < kCopyUnroll; ++u) {
+        const unsigned i = i0 + u * kCopyThreads;
+        if (i < chunks) v[u] = s[i];
+    }
+#pragma unroll
+    for (int u = 0; u < kCopyUnroll; ++u) {
+        const unsigned i = i0 + u * kCopyThreads;
+        if (i < chunks) d[i] = v[u];
+    }
+}
+
 extern "C" {
 
 const char* hpa_last_error(void) { return g_last_error; }
@@ -408,6 +440,34 @@ int hpa_pool_set_scales(const HpaKVPool* pool, const float* host_k_scale, const 
     if (e == hipSuccess) e = hipMemcpy(pool->scales, h, n * sizeof(float), hipMemcpyHostToDevice);
     free(h);
     HPA_CHECK(e);
+    return 0;
+}
+
+int hpa_pool_copy_pages(const HpaKVPool* pool, const int* src_pages, const int* dst_pages, int n) {
+    HPA_REQUIRE(pool && pool->base && src_pages && dst_pages, "copy_pages: pool, page lists");
+    HPA_REQUIRE(n >= 1 && n <= HPA_COPY_MAX_PAGES, "copy_pages: 1 <= n <= HPA_COPY_MAX_PAGES");
+    PoolCopyPairs pairs;
+    for (int i = 0; i < n; ++i) {
+        const int s = src_pages[i], t = dst_pages[i];
+        HPA_REQUIRE(s >= 0 && s < pool->num_pages && t >= 0 && t < pool->num_pages, "copy_pages: page out of range");
+        pairs.src[i] = s;
+        pairs.dst[i] = t;
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j) {
+            HPA_REQUIRE(pairs.dst[i] != pairs.src[j], "copy_pages: a page is both a source and a destination");
+            HPA_REQUIRE(i == j || pairs.dst[i] != pairs.dst[j], "copy_pages: a destination appears twice");
+        }
+    for (int i = n; i < HPA_COPY_MAX_PAGES; ++i) pairs.src[i] = pairs.dst[i] = 0;  // never read: grid.z = n
+    const size_t page_bytes = pool->page_elems * pool->elem_bytes;
+    HPA_REQUIRE(page_bytes % 16 == 0 && page_bytes / 16 <= 0xffffffffu, "copy_pages: page bytes");
+    const unsigned chunks = (unsigned)(page_bytes / 16);
+    const unsigned per_block = kCopyThreads * kCopyUnroll;
+    const dim3 grid((chunks + per_block - 1) / per_block, (unsigned)pool->num_layers, (unsigned)n);
+    HPA_REQUIRE(grid.y <= 65535u, "copy_pages: too many layers");
+    pool_copy_pages_kernel<<<grid, kCopyThreads, 0, g_stream>>>((char*)pool->base, pool->layer_elems * pool->elem_bytes,
+                                                                page_bytes, chunks, pairs);
+    HPA_LAUNCH_CHECK();
     return 0;
 }
 

@@ -1464,26 +1464,58 @@ static int dec_upload_tokens(GPT2Decode* d, const int* tokens) {
     return 0;
 }
 
+/* sequence ev was paged out by the allocator: it restarts at position 0 and is
+ * reported by gpt2_decode_evicted.  `busy` (nullable) marks the sequences the
+ * current call works on: losing one of those fails the call. */
+static int dec_note_eviction(GPT2Decode* d, int ev, const int* busy, int* evicted) {
+    if (ev < 0 || ev >= d->B) return 0;
+    if (evicted) ++*evicted;
+    d->h_evicted[ev] = 1;
+    d->h_pos[ev] = 0;
+    if (hpa_memcpy(d->d_pos + ev, &d->h_pos[ev], sizeof(int))) return 1;
+    if (busy && busy[ev]) {
+        fprintf(stderr, "[paged_infer] sequence %d of this batch was evicted: pool too small\n", ev);
+        return 1;
+    }
+    return 0;
+}
+
+/* sequence b is about to append into pages [first, last] of its list: one of
+ * them that it shares with a fork (gpt2_decode_fork shares full pages, and
+ * gpt2_decode_set_positions can rewind into them) is first replaced by a
+ * private copy -- a fresh page, the shared page's bytes of every layer
+ * (hpa_pool_copy_pages, in stream order behind the work that wrote them), the
+ * reference dropped.  Called only while the manager has shared pages. */
+static int dec_unshare(GPT2Decode* d, int b, int first, int last, const int* busy, int* evicted) {
+    for (int i = first; i <= last && i < d->bm->prompt_block_count[b]; i++) {
+        int old = -1;
+        if (bm_page_refs(d->bm, d->bm->prompt_block_list[b][i]) <= 1) continue;
+        const int fresh = bm_make_private(d->bm, b, i, &old);
+        if (dec_note_eviction(d, d->bm->last_evicted_prompt, busy, evicted)) return 1;
+        if (fresh < 0) {
+            if (d->bm->last_evicted_prompt == b) return 0; /* b restarts at 0 without pages: nothing left to copy */
+            return 1;
+        }
+        const int src = d->pv.map[old], dst = d->pv.map[fresh];
+        if (hpa_pool_copy_pages(&d->pool, &src, &dst, 1)) return 1;
+    }
+    return 0;
+}
+
 /* pages for positions pos[b] .. pos[b]+n-1 of sequence b.  The reference
  * policy may evict a whole LRU sequence to make room (block_manager.c:104-162);
  * the evicted sequence restarts at position 0 and is reported by
  * gpt2_decode_evicted.  `busy` (nullable) marks the sequences of the current
  * call: evicting one of those fails the call. */
 static int dec_grow(GPT2Decode* d, int b, int n, const int* busy, int* evicted) {
+    if (bm_shared_pages(d->bm) && dec_unshare(d, b, d->h_pos[b] / d->P, (d->h_pos[b] + n - 1) / d->P, busy, evicted))
+        return 1;
     for (;;) {
         const int need = (d->h_pos[b] + n - 1) / d->P + 1;
         if (d->bm->prompt_block_count[b] >= need) return 0;
         if (!request_block(d->bm, b)) return 1;
-        const int ev = d->bm->last_evicted_prompt; /* may be b itself */
-        if (ev < 0 || ev >= d->B) continue;
-        if (evicted) ++*evicted;
-        d->h_evicted[ev] = 1;
-        d->h_pos[ev] = 0;
-        if (hpa_memcpy(d->d_pos + ev, &d->h_pos[ev], sizeof(int))) return 1;
-        if (busy && busy[ev]) {
-            fprintf(stderr, "[paged_infer] sequence %d of this batch was evicted: pool too small\n", ev);
-            return 1;
-        }
+        /* the victim may be b itself */
+        if (dec_note_eviction(d, d->bm->last_evicted_prompt, busy, evicted)) return 1;
     }
 }
 
@@ -1492,6 +1524,7 @@ static int dec_grow(GPT2Decode* d, int b, int n, const int* busy, int* evicted) 
  * needs a page again: repeat until a pass evicts nobody (bounded). */
 static int dec_ensure_pages(GPT2Decode* d) {
     for (int pass = 0; pass <= d->B; pass++) {
+        const int shared = bm_shared_pages(d->bm); /* 0 unless a fork is live: then dec_grow checks the write page */
         int evictions = 0;
         for (int b = 0; b < d->B; b++) {
             const int p = d->h_pos[b];
@@ -1499,7 +1532,7 @@ static int dec_ensure_pages(GPT2Decode* d) {
                 fprintf(stderr, "[paged_infer] sequence %d is full (%d tokens)\n", b, p);
                 return 1;
             }
-            if (d->bm->prompt_block_count[b] >= p / d->P + 1) continue;
+            if (!shared && d->bm->prompt_block_count[b] >= p / d->P + 1) continue;
             if (dec_grow(d, b, 1, NULL, &evictions)) return 1;
         }
         if (!evictions) return 0;
@@ -2074,6 +2107,67 @@ int gpt2_decode_release(GPT2* model, int seq) {
     return dec_sync_block_table(d);
 }
 
+/* Prefix sharing: dst continues from src's first n_tokens cached tokens
+ * without computing or storing them again.  The full pages of the prefix get
+ * a second holder (bm_fork_prompt); the partly filled page, which both
+ * sequences would append into, is copied into a fresh page of dst's in every
+ * layer by one launch (hpa_pool_copy_pages).  So appends after a fork land in
+ * private pages; dec_unshare covers a rewind into a shared one. */
+int gpt2_decode_fork(GPT2* model, int src, int dst, int n_tokens) {
+    GPT2Decode* d = model->decode;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (src < 0 || src >= d->B || dst < 0 || dst >= d->B || src == dst) {
+        fprintf(stderr, "[paged_infer] fork: no such pair of sequences (%d -> %d)\n", src, dst);
+        return 1;
+    }
+    if (n_tokens == -1) n_tokens = d->h_pos[src];
+    if (n_tokens < 1 || n_tokens > d->h_pos[src]) {
+        fprintf(stderr, "[paged_infer] fork: n_tokens must be 1..%d (the source's position) or -1\n", d->h_pos[src]);
+        return 1;
+    }
+    if (d->h_pos[dst] != 0 || d->bm->prompt_block_count[dst] != 0) {
+        fprintf(stderr, "[paged_infer] fork: sequence %d is live (gpt2_decode_release it first)\n", dst);
+        return 1;
+    }
+    const int P = d->P, full = n_tokens / P, tail = n_tokens % P;
+    if (d->bm->prompt_block_count[src] < full + (tail ? 1 : 0)) {
+        fprintf(stderr, "[paged_infer] fork: sequence %d has no pages for %d tokens\n", src, n_tokens);
+        return 1;
+    }
+    if (hpa_synchronize()) return 1; /* as gpt2_decode_release: queued work may still use the pages */
+    if (bm_fork_prompt(d->bm, src, dst, full)) return 1;
+    if (tail) {
+        const int from = d->pv.map[d->bm->prompt_block_list[src][full]];
+        KVBlock* blk = request_block(d->bm, dst);
+        int* busy = (int*)calloc(d->B, sizeof(int));
+        int rc = !blk || !busy;
+        if (!rc) {
+            busy[src] = 1; /* a fork whose source was paged out to make room has nothing to copy */
+            rc = dec_note_eviction(d, d->bm->last_evicted_prompt, busy, NULL);
+        }
+        free(busy);
+        if (!rc) {
+            const int to = d->pv.map[bm_block_index(d->bm, blk)];
+            rc = hpa_pool_copy_pages(&d->pool, &from, &to, 1);
+        }
+        if (rc) {
+            free_blocks_for_prompt(d->bm, dst);
+            dec_sync_block_table(d);
+            return 1;
+        }
+    }
+    d->h_pos[dst] = n_tokens;
+    if (hpa_memcpy_async(d->d_pos + dst, &d->h_pos[dst], sizeof(int))) return 1;
+    if (n_tokens == d->h_pos[src]) { /* the source's pending next id is the fork's too */
+        if (hpa_memcpy_async(d->d_next + dst, d->d_next + src, sizeof(int)) ||
+            hpa_memcpy_async(d->d_tokens + dst, d->d_tokens + src, sizeof(int)))
+            return 1;
+    }
+    return dec_sync_block_table(d) || hpa_synchronize();
+}
+
+int gpt2_decode_free_pages(GPT2* model) { return model->decode ? bm_free_pages(model->decode->bm) : -1; }
+
 int gpt2_decode_step_async(GPT2* model, const int* tokens) { return dec_enqueue(model, tokens); }
 
 int gpt2_decode_step(GPT2* model, const int* tokens, int* next_tokens) {
@@ -2185,6 +2279,10 @@ int gpt2_decode_fill_random_ex(GPT2* model, int ctx, unsigned long long seed, in
     if (!d) return 1;
     if (ctx < 0 || ctx >= d->max_ctx) {
         fprintf(stderr, "[paged_infer] fill_random: ctx must be < max_ctx\n");
+        return 1;
+    }
+    if (bm_shared_pages(d->bm)) {
+        fprintf(stderr, "[paged_infer] fill_random: pages are shared between sequences (release the forks first)\n");
         return 1;
     }
     if (gpt2_decode_reset(model)) return 1;
@@ -2792,6 +2890,8 @@ int gpt2_decode_reserve(GPT2* model, int ctx) {
     if (!d || ctx < 0 || ctx > d->max_ctx) return 1;
     for (int b = 0; b < d->B; b++) {
         const int need = (ctx + d->P - 1) / d->P;
+        /* the pages the steps up to ctx append into are b's own (a fork's shared pages are copied now) */
+        if (bm_shared_pages(d->bm) && dec_unshare(d, b, d->h_pos[b] / d->P, need - 1, NULL, NULL)) return 1;
         while (d->bm->prompt_block_count[b] < need)
             if (!request_block(d->bm, b)) return 1;
     }

@@ -215,6 +215,13 @@ def lib():
     _sig(L, "bm_free_pages", i, [v])
     _sig(L, "bm_use_host_pages", None, [v])
     _sig(L, "bm_default_backend_kind", i, [])
+    _sig(L, "bm_fork_prompt", i, [v, i, i, i])
+    _sig(L, "bm_make_private", i, [v, i, i, _I])
+    _sig(L, "bm_page_refs", i, [v, i])
+    _sig(L, "bm_shared_pages", i, [v])
+    _sig(L, "hpa_pool_copy_pages", i, [P, _I, _I, i])
+    _sig(L, "gpt2_decode_fork", i, [v, i, i, i])
+    _sig(L, "gpt2_decode_free_pages", i, [v])
     # model + decode engine
     _sig(L, "gpt2_alloc", v, [])
     _sig(L, "gpt2_release", None, [v])
@@ -546,6 +553,16 @@ class Pool:
             v[t0:t0 + n] = vt[:, :n, :].transpose(1, 0, 2).reshape(n, NH * HS)
         return k, v
 
+    def copy_pages(self, src, dst):
+        """hpa_pool_copy_pages: page src[i] -> page dst[i] in every layer, one
+        asynchronous launch (1..HPA_COPY_MAX_PAGES pairs of pool slots)"""
+        s = np.ascontiguousarray(src, np.int32).reshape(-1)
+        d = np.ascontiguousarray(dst, np.int32).reshape(-1)
+        if s.size != d.size:
+            raise ValueError("copy_pages: src and dst differ in length")
+        check(lib().hpa_pool_copy_pages(self.ref, s.ctypes.data_as(_I), d.ctypes.data_as(_I), int(s.size)),
+              "pool_copy_pages")
+
     def destroy(self):
         if self.s.base:
             lib().hpa_pool_destroy(self.ref)
@@ -592,6 +609,19 @@ class Tokenizer(ctypes.Structure):
 
 
 # ---------------------------------------------------------------- block manager
+class BlockManagerStruct(ctypes.Structure):
+    """include/block_manager.h BlockManager, field for field"""
+    _fields_ = [("C", ctypes.c_int), ("blocks", ctypes.POINTER(KVBlock)),
+                ("prompt_block_list", ctypes.POINTER(_I)), ("prompt_block_count", _I),
+                ("lru_epoch", ctypes.c_int), ("max_prompts", ctypes.c_int), ("max_blocks", ctypes.c_int),
+                ("block_size", ctypes.c_int), ("max_blocks_per_prompt", ctypes.c_int), ("block_table", _I),
+                ("free_bits", ctypes.POINTER(ctypes.c_ulonglong)), ("free_words", ctypes.c_int),
+                ("free_hint", ctypes.c_int), ("free_count", ctypes.c_int),
+                ("backend_alloc", _V), ("backend_release", _V), ("backend_ctx", _V),
+                ("dirty_lo", ctypes.c_int), ("dirty_hi", ctypes.c_int), ("last_evicted_prompt", ctypes.c_int),
+                ("page_refs", _I), ("shared_pages", ctypes.c_int)]
+
+
 class BlockManager:
     """block_manager.c API (create_block_manager, request_block, ...)."""
 
@@ -616,6 +646,39 @@ class BlockManager:
         base = ctypes.cast(self.h, ctypes.POINTER(ctypes.c_void_p))
         blocks = ctypes.cast(base[1], ctypes.POINTER(KVBlock))  # BlockManager.blocks
         return blocks[index]
+
+    def fork(self, src, dst, n_pages):
+        """bm_fork_prompt: dst (owning no pages) shares src's first n_pages
+        pages; raises on a bad argument (nothing changed then)"""
+        if lib().bm_fork_prompt(self.h, int(src), int(dst), int(n_pages)) != 0:
+            raise ValueError(f"bm_fork_prompt({src}, {dst}, {n_pages}) refused")
+
+    def refs(self, page):
+        """holders of a page (0 = free)"""
+        return lib().bm_page_refs(self.h, int(page))
+
+    def shared_pages(self):
+        """pages with more than one holder"""
+        return lib().bm_shared_pages(self.h)
+
+    def free_pages(self):
+        return lib().bm_free_pages(self.h)
+
+    def free_prompt(self, prompt):
+        lib().free_blocks_for_prompt(self.h, int(prompt))
+
+    def struct(self):
+        """the C struct (fields of include/block_manager.h)"""
+        return ctypes.cast(self.h, ctypes.POINTER(BlockManagerStruct)).contents
+
+    def pages(self, prompt):
+        """the prompt's page list"""
+        bm = self.struct()
+        return [bm.prompt_block_list[prompt][i] for i in range(bm.prompt_block_count[prompt])]
+
+    def last_evicted(self):
+        """the prompt the last request_block paged out, or -1"""
+        return self.struct().last_evicted_prompt
 
     def close(self):
         if self.h:
@@ -855,6 +918,18 @@ class Model:
     def release(self, seq):
         """retire sequence seq: pages back to the pool, position 0"""
         check(lib().gpt2_decode_release(self.h, int(seq)), "release")
+
+    def fork(self, src, dst, n_tokens=-1):
+        """gpt2_decode_fork: slot dst (fresh or released) continues from the
+        first n_tokens cached tokens of slot src (-1: all of them), sharing
+        its full pages and copying only the partly filled one.  With all of
+        them dst also inherits src's pending next id (step(None) continues
+        both); its sampler state stays its own."""
+        check(lib().gpt2_decode_fork(self.h, int(src), int(dst), int(n_tokens)), "fork")
+
+    def free_pages(self):
+        """free pages of the engine's block manager"""
+        return lib().gpt2_decode_free_pages(self.h)
 
     def set_sampling(self, enable=True, seed=1337):
         check(lib().gpt2_decode_set_sampling(self.h, int(bool(enable)), int(seed)), "set_sampling")
