@@ -185,6 +185,7 @@ def lib():
     _sig(L, "hpa_attn_ws_bytes", sz, [i, i, i])
     _sig(L, "hpa_attn_pick_splits", i, [i, i, i, i])
     _sig(L, "hpa_paged_attention_decode_split", i, [v, P, i, v, i, v, v, i, i, v, i])
+    _sig(L, "hpa_paged_attention_decode_split_w", i, [v, P, i, v, i, v, v, i, i, v, i, i])
     _sig(L, "hpa_comm_id_bytes", sz, [])
     _sig(L, "hpa_comm_unique_id", i, [v, sz])
     _sig(L, "hpa_comm_init", i, [i, i, v])
