@@ -17,8 +17,12 @@
  *       -Wl,-rpath,$PWD/llm.c-paged_amd -o decode_main
  *   ./decode_main [-c checkpoint.bin] [-k tokenizer.bin] [-t tokens.bin]
  *                 [-b B] [-p prompt_len] [-n new_tokens] [-g] [-o ids.bin] [-q]
+ *                 [--temperature X] [--top-k N] [--top-p X]
  *     -g greedy (default: sampling as the reference), -o writes the B x
  *     (prompt + new) token ids as int32, -q prints only the summary line.
+ *     --temperature / --top-k / --top-p: any of them selects filtered
+ *     sampling (gpt2_decode_set_sampling mode 2) with these settings for
+ *     every sequence (defaults 1, 0 = off, 1 = off); -g still wins.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -41,7 +45,8 @@ static void print_token(Tokenizer* tk, int id) {
 
 int main(int argc, char** argv) {
     const char *ckpt = NULL, *tok_path = NULL, *tokens_path = NULL, *ids_out = NULL;
-    int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0;
+    int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
+    float temperature = 1.0f, top_p = 1.0f;
     for (int i = 1; i < argc; i++) {
         const char* a = argv[i];
         const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -55,6 +60,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "-b")) B = atoi(v);
         else if (!strcmp(a, "-p")) prompt_len = atoi(v);
         else if (!strcmp(a, "-n")) new_tokens = atoi(v);
+        else if (!strcmp(a, "--temperature")) { temperature = (float)atof(v); filtered = 1; }
+        else if (!strcmp(a, "--top-k")) { top_k = atoi(v); filtered = 1; }
+        else if (!strcmp(a, "--top-p")) { top_p = (float)atof(v); filtered = 1; }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         i++;
     }
@@ -76,7 +84,8 @@ int main(int argc, char** argv) {
     if (!bm) return 1;
     model.manager = bm;
     if (gpt2_decode_init(&model, B, page_size, total)) return 1;
-    if (!greedy && gpt2_decode_set_sampling(&model, 1, 1337ULL)) return 1; /* rng_state = 1337 (:975) */
+    if (!greedy && gpt2_decode_set_sampling(&model, filtered ? 2 : 1, 1337ULL)) return 1; /* rng_state = 1337 (:975) */
+    if (!greedy && filtered && gpt2_decode_set_sampling_params(&model, -1, temperature, top_k, top_p)) return 2;
     gpt2_decode_set_graph(&model, 1);
 
     int* gen = (int*)malloc((size_t)B * total * sizeof(int));

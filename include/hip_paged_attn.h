@@ -595,6 +595,35 @@ int hpa_sample_final(const float* logits, int B, int V, unsigned long long* stat
  * cross-check of hpa_sample_final's integer-scan formulation */
 int hpa_sample_final_serial(const float* logits, int B, int V, unsigned long long* state, int* next, int* tokens,
                             int* pos, const int* active);
+/* temperature / top-k / top-p sampling with per-row settings (device arrays
+ * [B]: temperature, top_k, top_p).  active, tokens, pos and next as in
+ * hpa_sample_final; an inactive row changes nothing, its state included.
+ * Per active row b, x = logits[b]:
+ *  - coin: the row's xorshift state advances exactly once per call (greedy
+ *    rows too), u = (xorshift_u32(state) >> 8) / 16777216.0f;
+ *  - temperature[b] == 0: greedy, the argmax of x (lowest index on ties),
+ *    n_kept = 1, cut = max x;
+ *  - canonical order: tokens by (logit descending, index ascending);
+ *  - top-k: k = top_k[b]; 0 or k >= V keeps everything, else the first k
+ *    tokens of the canonical order (exact: temperature keeps the order);
+ *  - probabilities over the top-k set, T = temperature[b], m = max x:
+ *    p_i = exp((x_i - m) / T) / sum_kept exp((x_j - m) / T);
+ *  - top-p: P = top_p[b] in (0, 1] keeps the shortest prefix of the canonical
+ *    order, inside the top-k set, whose mass is >= P; at least one token;
+ *    P = 1 keeps the whole top-k set;
+ *  - n_kept[b]: the length of that prefix; cut[b]: the logit of its last
+ *    token (both nullable).  The kept set is every token with x > cut plus
+ *    the lowest-indexed tokens with x == cut, n_kept in all;
+ *  - draw: over the kept tokens in index order (as sample_mult walks them),
+ *    renormalised to the kept mass: the first kept index whose running cdf
+ *    exceeds u.
+ * Bad per-row values cannot index out of range: T < 0 or non-finite counts as
+ * 1, k < 0 as 0, P outside (0, 1] as 1.  Sums are fixed-point integers
+ * (hpa_sample.hip), so a launch repeated on the same inputs and states
+ * returns the same ids. */
+int hpa_sample_filtered(const float* logits, int B, int V, const float* temperature, const int* top_k,
+                        const float* top_p, unsigned long long* state, int* next, int* tokens, int* pos,
+                        const int* active, int* n_kept, float* cut);
 /* paged decode attention writing its output in frag layout ([B][C]) */
 int hpa_paged_attention_decode_frag(const float* q, const HpaKVPool* pool, int layer,
                                     const int* block_table, int bt_stride, const int* pos,

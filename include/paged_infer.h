@@ -187,7 +187,9 @@ int  gpt2_decode_prefill(GPT2* model, const int* tokens, int T, int* next_tokens
  * id, sampler state).  next_tokens[b] is each sequence's next id. */
 int  gpt2_decode_prefill_ragged(GPT2* model, const int* tokens, const int* lens, int* next_tokens);
 /* retire sequence seq: its pages go back to the pool (block_manager.c:78-90),
- * its position restarts at 0, so the slot can admit a new prompt */
+ * its position restarts at 0, so the slot can admit a new prompt.  The slot's
+ * sampler state and sampling settings (gpt2_decode_set_sampling_params) stay
+ * as they are */
 int  gpt2_decode_release(GPT2* model, int seq);
 /* prefix sharing: sequence dst continues from the first n_tokens cached tokens
  * of sequence src (n_tokens in [1, pos[src]], or -1 for pos[src]) without
@@ -202,8 +204,8 @@ int  gpt2_decode_release(GPT2* model, int seq);
  * reads, as in any reused page).  pos[dst] = n_tokens.  When n_tokens ==
  * pos[src], dst also inherits src's pending next id, so gpt2_decode_step(model,
  * NULL, ...) continues both; otherwise dst has no valid next id until it is fed
- * tokens.  dst's sampler state is untouched (seeded seed + dst), so forks of
- * one prompt draw different tokens.  Only full pages are shared and the tail
+ * tokens.  dst's sampler state and sampling settings are untouched (seeded
+ * seed + dst), so forks of one prompt draw different tokens.  Only full pages are shared and the tail
  * is copied here, so appends after a fork land in private pages; a sequence
  * rewound into a shared page (gpt2_decode_set_positions) gets a private copy
  * of it before its next append.  The LRU policy never evicts the holder of a
@@ -339,10 +341,29 @@ int    gpt2_decode_time_attention(GPT2* model, int iters, double* ms_per_launch,
  * of each part (per-iteration events) */
 int    gpt2_decode_time_attention_pf(GPT2* model, int iters, double frac, int pf_grid, double* ms_attn,
                                      double* ms_pf);
-/* token choice: 0 = greedy argmax (default); 1 = multinomial sampling as the
- * reference driver (softmax_forward + sample_mult with random_f32 coins),
- * sequence b seeded with seed + b; the coins stay on the device */
+/* token choice: 0 = greedy argmax (default); 1 (and any nonzero value but 2)
+ * = multinomial sampling as the reference driver (softmax_forward +
+ * sample_mult with random_f32 coins); 2 = filtered: temperature / top-k /
+ * top-p per sequence (hpa_sample_filtered states the rules), same coins.
+ * Sequence b is seeded with seed + b; the coins stay on the device */
 int    gpt2_decode_set_sampling(GPT2* model, int enable, unsigned long long seed);
+/* mode 2's settings of sequence seq in [0, B), or of every sequence (seq =
+ * -1).  Valid: temperature finite and >= 0 (0 = greedy for that sequence),
+ * top_k >= 0 (0 = off), 0 < top_p <= 1 (1 = off); anything else returns
+ * nonzero with a message and changes nothing.  Defaults 1, 0, 1.  They live in
+ * device arrays the kernel reads, so changing them keeps the captured graph;
+ * they can be set in any mode and only mode 2 reads them.  Waits for queued
+ * work like gpt2_decode_release.  gpt2_decode_release, gpt2_decode_fork and
+ * eviction leave a slot's settings and sampler state untouched. */
+int    gpt2_decode_set_sampling_params(GPT2* model, int seq, float temperature, int top_k, float top_p);
+/* the settings of sequence seq (each out pointer nullable); nonzero for seq
+ * out of range */
+int    gpt2_decode_sampling_params(GPT2* model, int seq, float* temperature, int* top_k, float* top_p);
+/* restart sequence seq's coin stream at seed, so a request admitted into a
+ * released slot draws a reproducible stream of its own.  Nonzero before any
+ * gpt2_decode_set_sampling call (no states yet) and for seq out of range.
+ * Waits for queued work. */
+int    gpt2_decode_seed_sequence(GPT2* model, int seq, unsigned long long seed);
 /* algorithmic HBM bytes one step reads+writes at the current positions
  * (SURVEY.md 8d formula) and the attention kernel's share of them */
 double gpt2_decode_step_bytes(GPT2* model, double* attention_bytes);

@@ -185,12 +185,7 @@ __global__ __launch_bounds__(256) void argmax_final_kernel(const float* __restri
 // stay sequential (one lane), everything else is parallel (see the kernel).
 // Each sequence has its own xorshift state, advanced once per draw on the
 // device.
-__device__ __forceinline__ unsigned int xorshift_u32(unsigned long long& s) {
-    s ^= s >> 12;
-    s ^= s << 25;
-    s ^= s >> 27;
-    return (unsigned int)((s * 0x2545F4914F6CDD1Dull) >> 32);
-}
+using hpa::xorshift_u32;  // the reference's generator (hpa_internal.h)
 
 constexpr int kSampPer = 16;                 // elements per lane per block
 constexpr int kSampBlk = 64 * kSampPer;     // 1024 elements per block

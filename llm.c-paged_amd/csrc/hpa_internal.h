@@ -101,6 +101,15 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
+// the reference's xorshift* generator (random_u32, paged_infer.c:826-830); the
+// samplers' coin is (xorshift_u32(state) >> 8) / 16777216.0f (random_f32)
+__device__ __forceinline__ unsigned int xorshift_u32(unsigned long long& s) {
+    s ^= s >> 12;
+    s ^= s << 25;
+    s ^= s >> 27;
+    return (unsigned int)((s * 0x2545F4914F6CDD1Dull) >> 32);
+}
+
 // "frag" layout of a [rows][K] fp32 matrix (rows padded to 16, K % 16 == 0),
 // the operand layout of v_mfma_f32_16x16x4_f32 loaded 16 bytes per lane:
 // element (m, k) sits at lane (m%16) + 16*((k%16)/4), float (k%4) of the

@@ -665,8 +665,14 @@ struct GPT2Decode {
     int attn_waves;   /* waves per attention workgroup (hpa_attn_pick_waves of the global batch) */
     void* d_attn_ws;  /* split records + counters (hpa_attn_ws_bytes at HPA_ATTN_MAX_SPLITS) */
     size_t attn_ws_bytes;
-    int sample;       /* 0: greedy argmax; 1: multinomial with per-sequence xorshift */
+    int sample;       /* 0: greedy argmax; 1: multinomial with per-sequence xorshift; 2: filtered */
     unsigned long long* d_rng; /* [B] sampler states */
+    float* d_samp_t;  /* [B] per-sequence temperature, top-k, top-p (read by mode 2 only) */
+    int* d_samp_k;
+    float* d_samp_p;
+    float* h_samp_t;  /* host mirrors (gpt2_decode_sampling_params) */
+    int* h_samp_k;
+    float* h_samp_p;
     /* prefill workspace (gpt2_decode_prefill), rows R = sum of lengths, grown on demand */
     int pf_cap;
     float *pf_res, *pf_res2, *pf_att, *pf_fch, *pf_st1, *pf_st2, *pf_q;
@@ -776,6 +782,12 @@ static void dec_shard_free(GPT2Decode* d) {
     d->shard = NULL;
 }
 
+static int dec_upload_sampling_params(GPT2Decode* d) {
+    return hpa_memcpy(d->d_samp_t, d->h_samp_t, d->B * sizeof(float)) ||
+           hpa_memcpy(d->d_samp_k, d->h_samp_k, d->B * sizeof(int)) ||
+           hpa_memcpy(d->d_samp_p, d->h_samp_p, d->B * sizeof(float));
+}
+
 /* every teardown and error path: a caller-owned manager gets its pages back
  * and its default backend, so it never keeps pointers into the freed pool */
 static void dec_free(GPT2Decode* d) {
@@ -810,6 +822,8 @@ static void dec_free(GPT2Decode* d) {
     hpa_free(d->pl_rec); hpa_free(d->pl_slab); hpa_free(d->pl_ctr);
     hpa_free(d->d_pipe_lay); hpa_free(d->pipe_slab);
     hpa_free(d->d_rng);
+    hpa_free(d->d_samp_t); hpa_free(d->d_samp_k); hpa_free(d->d_samp_p);
+    free(d->h_samp_t); free(d->h_samp_k); free(d->h_samp_p);
     hpa_free(d->pos_logits);
     hpa_host_free(d->h_next);
     free(d->pv.map);
@@ -1363,8 +1377,19 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
     d->st1 = (float*)hpa_malloc((size_t)ct * Mp * 2 * 4);
     d->st2 = (float*)hpa_malloc((size_t)ct * Mp * 2 * 4);
     d->part = (float*)hpa_malloc((size_t)((V + 15) / 16) * Mp * 2 * 4);
+    d->d_samp_t = (float*)hpa_malloc(B * sizeof(float));
+    d->d_samp_k = (int*)hpa_malloc(B * sizeof(int));
+    d->d_samp_p = (float*)hpa_malloc(B * sizeof(float));
+    d->h_samp_t = (float*)malloc(B * sizeof(float));
+    d->h_samp_k = (int*)malloc(B * sizeof(int));
+    d->h_samp_p = (float*)malloc(B * sizeof(float));
     int ok = d->d_bt && d->d_pos && d->d_tokens && d->d_next && d->h_pos && d->h_evicted && d->h_next && d->d_q &&
-             d->d_logits && d->res && d->res2 && d->att && d->fch && d->st1 && d->st2 && d->part;
+             d->d_logits && d->res && d->res2 && d->att && d->fch && d->st1 && d->st2 && d->part &&
+             d->d_samp_t && d->d_samp_k && d->d_samp_p && d->h_samp_t && d->h_samp_k && d->h_samp_p;
+    if (ok) { /* temperature 1, no top-k, no top-p */
+        for (int b = 0; b < B; b++) { d->h_samp_t[b] = 1.0f; d->h_samp_k[b] = 0; d->h_samp_p[b] = 1.0f; }
+        ok = dec_upload_sampling_params(d) == 0;
+    }
     /* logits GEMM: the activation-resident kernel where it applies (C = 768,
      * B <= 64); stream-K where its shape limits allow (XL at B <= 64), which
      * needs a slab and zeroed counters; else the looped kernel */
@@ -1643,6 +1668,9 @@ static int dec_gemm(GPT2* model, int l, int which) {
 static int dec_pick(GPT2* model, const int* active) {
     GPT2Decode* d = model->decode;
     const int V = model->config.vocab_size;
+    if (d->sample == 2)
+        return hpa_sample_filtered(d->d_logits, d->B, V, d->d_samp_t, d->d_samp_k, d->d_samp_p, d->d_rng, d->d_next,
+                                   d->d_tokens, d->d_pos, active, NULL, NULL);
     if (d->sample)
         return hpa_sample_final(d->d_logits, d->B, V, d->d_rng, d->d_next, d->d_tokens, d->d_pos, active);
     HpaFusedGemm g;
@@ -1808,13 +1836,62 @@ int gpt2_decode_set_sampling(GPT2* model, int enable, unsigned long long seed) {
     const int rc = hpa_memcpy(d->d_rng, h, d->B * sizeof(unsigned long long));
     free(h);
     if (rc) return 1;
-    d->sample = enable ? 1 : 0;
+    d->sample = enable == 2 ? 2 : enable ? 1 : 0;
     if (d->graph) { /* recapture with the other token-choice kernel */
         hpa_graph_destroy(d->graph);
         d->graph = NULL;
         if (dec_rezero(d)) return 1;
     }
     return 0;
+}
+
+/* per-sequence temperature / top-k / top-p of mode 2 (seq = -1: every
+ * sequence).  The kernel reads them from device memory, so a captured graph
+ * stays valid. */
+int gpt2_decode_set_sampling_params(GPT2* model, int seq, float temperature, int top_k, float top_p) {
+    GPT2Decode* d = model->decode;
+    if (!d) return 1;
+    if (seq < -1 || seq >= d->B) {
+        fprintf(stderr, "[paged_infer] set_sampling_params: sequence %d out of range\n", seq);
+        return 1;
+    }
+    if (!(temperature >= 0.0f) || isinf(temperature) || top_k < 0 || !(top_p > 0.0f && top_p <= 1.0f)) {
+        fprintf(stderr, "[paged_infer] set_sampling_params: need temperature finite and >= 0, top_k >= 0, "
+                        "0 < top_p <= 1 (got %g, %d, %g)\n", (double)temperature, top_k, (double)top_p);
+        return 1;
+    }
+    if (hpa_synchronize()) return 1; /* queued steps still read the old values */
+    for (int b = seq < 0 ? 0 : seq; b < (seq < 0 ? d->B : seq + 1); b++) {
+        d->h_samp_t[b] = temperature;
+        d->h_samp_k[b] = top_k;
+        d->h_samp_p[b] = top_p;
+    }
+    return dec_upload_sampling_params(d);
+}
+
+int gpt2_decode_sampling_params(GPT2* model, int seq, float* temperature, int* top_k, float* top_p) {
+    GPT2Decode* d = model->decode;
+    if (!d || seq < 0 || seq >= d->B) return 1;
+    if (temperature) *temperature = d->h_samp_t[seq];
+    if (top_k) *top_k = d->h_samp_k[seq];
+    if (top_p) *top_p = d->h_samp_p[seq];
+    return 0;
+}
+
+/* restart sequence seq's coin stream at `seed` (a request admitted into a
+ * released slot gets a reproducible stream of its own) */
+int gpt2_decode_seed_sequence(GPT2* model, int seq, unsigned long long seed) {
+    GPT2Decode* d = model->decode;
+    if (!d || !d->d_rng) {
+        fprintf(stderr, "[paged_infer] seed_sequence: gpt2_decode_set_sampling first\n");
+        return 1;
+    }
+    if (seq < 0 || seq >= d->B) {
+        fprintf(stderr, "[paged_infer] seed_sequence: sequence %d out of range\n", seq);
+        return 1;
+    }
+    if (hpa_synchronize()) return 1; /* a queued step may still draw from the old state */
+    return hpa_memcpy(d->d_rng + seq, &seed, sizeof(seed));
 }
 
 int gpt2_decode_set_graph(GPT2* model, int enable) {

@@ -251,6 +251,9 @@ def lib():
     _sig(L, "gpt2_decode_prefill_ragged", i, [v, _I, _I, _I])
     _sig(L, "gpt2_decode_release", i, [v, i])
     _sig(L, "gpt2_decode_set_sampling", i, [v, i, ctypes.c_ulonglong])
+    _sig(L, "gpt2_decode_set_sampling_params", i, [v, i, ctypes.c_float, i, ctypes.c_float])
+    _sig(L, "gpt2_decode_sampling_params", i, [v, i, _F, _I, _F])
+    _sig(L, "gpt2_decode_seed_sequence", i, [v, i, ctypes.c_ulonglong])
     _sig(L, "hpa_paged_attention_prefill", i, [_F, v, i, _I, i, _I, i, i, _F])
     _sig(L, "hpa_paged_attention_prefill_ragged", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
     _sig(L, "hpa_gather_rows_frag", i, [_F, _F, i, _I, i, _F, _F, i, i])
@@ -312,6 +315,7 @@ def lib():
     _sig(L, "hpa_argmax_final", i, [v, i, i, i, v, v, v, v])
     _sig(L, "hpa_sample_final", i, [v, i, i, v, v, v, v, v])
     _sig(L, "hpa_sample_final_serial", i, [v, i, i, v, v, v, v, v])
+    _sig(L, "hpa_sample_filtered", i, [v, i, i, v, v, v, v, v, v, v, v, v, v])
     _sig(L, "hpa_paged_attention_decode_frag", i, [v, P, i, v, i, v, v, i])
     _sig(L, "gpt2_decode_set_positions", i, [v, _I])
     _sig(L, "gpt2_decode_logits", v, [v])
@@ -932,8 +936,29 @@ class Model:
         """free pages of the engine's block manager"""
         return lib().gpt2_decode_free_pages(self.h)
 
-    def set_sampling(self, enable=True, seed=1337):
-        check(lib().gpt2_decode_set_sampling(self.h, int(bool(enable)), int(seed)), "set_sampling")
+    def set_sampling(self, enable=True, seed=1337, filtered=False):
+        """token choice: greedy (enable=False), the reference's multinomial
+        draw, or with filtered=True temperature / top-k / top-p per sequence
+        (set_sampling_params); sequence b's coins start at seed + b"""
+        mode = 2 if (enable and filtered) else int(bool(enable))
+        check(lib().gpt2_decode_set_sampling(self.h, mode, int(seed)), "set_sampling")
+
+    def set_sampling_params(self, seq=-1, temperature=1.0, top_k=0, top_p=1.0):
+        """filtered sampling's settings of sequence seq (-1: every sequence):
+        temperature >= 0 (0 = greedy), top_k >= 0 (0 = off), 0 < top_p <= 1"""
+        check(lib().gpt2_decode_set_sampling_params(self.h, int(seq), float(temperature), int(top_k),
+                                                    float(top_p)), "set_sampling_params")
+
+    def sampling_params(self, seq):
+        """(temperature, top_k, top_p) of sequence seq"""
+        t, k, p = ctypes.c_float(), ctypes.c_int(), ctypes.c_float()
+        check(lib().gpt2_decode_sampling_params(self.h, int(seq), ctypes.byref(t), ctypes.byref(k),
+                                                ctypes.byref(p)), "sampling_params")
+        return t.value, k.value, p.value
+
+    def seed_sequence(self, seq, seed):
+        """restart sequence seq's coin stream at seed"""
+        check(lib().gpt2_decode_seed_sequence(self.h, int(seq), int(seed)), "seed_sequence")
 
     def gemm_config(self, waves=None, row_blocks=None, col_tiles=None):
         """fused GEMM launch shapes [qkv, attproj, fc, fcproj, logits]:
