@@ -359,7 +359,7 @@ void hpa_fused_pick_bf16(int M, int N, int K, int* out3);
  * out3 = {waves, row_blocks, rounds}; returns 1 where variant 0 uses it */
 int hpa_fused_pick_bf16_ares(int M, int N, int K, int* out3);
 int hpa_fused_pick_waves(int M, int N, int K);
-/* ---------------- persistent decode layer (hpa_layer.hip) ----------------
+/* ---------------- persistent decode layer (hpa_layer.hip and the form files behind it) ----------------
  * The decode step's layer loop (reference gpt2_forward, paged_infer.c:659-722)
  * as ONE launch per layer l instead of five:
  *   attention(l) -> attproj(l) -> fc(l) -> fcproj(l) -> qkv(l+1)

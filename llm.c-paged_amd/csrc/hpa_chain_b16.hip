@@ -3,7 +3,7 @@
 // per layer:
 //     attproj(l) -> fc(l) -> fcproj(l) -> qkv(l+1)
 // after the layer's decode-attention launch (reference gpt2_forward,
-// paged_infer.c:659-722; the same phases as chain form 6, hpa_layer.hip, which
+// paged_infer.c:659-722; the same phases as chain form 6, hpa_chain6.hip, which
 // is fp32-only with the LayerNorms folded into the weights and B <= 64).
 // Replaces four bf16 GEMM launches per layer (qkv / attproj / fc / fcproj,
 // 16.5 + 8.8 + 14.0 + 8.8 us at B = 256 in round 4's step).
@@ -33,6 +33,7 @@
 #include <math.h>
 
 #include "hpa_gemm_body.h"
+#include "hpa_handoff.h"
 
 namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -40,15 +41,18 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));
 
 namespace cb {
+using hpa::drain_vm;
+using hpa::kPad;  // ints per counter line (128 B)
+using hpa::kSpinTicks;
+using hpa::ld4;
+using hpa::lds_barrier;
 constexpr int NW = 8, NT = NW * 64;
 constexpr int C = 768, K16 = 48, K32 = 24, NCT = 48;
 constexpr int SPW = K32 / NW;  // 32-deep k-steps per wave of a 768 range
-constexpr int kPad = 32;       // ints per counter line (128 B)
 // counter lines: X1[16] attproj tiles done per row block, H[16][4] fc tile
 // groups done per (row block, fcproj K part), X2[16] fcproj combines per row
 // block, tickets[4][16] per (fcproj row quad, tile group)
 constexpr int kX1 = 0, kH = 16, kX2 = 80, kTick = 96, kLines = 160;
-constexpr long long kSpinTicks = 20000000;  // s_memrealtime is 100 MHz: 200 ms
 // phase shapes (RG row blocks, T tiles, NG tile groups) by the per-CU operand
 // bytes of a unit (fp32 A: 48 KiB per row block, read sc1 -- measured about
 // twice the cost per byte of the L2-served weights; bf16 A and weights 24 KiB
@@ -94,7 +98,7 @@ struct Smem {
 };
 
 // diagnostic build (-DHPA_LAYER_TRACE, tools/pl_trace.py b16): s_memrealtime
-// of workgroup-level events per (layer, workgroup), slots as hpa_layer.hip's
+// of workgroup-level events per (layer, workgroup), slots as hpa_chain6.hip's
 // (0 start, 4/6/8/10 phase B/C/D/E wait done, 12/13/14 B/C/D stored,
 // 5/7/9 B/C/D arrived, 15 E folded, 11 end); never in the product library
 #ifdef HPA_LAYER_TRACE
@@ -110,16 +114,6 @@ __device__ unsigned long long g_cb_trace[64][256][16];
     } while (0)
 #endif
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// every storing wave drained (the builtin form: the compiler then knows
-// vmcnt is 0 and does not wait again, past the next phase's weight loads)
-__device__ __forceinline__ void drain_vm() {
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
 
 __device__ __forceinline__ bf16x8 pack_bf16(float4 a, float4 b) {
@@ -150,6 +144,9 @@ __device__ __forceinline__ void arrive(const Args& a, int line) {
     __hip_atomic_fetch_add(a.ctr + line * kPad, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// This kernel keeps its own copy of the bounded wait (the protocol and the
+// bound are hpa_handoff.h's wait_wg / spin_bounded): with the shared one its
+// spin compiles with two more waits (profiles/r10/README.md).
 // wave 0 polls the n (0..4) counter lines base, base + stride, .. until all
 // reach `expected` (bounded; the other waves wait at the barrier)
 __device__ __forceinline__ bool wait_lines(const Args& a, int base, int stride, int n, int expected, int code,
@@ -384,8 +381,7 @@ __device__ __forceinline__ void where(int e, int rb0, int j0, int& row, int& col
 // qkv epilogue store of columns col..col+3 of `row`: q row-major, or K / V of
 // this token (position ps, page `page`, loaded by phase E before its wait)
 // into the sequence's page of layer l+1 (add_to_cache, paged_infer.c:505-573;
-// fp32 pool K [chunk of 4][slot][4], bf16 pool K [chunk of 8][slot][8] RNE,
-// V [slot][64])
+// hpa::kv_store4)
 template <int P, bool BF>
 __device__ __forceinline__ void qkv_store(const Args& a, int row, int col, int ps, int page, float4 v) {
     constexpr int NH = 12;
@@ -398,17 +394,8 @@ __device__ __forceinline__ void qkv_store(const Args& a, int row, int col, int p
     const int hh = c >> 6, d = c & 63;
     if (page < 0) return;  // no page (host bug): never write below the pool
     const int pslot = ps % P;
-    const size_t toff = (size_t)page * a.page_elems + ((size_t)kv * NH + hh) * P * 64;
-    if constexpr (BF) {
-        unsigned short* kvt = reinterpret_cast<unsigned short*>(a.kv_next) + toff +
-                              (kv == 0 ? ((d >> 3) * P + pslot) * 8 + (d & 7) : pslot * 64 + d);
-        const unsigned lo = hpa::f32_to_bf16(v.x) | ((unsigned)hpa::f32_to_bf16(v.y) << 16);
-        const unsigned hi = hpa::f32_to_bf16(v.z) | ((unsigned)hpa::f32_to_bf16(v.w) << 16);
-        *reinterpret_cast<uint2*>(kvt) = make_uint2(lo, hi);
-    } else {
-        float* kvt = reinterpret_cast<float*>(a.kv_next) + toff + (kv == 0 ? ((d >> 2) * P + pslot) * 4 : pslot * 64 + d);
-        *reinterpret_cast<float4*>(kvt) = v;
-    }
+    const size_t toff = hpa::kv_tile_off(page, a.page_elems, NH, kv, hh, P);
+    hpa::kv_store4<BF ? 8 : 4>(a.kv_next, toff, kv, d, pslot, P, v);
 }
 
 }  // namespace cb

@@ -203,23 +203,9 @@ struct Epi {
                             const int page = p.bt[(size_t)seq * p.bt_stride + ps / p.P];
                             if (page < 0) continue;  // no page (host bug): never write below the pool
                             const int slot = ps % p.P;
-                            const size_t toff = (size_t)page * p.page_elems + ((size_t)kv * p.NH + hh) * p.P * 64;
-                            if (p.kv_dtype == HPA_FP8) {  // fp8 pool: K [chunk of 16][slot][16], V [slot][64], e4m3fn codes
-                                unsigned char* kvt = reinterpret_cast<unsigned char*>(p.kv_base) + toff;
-                                const float inv = p.kv_scales[((size_t)kv * p.NH + hh) * 2 + 1];
-                                kvt[kv == 0 ? ((d >> 4) * p.P + slot) * 16 + (d & 15) : slot * 64 + d] =
-                                    hpa::f32_to_e4m3(val, inv);
-                            } else if (p.kv_dtype == HPA_BF16) {  // bf16 pool: K [chunk of 8][slot][8], V [slot][64], RNE
-                                unsigned short* kvt = reinterpret_cast<unsigned short*>(p.kv_base) + toff;
-                                kvt[kv == 0 ? ((d >> 3) * p.P + slot) * 8 + (d & 7) : slot * 64 + d] =
-                                    hpa::f32_to_bf16(val);
-                            } else {
-                                float* kvt = p.kv_base + toff;
-                                if (kv == 0)
-                                    kvt[((d >> 2) * p.P + slot) * 4 + (d & 3)] = val;  // K: [chunk][slot][4]
-                                else
-                                    kvt[slot * 64 + d] = val;  // V: [slot][64]
-                            }
+                            const size_t toff = hpa::kv_tile_off(page, p.page_elems, p.NH, kv, hh, p.P);
+                            hpa::kv_store1_rt(p.kv_dtype, p.kv_base, toff, kv, d, slot, p.P, val, p.kv_scales,
+                                           ((size_t)kv * p.NH + hh) * 2 + 1);
                         }
                     }
                 } else if (EPI == HPA_FEPI_GELU) {

@@ -166,6 +166,91 @@ __device__ __forceinline__ float4 e4m3x4_to_f32(unsigned w) {
     return make_float4(lo.x, lo.y, hi.x, hi.y);
 }
 
+// The K/V slot of the pool layout (hip_paged_attn.h), in elements of the pool's
+// dtype.  A page holds [K | V][head] tiles of P slots x 64 dims: the tile of
+// (kv, head) of `page` starts at kv_tile_off from the layer's base.  Within
+// it K is [chunk of 16 B][slot][chunk] -- CH = 4 (fp32), 8 (bf16) or 16 (fp8)
+// elements per chunk -- and V is [slot][64].  (hs: the head size, 64 in every
+// kernel; the host's index functions pass the pool's.)
+__host__ __device__ __forceinline__ size_t kv_tile_off(int page, const size_t& page_elems, int NH, int kv, int head,
+                                                       int P, int hs = 64) {
+    return (size_t)page * page_elems + ((size_t)kv * NH + head) * P * hs;
+}
+template <int CH>  // the chunk of dim d at `slot`
+__host__ __device__ __forceinline__ int kv_k_chunk(int d, int slot, int P) {
+    static_assert(CH == 4 || CH == 8 || CH == 16, "K chunks of 16 bytes: fp32, bf16 or fp8 elements");
+    constexpr int SH = CH == 4 ? 2 : CH == 8 ? 3 : 4;
+    return ((d >> SH) * P + slot) * CH;
+}
+template <int CH>
+__host__ __device__ __forceinline__ int kv_k_off(int d, int slot, int P) {
+    return kv_k_chunk<CH>(d, slot, P) + (d & (CH - 1));
+}
+__host__ __device__ __forceinline__ int kv_v_off(int d, int slot, int hs = 64) { return slot * hs + d; }
+template <int CH>  // ... of K (kv = 0) or V (kv = 1)
+__host__ __device__ __forceinline__ int kv_off(int kv, int d, int slot, int P) {
+    return kv == 0 ? kv_k_off<CH>(d, slot, P) : kv_v_off(d, slot);
+}
+
+// The K/V stores of every decode path (add_to_cache, paged_infer.c:505-573)
+// into the tile at toff = kv_tile_off(..) of the layer at `layer`: fp32 as is,
+// bf16 RNE, fp8 the e4m3fn codes of val * inv (inv: the tile's entry of the
+// pool's scales).  A caller computes toff once, ahead of any branch on the
+// pool's dtype.
+// kv_store4: dims d .. d+3 (d % 4 == 0) of one slot as one 16 B, 8 B or 4 B
+// store
+template <int CH>
+__device__ __forceinline__ void kv_store4(void* layer, size_t toff, int kv, int d, int slot, int P, float4 v,
+                                          float inv = 1.f) {
+    if constexpr (CH == 4) {  // four dims are one whole fp32 chunk
+        float* kvt = reinterpret_cast<float*>(layer) + toff + (kv == 0 ? kv_k_chunk<4>(d, slot, P) : kv_v_off(d, slot));
+        *reinterpret_cast<float4*>(kvt) = v;
+    } else if constexpr (CH == 8) {
+        unsigned short* kvt = reinterpret_cast<unsigned short*>(layer) + toff + kv_off<8>(kv, d, slot, P);
+        const unsigned lo = f32_to_bf16(v.x) | ((unsigned)f32_to_bf16(v.y) << 16);
+        const unsigned hi = f32_to_bf16(v.z) | ((unsigned)f32_to_bf16(v.w) << 16);
+        *reinterpret_cast<uint2*>(kvt) = make_uint2(lo, hi);
+    } else {
+        unsigned char* kvt = reinterpret_cast<unsigned char*>(layer) + toff + kv_off<16>(kv, d, slot, P);
+        *reinterpret_cast<unsigned*>(kvt) = f32x4_to_e4m3(v.x, v.y, v.z, v.w, inv);
+    }
+}
+// kv_store1: one dim; inv: fp8 pools
+template <int CH>
+__device__ __forceinline__ void kv_store1(void* layer, size_t toff, int kv, int d, int slot, int P, float val,
+                                          float inv = 1.f) {
+    if constexpr (CH == 16) {
+        unsigned char* kvt = reinterpret_cast<unsigned char*>(layer) + toff;
+        kvt[kv_off<16>(kv, d, slot, P)] = f32_to_e4m3(val, inv);
+    } else if constexpr (CH == 8) {
+        unsigned short* kvt = reinterpret_cast<unsigned short*>(layer) + toff;
+        kvt[kv_off<8>(kv, d, slot, P)] = f32_to_bf16(val);
+    } else {
+        float* kvt = reinterpret_cast<float*>(layer) + toff;
+        kvt[kv_off<4>(kv, d, slot, P)] = val;
+    }
+}
+// kv_store1_rt: ... by the pool's run-time dtype; scales[sidx]: the tile's inv (read by fp8
+// pools only).  SPLIT32: an fp32 pool's K and V as two stores under a branch
+// on kv, the form the GEMM epilogues were tuned with (else one store at a
+// selected address)
+template <bool SPLIT32 = true>
+__device__ __forceinline__ void kv_store1_rt(int dtype, void* layer, size_t toff, int kv, int d, int slot, int P, float val,
+                                          const float* scales, size_t sidx) {
+    if (dtype == HPA_FP8) {
+        kv_store1<16>(layer, toff, kv, d, slot, P, val, scales[sidx]);
+    } else if (dtype == HPA_BF16) {
+        kv_store1<8>(layer, toff, kv, d, slot, P, val);
+    } else if (SPLIT32) {
+        if (kv == 0)
+            kv_store1<4>(layer, toff, 0, d, slot, P, val);
+        else
+            kv_store1<4>(layer, toff, 1, d, slot, P, val);
+    } else {
+        kv_store1<4>(layer, toff, kv, d, slot, P, val);
+    }
+}
+
 // GELU of the reference (paged_infer.c:243-251): 0.5 x (1 + tanh(sqrt(2/pi)(x + 0.044715 x^3)))
 __device__ __forceinline__ float gelu_ref(float x) {
     // sqrtf(2.0f / M_PI) as the reference computes it: float(2/pi) then sqrtf

@@ -63,17 +63,14 @@
 
 #include "hpa_attn_body.h"
 #include "hpa_gemm_body.h"
+#include "hpa_handoff.h"
 
 namespace {
-using hpa_attn::HS;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using hpa::kPad;
 
-constexpr int C = 768, NH = 12, K16 = 48, NCT = 48;  // GPT-2 124M
-constexpr int NWV = 12;                              // waves per workgroup (every role)
-constexpr int SPW = 4;                               // k16 steps per wave of a K = 768 range
-constexpr int kPad = 32;                             // ints per counter shard (one 128-B line)
-constexpr long long kSpinTicks = 20000000;           // s_memrealtime is 100 MHz: 200 ms
-constexpr int kDefaultG = 64;
+// what hpa_decode_pipe_sizes needs (every build)
+constexpr int NCT = 48;  // 16-column tiles of C = 768 (GPT-2 124M)
+constexpr int kT = 3;    // tiles per unit of fc / fcproj / qkv: 64 / 64 / 48 units
 
 // counters of layer l, half h: counter c's 8 shards at ((h*kNC + c)*8 + shard)*kPad
 //   QKV    qkv(l) units of the half done (written by chain(l-1, h))
@@ -84,6 +81,20 @@ constexpr int kDefaultG = 64;
 enum { PC_QKV = 0, PC_ATT = 1, PC_X1 = 2, PC_H = 3, PC_X2 = 7, kNC = 8 };
 constexpr int kTick = 2 * kNC * 8 * kPad;
 constexpr int kLayerInts = kTick + 2 * 32;
+
+#ifdef HPA_AB  // the kernel and its launch: A/B builds only (the product library compiles no device code here)
+using hpa::drain_vm;
+using hpa::kSpinTicks;
+using hpa::ld4;
+using hpa::lds_barrier;
+using hpa::wave_sum_int;
+using hpa_attn::HS;
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int C = 768, NH = 12, K16 = 48;  // GPT-2 124M
+constexpr int NWV = 12;                    // waves per workgroup (every role)
+constexpr int SPW = 4;                     // k16 steps per wave of a K = 768 range
+constexpr int kDefaultG = 64;
 
 struct PA {
     int B, L, NG, NA, stats_mp;
@@ -124,8 +135,6 @@ struct PSmem {
     int s_ok;
 };
 
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 // diagnostic build (-DHPA_PIPE_TRACE, tools/pipe_trace.py): s_memrealtime of
 // workgroup-level events per (layer, half, workgroup); never in the product library
 #ifdef HPA_PIPE_TRACE
@@ -141,27 +150,17 @@ __device__ unsigned long long g_pipe_trace[2 * 64][256][12];
     } while (0)
 #endif
 
-// every storing wave drained (the builtin: the compiler then knows vmcnt is 0)
-__device__ __forceinline__ void drain_vm() {
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0) expcnt(7) lgkmcnt(15)
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __device__ __forceinline__ int* ctr_of(const PA& a, int l, int h, int c) {
     return a.ctr + (size_t)l * a.layer_ctr + (size_t)(h * kNC + c) * 8 * kPad;
 }
 
 // one lane, after every storing wave's drain and the workgroup barrier
-__device__ __forceinline__ void arrive(int* c, int n) {
-    __hip_atomic_fetch_add(c + (blockIdx.x & 7) * kPad, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+__device__ __forceinline__ void arrive(int* c, int n) { hpa::arrive_shard(c, n); }
 
+// This kernel keeps its own copy of the bounded wait (the protocol and the
+// bound are hpa_handoff.h's wait_wg / spin_bounded): with the shared one the
+// A role spills one more register in five of the eight instantiations
+// (profiles/r10/README.md).
 // every thread calls; wave 0 polls the 8 shards of `c` until they sum to
 // `expected` (bounded), the others wait at the barrier
 template <typename SM>
@@ -484,7 +483,6 @@ __device__ __forceinline__ float4 ln4(const float* ws, int er, float4 v, float4 
     return v;
 }
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 
 // chain(l, h): one call per (layer, half).  Not inlined into the layer loop:
@@ -665,9 +663,9 @@ __device__ __attribute__((noinline)) bool g_chain(const PA& a, PSmem<HR, T>& smu
                         const int kv = col >= 2 * C;
                         const int c = col - (kv ? 2 * C : C);
                         const int hh = c >> 6, d = c & 63;
-                        const int pslot = ps % P;
-                        const size_t toff = (size_t)page * a.page_elems + ((size_t)kv * NH + hh) * P * 64 +
-                                            (kv == 0 ? ((d >> 2) * P + pslot) * 4 : pslot * 64 + d);
+                        const int pslot = ps % P;  // the slot's offset (hpa_internal.h), stored write-through
+                        const size_t toff = hpa::kv_tile_off(page, a.page_elems, NH, kv, hh, P) +
+                                            (kv == 0 ? hpa::kv_k_chunk<4>(d, pslot, P) : hpa::kv_v_off(d, pslot));
                         hpa::store_wt16(a.kv + (size_t)(l + 1) * a.layer_bytes, (int)(toff * 4), v);
                     }
                 }
@@ -702,8 +700,6 @@ __global__ __launch_bounds__(768) void decode_pipe_kernel(PA args) {
         a_role<P, HR, T>(a, sm);
 }
 
-constexpr int kT = 3;  // tiles per unit of fc / fcproj / qkv: 64 / 64 / 48 units
-
 template <int P, int HR>
 int launch_pipe(PA& a) {
     HPA_REQUIRE((hpa::resident_blocks<decode_pipe_kernel<P, HR, kT>>(768) >= 1),
@@ -724,6 +720,7 @@ bool pipe_shape(int B, int ncu, int g_cus, int* HR) {
     *HR = hr;
     return true;
 }
+#endif  // HPA_AB
 
 }  // namespace
 
@@ -739,9 +736,10 @@ int hpa_decode_pipe_eligible_cus(int B, int C_, int num_heads, int kv_dtype, int
     (void)kv_dtype;
     (void)ncu;
     return 0;
-#endif
+#else
     int hr = 0;
     return C_ == C && num_heads == NH && kv_dtype == HPA_F32 && ncu > 0 && pipe_shape(B, ncu, kDefaultG, &hr) ? 1 : 0;
+#endif
 }
 int hpa_decode_pipe_eligible(int B, int C_, int num_heads, int kv_dtype) {
     return hpa_decode_pipe_eligible_cus(B, C_, num_heads, kv_dtype, hpa::num_cus());
@@ -750,7 +748,7 @@ int hpa_decode_pipe_eligible(int B, int C_, int num_heads, int kv_dtype) {
 // trace build only: the stamps of the last launch ([2 * layers][256][12] u64,
 // s_memrealtime ticks of 10 ns); host NULL clears them.  1 in the product build.
 int hpa_decode_pipe_trace(unsigned long long* host, int layers) {
-#ifdef HPA_PIPE_TRACE
+#if defined(HPA_AB) && defined(HPA_PIPE_TRACE)
     HPA_REQUIRE(layers >= 0 && layers <= 64, "pipe trace: layers 0..64");
     if (!host) {
         static unsigned long long zero[2 * 64 * 256 * 12];

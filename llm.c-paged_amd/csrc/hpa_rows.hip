@@ -25,7 +25,6 @@ __global__ __launch_bounds__(256) void pool_fill_random_kernel(void* __restrict_
     const int C = NH * 64;
     const int page = bt[(size_t)b * bt_stride + p / P];
     const int slot = p % P;
-    const size_t off = (size_t)l * layer_elems + (size_t)page * page_elems;
     const uint64_t key = (((uint64_t)l * 4096u + bg) * 1048576u + p) * 4u;
     for (int i = threadIdx.x; i < 2 * C; i += 256) {
         const int kv = i >= C;
@@ -33,18 +32,11 @@ __global__ __launch_bounds__(256) void pool_fill_random_kernel(void* __restrict_
         const int hh = c >> 6, d = c & 63;
         const uint64_t r = splitmix64(seed ^ (key * 2654435761ull + (uint64_t)i));
         const float u = (float)(r >> 40) * (1.0f / 16777216.0f) * 2.0f - 1.0f;
-        const size_t tile = off + ((size_t)kv * NH + hh) * P * 64;
-        if (dtype == HPA_FP8) {  // scales: [L][2][NH][2] (scale, inv)
-            unsigned char* t = reinterpret_cast<unsigned char*>(base_v) + tile;
-            const float inv = scales[(((size_t)l * 2 + kv) * NH + hh) * 2 + 1];
-            t[kv == 0 ? ((d >> 4) * P + slot) * 16 + (d & 15) : slot * 64 + d] = hpa::f32_to_e4m3(u, inv);
-        } else if (dtype == HPA_BF16) {
-            unsigned short* t = reinterpret_cast<unsigned short*>(base_v) + tile;
-            t[kv == 0 ? ((d >> 3) * P + slot) * 8 + (d & 7) : slot * 64 + d] = hpa::f32_to_bf16(u);
-        } else {
-            float* t = reinterpret_cast<float*>(base_v) + tile;
-            t[kv == 0 ? ((d >> 2) * P + slot) * 4 + (d & 3) : slot * 64 + d] = u;
-        }
+        // the tile of (kv, hh) of the page, from the pool's base
+        const size_t tile = (size_t)l * layer_elems + hpa::kv_tile_off(page, page_elems, NH, kv, hh, P);
+        // scales: [L][2][NH][2] (scale, inv); one store per element (SPLIT32 = false)
+        hpa::kv_store1_rt</*SPLIT32=*/false>(dtype, base_v, tile, kv, d, slot, P, u, scales,
+                                             (((size_t)l * 2 + kv) * NH + hh) * 2 + 1);
     }
 }
 

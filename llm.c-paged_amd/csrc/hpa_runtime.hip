@@ -479,18 +479,15 @@ void* hpa_pool_tile(const HpaKVPool* p, int layer, int page, int kv, int head) {
 }
 
 size_t hpa_pool_k_index(const HpaKVPool* p, int layer, int page, int head, int slot, int d) {
-    size_t tile = (size_t)p->page_size * p->head_size;
-    size_t base = (size_t)layer * p->layer_elems + (size_t)page * p->page_elems + (size_t)head * tile;
-    if (p->dtype == HPA_FP8) return base + ((size_t)(d >> 4) * p->page_size + slot) * 16 + (d & 15);
-    if (p->dtype == HPA_BF16) return base + ((size_t)(d >> 3) * p->page_size + slot) * 8 + (d & 7);
-    return base + ((size_t)(d >> 2) * p->page_size + slot) * 4 + (d & 3);
+    const int P = p->page_size;
+    return (size_t)layer * p->layer_elems + hpa::kv_tile_off(page, p->page_elems, p->num_heads, 0, head, P, p->head_size) +
+           (p->dtype == HPA_FP8 ? hpa::kv_k_off<16>(d, slot, P)
+                                : p->dtype == HPA_BF16 ? hpa::kv_k_off<8>(d, slot, P) : hpa::kv_k_off<4>(d, slot, P));
 }
 
 size_t hpa_pool_v_index(const HpaKVPool* p, int layer, int page, int head, int slot, int d) {
-    size_t tile = (size_t)p->page_size * p->head_size;
-    size_t base = (size_t)layer * p->layer_elems + (size_t)page * p->page_elems +
-                  ((size_t)p->num_heads + head) * tile;
-    return base + (size_t)slot * p->head_size + d;
+    return (size_t)layer * p->layer_elems + hpa::kv_tile_off(page, p->page_elems, p->num_heads, 1, head, p->page_size, p->head_size) +
+           hpa::kv_v_off(d, slot, p->head_size);
 }
 
 }  // extern "C"

@@ -2442,24 +2442,20 @@ int gpt2_decode_read_kv(GPT2* model, int l, int b, int n, float* k, float* v) {
         for (int t = p0; t < n && t < p0 + P && !rc; t++)
             for (int h = 0; h < NH; h++)
                 for (int x = 0; x < 64; x++) {
-                    const int s = t - p0;
-                    /* K [chunk][slot][4|8|16], V [slot][64] (hip_paged_attn.h pool layout) */
-                    const size_t ki = eb == 4   ? ((size_t)(x >> 2) * P + s) * 4 + (x & 3)
-                                      : eb == 2 ? ((size_t)(x >> 3) * P + s) * 8 + (x & 7)
-                                                : ((size_t)(x >> 4) * P + s) * 16 + (x & 15);
-                    const size_t vi = (size_t)s * 64 + x;
-                    const size_t kt = (size_t)h * tile, vt = (size_t)(NH + h) * tile;
+                    /* the slot within buf, the copy of one page of one layer (pool layout: hpa_internal.h kv_*_off) */
+                    const size_t ki = hpa_pool_k_index(&d->pool, 0, 0, h, t - p0, x);
+                    const size_t vi = hpa_pool_v_index(&d->pool, 0, 0, h, t - p0, x);
                     float kf, vf;
                     if (eb == 4) {
-                        kf = ((const float*)buf)[kt + ki];
-                        vf = ((const float*)buf)[vt + vi];
+                        kf = ((const float*)buf)[ki];
+                        vf = ((const float*)buf)[vi];
                     } else if (eb == 1) { /* decode(code) * scale, an fp32 product */
                         const size_t LN = (size_t)model->config.num_layers * NH;
-                        kf = e4m3[buf[kt + ki]] * d->h_kv_scale[(size_t)l * NH + h];
-                        vf = e4m3[buf[vt + vi]] * d->h_kv_scale[LN + (size_t)l * NH + h];
+                        kf = e4m3[buf[ki]] * d->h_kv_scale[(size_t)l * NH + h];
+                        vf = e4m3[buf[vi]] * d->h_kv_scale[LN + (size_t)l * NH + h];
                     } else {
-                        const unsigned ku = (unsigned)((const unsigned short*)buf)[kt + ki] << 16;
-                        const unsigned vu = (unsigned)((const unsigned short*)buf)[vt + vi] << 16;
+                        const unsigned ku = (unsigned)((const unsigned short*)buf)[ki] << 16;
+                        const unsigned vu = (unsigned)((const unsigned short*)buf)[vi] << 16;
                         memcpy(&kf, &ku, 4);
                         memcpy(&vf, &vu, 4);
                     }

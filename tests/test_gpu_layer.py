@@ -1,4 +1,4 @@
-"""The persistent decode layer (hpa_layer.hip: attention -> attproj -> fc ->
+"""The persistent decode layer (hpa_layer_units.hip, hpa_chain6.hip, hpa_chain8.hip behind hpa_layer.hip: attention -> attproj -> fc ->
 fcproj -> next qkv as one launch per layer) against the five-launch layer and
 the oracle.
 

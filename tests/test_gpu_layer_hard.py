@@ -198,7 +198,7 @@ def _ab_only(hip, select):
     _case(768, 12, 64, 16, "f32", 2, 1), _case(768, 12, 17, 8, "f32", 2, 1),
 ])
 def test_layer_peaked_persistent_layer(hip, C, NH, B, P, kv, select, form):
-    """request 2, hpa_layer.hip: the full persistent layer carries its own attention units"""
+    """request 2, hpa_layer_units.hip: the full persistent layer carries its own attention units"""
     _ab_only(hip, select)
     _run_case(hip, C, NH, B, P, kv, select, form)
 

@@ -2,7 +2,7 @@
 per-(layer, half, workgroup) s_memrealtime stamps.
 
 usage: HPA_LIB=llm.c-paged_amd/libpl_pt.so python tools/pipe_trace.py [B] [ctx] [g_cus]
-  (the library: make -C llm.c-paged_amd BUILD=build_pt LIB=libpl_pt.so XFLAGS=-DHPA_PIPE_TRACE)
+  (the library: make -C llm.c-paged_amd BUILD=build_pt LIB=libpl_pt.so XFLAGS="-DHPA_AB -DHPA_PIPE_TRACE")
 
 Prints, for every (layer, half) of the last step, the A role's attention
 window (first wait done .. last unit done over the A workgroups) and the G
@@ -42,7 +42,7 @@ def main():
     for _ in range(8):
         m.step(toks)
     if L.hpa_decode_pipe_trace(None, 0) != 0:
-        raise SystemExit("not a trace build (XFLAGS=-DHPA_PIPE_TRACE)")
+        raise SystemExit('not a trace build (XFLAGS="-DHPA_AB -DHPA_PIPE_TRACE")')
     m.step(toks)
     m.status()
     nl = cfg["L"]

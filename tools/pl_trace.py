@@ -1,4 +1,4 @@
-"""Phase timeline of the persistent decode layer (hpa_layer.hip), from the
+"""Phase timeline of the persistent decode layer (hpa_layer_units.hip, hpa_chain6.hip, hpa_chain8.hip), from the
 trace build's per-(layer, workgroup) s_memrealtime stamps.
 
 usage: HPA_LIB=llm.c-paged_amd/libpaged_hip_trace.so python tools/pl_trace.py [B] [ctx] [mode] [XL|b16]
