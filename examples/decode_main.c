@@ -17,12 +17,17 @@
  *       -Wl,-rpath,$PWD/llm.c-paged_amd -o decode_main
  *   ./decode_main [-c checkpoint.bin] [-k tokenizer.bin] [-t tokens.bin]
  *                 [-b B] [-p prompt_len] [-n new_tokens] [-g] [-o ids.bin] [-q]
- *                 [--temperature X] [--top-k N] [--top-p X]
+ *                 [--temperature X] [--top-k N] [--top-p X] [--perplexity] [--logprobs]
  *     -g greedy (default: sampling as the reference), -o writes the B x
  *     (prompt + new) token ids as int32, -q prints only the summary line.
  *     --temperature / --top-k / --top-p: any of them selects filtered
  *     sampling (gpt2_decode_set_sampling mode 2) with these settings for
  *     every sequence (defaults 1, 0 = off, 1 = off); -g still wins.
+ *     --perplexity: the prompt pass is gpt2_decode_score with shifted targets
+ *     (token t+1 scores position t): prints the mean negative log-likelihood
+ *     and its exp per sequence and overall.  --logprobs: prints sequence 0's
+ *     log-probability beside each generated token (gpt2_decode_set_logprobs:
+ *     the raw model distribution, whatever the sampling settings).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -38,6 +43,17 @@ static double now_s(void) {
     return t.tv_sec + 1e-9 * t.tv_nsec;
 }
 
+/* e^x without libm (this file links against libpaged_hip only): halve the
+ * argument into [-0.5, 0.5], Taylor series, square back */
+static double exp_d(double x) {
+    int n = 0;
+    while (x > 0.5 || x < -0.5) { x *= 0.5; n++; }
+    double s = 1.0, term = 1.0;
+    for (int i = 1; i < 20; i++) { term *= x / i; s += term; }
+    while (n--) s *= s;
+    return s;
+}
+
 static void print_token(Tokenizer* tk, int id) {
     if (tk->init_ok) safe_printf(tokenizer_decode(tk, (unsigned)id));
     else printf("%d ", id);
@@ -46,12 +62,15 @@ static void print_token(Tokenizer* tk, int id) {
 int main(int argc, char** argv) {
     const char *ckpt = NULL, *tok_path = NULL, *tokens_path = NULL, *ids_out = NULL;
     int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
+    int perplexity = 0, logprobs = 0;
     float temperature = 1.0f, top_p = 1.0f;
     for (int i = 1; i < argc; i++) {
         const char* a = argv[i];
         const char* v = i + 1 < argc ? argv[i + 1] : NULL;
         if (!strcmp(a, "-g")) { greedy = 1; continue; }
         if (!strcmp(a, "-q")) { quiet = 1; continue; }
+        if (!strcmp(a, "--perplexity")) { perplexity = 1; continue; }
+        if (!strcmp(a, "--logprobs")) { logprobs = 1; continue; }
         if (!v) { fprintf(stderr, "missing value for %s\n", a); return 2; }
         if (!strcmp(a, "-c")) ckpt = v;
         else if (!strcmp(a, "-k")) tok_path = v;
@@ -86,12 +105,14 @@ int main(int argc, char** argv) {
     if (gpt2_decode_init(&model, B, page_size, total)) return 1;
     if (!greedy && gpt2_decode_set_sampling(&model, filtered ? 2 : 1, 1337ULL)) return 1; /* rng_state = 1337 (:975) */
     if (!greedy && filtered && gpt2_decode_set_sampling_params(&model, -1, temperature, top_k, top_p)) return 2;
+    if (logprobs && gpt2_decode_set_logprobs(&model, 1)) return 1;
     gpt2_decode_set_graph(&model, 1);
 
     int* gen = (int*)malloc((size_t)B * total * sizeof(int));
     int* prompt = (int*)malloc((size_t)B * prompt_len * sizeof(int));
     int* next = (int*)malloc(B * sizeof(int));
-    if (!gen || !prompt || !next) return 1;
+    float* lp = (float*)malloc(B * sizeof(float));
+    if (!gen || !prompt || !next || !lp) return 1;
     if (tokens_path) { /* int32 tokens, e.g. a prepro_tinyshakespeare.py .bin */
         FILE* f = fopen(tokens_path, "rb");
         if (!f || fread(prompt, sizeof(int), (size_t)B * prompt_len, f) != (size_t)B * prompt_len) {
@@ -116,8 +137,38 @@ int main(int argc, char** argv) {
     }
     double t0 = now_s();
     /* the whole prompt of every sequence in one pass; next[b] = the first new token */
-    if (gpt2_decode_prefill(&model, prompt, prompt_len, next)) return 1;
+    if (perplexity) { /* the same pass, scoring every prompt token against its successor */
+        const size_t R = (size_t)B * prompt_len;
+        int* lens = (int*)malloc(B * sizeof(int));
+        int* targets = (int*)malloc(R * sizeof(int));
+        float* score = (float*)malloc(R * sizeof(float));
+        if (!lens || !targets || !score) return 1;
+        for (int b = 0; b < B; b++) {
+            lens[b] = prompt_len;
+            for (int t = 0; t < prompt_len; t++)
+                targets[(size_t)b * prompt_len + t] = t + 1 < prompt_len ? prompt[(size_t)b * prompt_len + t + 1] : -1;
+        }
+        if (gpt2_decode_score(&model, prompt, lens, targets, score, NULL, next)) return 1;
+        double all = 0.0;
+        for (int b = 0; b < B && prompt_len > 1; b++) {
+            double nll = 0.0;
+            for (int t = 0; t + 1 < prompt_len; t++) nll -= score[(size_t)b * prompt_len + t];
+            all += nll;
+            nll /= prompt_len - 1;
+            printf("sequence %d: mean NLL %.6f, perplexity %.4f over %d tokens\n", b, nll, exp_d(nll), prompt_len - 1);
+        }
+        if (prompt_len > 1) {
+            all /= (double)B * (prompt_len - 1);
+            printf("overall: mean NLL %.6f, perplexity %.4f over %d tokens\n", all, exp_d(all), B * (prompt_len - 1));
+        }
+        free(lens);
+        free(targets);
+        free(score);
+    } else if (gpt2_decode_prefill(&model, prompt, prompt_len, next)) {
+        return 1;
+    }
     double t1 = now_s();
+    if (logprobs && gpt2_decode_logprobs(&model, lp)) return 1;
     for (int b = 0; b < B; b++) {
         memcpy(gen + (size_t)b * total, prompt + (size_t)b * prompt_len, prompt_len * sizeof(int));
         if (new_tokens > 0) gen[(size_t)b * total + prompt_len] = next[b];
@@ -125,11 +176,14 @@ int main(int argc, char** argv) {
     if (!quiet) printf("\ngenerating:\n---\n");
     for (int t = 1; t < new_tokens; t++) {
         if (!quiet) print_token(&tk, next[0]);
+        if (!quiet && logprobs) printf("[%.4f] ", lp[0]);
         /* the previous ids stay on the device and feed this step */
         if (gpt2_decode_step(&model, NULL, next)) return 1;
+        if (logprobs && gpt2_decode_logprobs(&model, lp)) return 1;
         for (int b = 0; b < B; b++) gen[(size_t)b * total + prompt_len + t] = next[b];
     }
     if (!quiet && new_tokens > 0) print_token(&tk, next[0]);
+    if (!quiet && logprobs && new_tokens > 0) printf("[%.4f] ", lp[0]);
     double t2 = now_s();
     if (!quiet) printf("\n---\nFinished!\n");
     printf("prefill %d x %d tokens in %.3f ms; generated %d tokens x %d sequences (%s) in %.3f ms: "
@@ -144,6 +198,7 @@ int main(int argc, char** argv) {
     free(gen);
     free(prompt);
     free(next);
+    free(lp);
     gpt2_free(&model);         /* does not free the manager (reference ownership) */
     destroy_block_manager(bm);
     return 0;

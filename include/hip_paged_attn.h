@@ -232,7 +232,7 @@ int hpa_pack_frag_bf16(const float* src, int rows, int K, int ld, void* dst);
  * the `ntiles` partials of a row in order: mean = S1/C, var = S2/C - mean^2,
  * rstd = 1/sqrtf(var + 1e-5) (layernorm_forward, paged_infer.c:49-89, in its
  * one-pass form) and applies (x - mean) * rstd * w + b to its A fragments. */
-enum { HPA_FEPI_QKV = 0, HPA_FEPI_RESID = 1, HPA_FEPI_GELU = 2, HPA_FEPI_LOGITS = 3 };
+enum { HPA_FEPI_QKV = 0, HPA_FEPI_RESID = 1, HPA_FEPI_GELU = 2, HPA_FEPI_LOGITS = 3, HPA_FEPI_SCORE = 4 };
 typedef struct {
     /* A = x (frag layout, M rows, K cols), optionally LayerNorm'ed on the fly */
     const float* x;
@@ -251,6 +251,8 @@ typedef struct {
        (NULL: no statistics -- the consumer folds its LN and sums its own) */
     /* GELU: out = gelu(acc + bias) (frag layout [M][N]) */
     /* LOGITS: out = acc [M][N] row-major (ld = N); part_out[N/16 tiles][Mp][2] = (max, argmax) */
+    /* SCORE: the LOGITS arithmetic with a log-softmax epilogue: no out (may be NULL), the logits
+       never reach memory; score_part[N/16 tiles][Mp][4] row partials (below) */
     float* out;
     const float* res_in;
     float* stats_out;
@@ -320,6 +322,18 @@ typedef struct {
     int* pick_tokens;
     int* pick_pos;
     int* pick_count;
+    /* SCORE (looped fp32 kernel: variant 0 / 1; bf16 weights: variant 0 / 1 / 5; any other
+     * variant is refused).  score_target: device [M], the column whose logit each row
+     * reports, -1 (or a NULL array) = none.  score_part: device, hpa_score_workspace(N,
+     * Mp) floats, 16-byte aligned; per (16-column tile t, row m) one float4 at
+     * [(t * Mp + m) * 4]:
+     *   .x  m_t = the maximum of the tile's columns < N
+     *   .y  sum over those columns of expf(v - m_t), added in column order
+     *   .z  the target's logit when the target column lies in the tile, else -inf
+     *   .w  the bits of the tile's first-maximum column (lowest column wins, as LOGITS)
+     * Rows M <= m < Mp get (-inf, 0, -inf, 16 t): no NaN.  hpa_score_final combines them. */
+    const int* score_target;
+    float* score_part;
 } HpaFusedGemm;
 /* LayerNorm folding for hpa_gemm_fused (layernorm_forward :49-89 followed by
  * matmul_forward :92-114, restated): for W [N][K] row-major (device), writes
@@ -583,6 +597,28 @@ int hpa_embed_frag_zero(const int* tokens, const int* pos, const float* wte, con
  * active (nullable, [B]): rows with active[b] <= 0 are left untouched */
 int hpa_argmax_final(const float* part, int ntiles, int Mp, int B, int* next, int* tokens, int* pos,
                      const int* active);
+/* ---------------- log-probabilities (hpa_score.hip) ----------------
+ * floats in the SCORE partial buffer of an (N)-column GEMM over chunk_rows rows
+ * (a positive multiple of 16): ceil(N/16) * chunk_rows * 4.  Host arithmetic
+ * only; nonzero on bad arguments. */
+int hpa_score_workspace(int N, int chunk_rows, size_t* floats);
+/* combines the SCORE partials of rows 0..M-1 (part[ntiles][Mp][4]; rows up to
+ * Mp are read, as the SCORE GEMM writes them), one workgroup per four rows, in
+ * a fixed order (a launch repeats bit for bit): the row maximum Mx over the
+ * tiles, S = sum_t s_t * exp(m_t - Mx) in double (each thread its tiles in
+ * increasing order under a running maximum, then a fixed tree), and
+ *   lse[m]         = Mx + log S
+ *   logprob[m]     = target logit - lse, 0.0f where the row has no target
+ *   top_id[m]      = the lowest column of the row's maximum
+ *   top_logprob[m] = Mx - lse
+ * Any of the four outputs may be NULL. */
+int hpa_score_final(const float* part, int ntiles, int Mp, int M, float* logprob, float* lse, int* top_id,
+                    float* top_logprob);
+/* logprob[b] = logits[b][ids[b]] - logsumexp(logits[b]) for logits [B][V]
+ * row-major (the raw distribution: temperature 1, no filter), one workgroup
+ * per row, sums in double in a fixed order.  active as hpa_argmax_final: rows
+ * with active[b] <= 0 are left untouched.  An id outside [0, V) gives 0. */
+int hpa_logprob_rows(const float* logits, int B, int V, const int* ids, const int* active, float* logprob);
 /* multinomial draw per row from softmax(logits) with the reference's
  * generator and arithmetic order (softmax_forward :259-286, sample_mult
  * :837-848, random_f32 :826-835), one xorshift state per row advanced on the

@@ -186,6 +186,33 @@ int  gpt2_decode_prefill(GPT2* model, const int* tokens, int T, int* next_tokens
  * the same call.  Sequences with lens[b] = 0 are untouched (position, next
  * id, sampler state).  next_tokens[b] is each sequence's next id. */
 int  gpt2_decode_prefill_ragged(GPT2* model, const int* tokens, const int* lens, int* next_tokens);
+/* prompt scoring: everything gpt2_decode_prefill_ragged does (K/V appended,
+ * positions advanced, the last row's logits and pick, lens[b] = 0 sequences
+ * untouched) and, for every packed row r (host arrays of sum(lens) entries,
+ * packed like tokens):
+ *   logprobs[r] = log softmax(logits_r)[targets[r]], 0 where targets[r] == -1
+ *   top_ids[r]  = row r's greedy id (lowest index on ties); nullable
+ * The logits of the rows never reach memory: the rows go through a SCORE GEMM
+ * (HPA_FEPI_SCORE, a log-softmax epilogue) in chunks of
+ * gpt2_decode_set_score_chunk rows, whose partial workspace (allocated on
+ * first use, freed with the engine) is the only buffer that grows with the
+ * vocabulary.  A target outside [-1, vocab_size) returns nonzero with a
+ * message and changes nothing. */
+int  gpt2_decode_score(GPT2* model, const int* tokens, const int* lens, const int* targets, float* logprobs,
+                       int* top_ids, int* next_tokens);
+/* rows per SCORE GEMM: 0 = the default (1024: 50 MiB of partials at
+ * V = 50257), else a positive multiple of 16 (anything else: nonzero) */
+int  gpt2_decode_set_score_chunk(GPT2* model, int rows);
+/* enable != 0: every pick (decode step, prefill, ragged prefill, score) is
+ * followed by one hpa_logprob_rows launch: the log-probability of the chosen
+ * id under the raw model distribution (temperature 1, no filter, in every
+ * sampling mode) into a device [B] array; sequences a ragged call leaves
+ * untouched keep their value.  Default off: the step's launches are then
+ * exactly those without it.  Toggling drops a captured graph. */
+int  gpt2_decode_set_logprobs(GPT2* model, int enable);
+/* host_out [B] <- those log-probabilities (waits for the queued work);
+ * host_out NULL: only the status.  Nonzero unless gpt2_decode_set_logprobs is on. */
+int  gpt2_decode_logprobs(GPT2* model, float* host_out);
 /* retire sequence seq: its pages go back to the pool (block_manager.c:78-90),
  * its position restarts at 0, so the slot can admit a new prompt.  The slot's
  * sampler state and sampling settings (gpt2_decode_set_sampling_params) stay

@@ -617,6 +617,7 @@ int launch16(FG p, int epi) {
         case HPA_FEPI_RESID: gemm16_kernel<NW, HPA_FEPI_RESID, MT, NTW><<<grid, block, 0, hpa_stream()>>>(p); break;
         case HPA_FEPI_GELU: gemm16_kernel<NW, HPA_FEPI_GELU, MT, NTW><<<grid, block, 0, hpa_stream()>>>(p); break;
         case HPA_FEPI_LOGITS: gemm16_kernel<NW, HPA_FEPI_LOGITS, MT, NTW><<<grid, block, 0, hpa_stream()>>>(p); break;
+        case HPA_FEPI_SCORE: gemm16_kernel<NW, HPA_FEPI_SCORE, MT, NTW><<<grid, block, 0, hpa_stream()>>>(p); break;
         default: return hpa_fail(__FILE__, __LINE__, "gemm_fused: unknown epilogue");
     }
     HPA_LAUNCH_CHECK();
@@ -821,6 +822,11 @@ int hpa_gemm_fused(const HpaFusedGemm* g) {
 
 static int gemm_fused_launch(const HpaFusedGemm* g, FG& p) {
     int nw, mt, ntw;
+    // SCORE lives in the looped fp32 kernel and the two bf16-weight kernels only
+    const bool score = g->epilogue == HPA_FEPI_SCORE;
+    HPA_REQUIRE(!score || g->variant == 0 || g->variant == 1 || (g->variant == 5 && g->w_dtype == HPA_BF16),
+                "gemm_fused SCORE: variant 0 or 1 (looped), or 5 on bf16 weights; not one-shot (2), ring (3), "
+                "activation-resident (4) or stream-K (6)");
     if (g->w_dtype == HPA_BF16) {  // bf16 weights: hpa_gemm_bf16.hip
         HPA_REQUIRE(g->K % 32 == 0 && !g->ln_fold_c1 &&
                         (g->variant == 0 || g->variant == 4 || g->variant == 5 || g->variant == 1),
@@ -867,7 +873,7 @@ static int gemm_fused_launch(const HpaFusedGemm* g, FG& p) {
         return launch_sk(p, g->epilogue);  // else the looped kernel below
     HPA_REQUIRE(g->col_tiles == 0 || g->col_tiles == 1 || g->col_tiles == 2 || g->col_tiles == 4,
                 "gemm_fused: col_tiles must be 1, 2 or 4");
-    if (g->variant == 2 || (g->variant == 0 && mt == 1 && p.ntn < 1024 && g->col_tiles <= 1)) {
+    if (g->variant == 2 || (g->variant == 0 && !score && mt == 1 && p.ntn < 1024 && g->col_tiles <= 1)) {
         const int rc = launch_os(p, g->epilogue, nw);
         if (rc >= 0) return rc;
         HPA_REQUIRE(g->variant == 0, "gemm_fused: one-shot needs (waves, K/16) in {(4,48), (8,48), (16,48), (8,192), (16,192), (10,100)}");

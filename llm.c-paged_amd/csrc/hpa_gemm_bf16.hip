@@ -295,6 +295,7 @@ static int launch_ares_t(FG p, int epi, int rounds) {
         case HPA_FEPI_RESID: gemm_b16_ares_kernel<NW, HPA_FEPI_RESID, MT, KC, U><<<grid, block, 0, hpa_stream()>>>(p, cpw); break;
         case HPA_FEPI_GELU: gemm_b16_ares_kernel<NW, HPA_FEPI_GELU, MT, KC, U><<<grid, block, 0, hpa_stream()>>>(p, cpw); break;
         case HPA_FEPI_LOGITS: gemm_b16_ares_kernel<NW, HPA_FEPI_LOGITS, MT, KC, U><<<grid, block, 0, hpa_stream()>>>(p, cpw); break;
+        case HPA_FEPI_SCORE: gemm_b16_ares_kernel<NW, HPA_FEPI_SCORE, MT, KC, U><<<grid, block, 0, hpa_stream()>>>(p, cpw); break;
         default: return hpa_fail(__FILE__, __LINE__, "gemm_fused bf16: unknown epilogue");
     }
     HPA_LAUNCH_CHECK();
@@ -335,6 +336,7 @@ static int launch_b16_t(FG p, int epi) {
         case HPA_FEPI_RESID: gemm_b16_kernel<NW, HPA_FEPI_RESID, MT, NTW><<<grid, block, 0, hpa_stream()>>>(p); break;
         case HPA_FEPI_GELU: gemm_b16_kernel<NW, HPA_FEPI_GELU, MT, NTW><<<grid, block, 0, hpa_stream()>>>(p); break;
         case HPA_FEPI_LOGITS: gemm_b16_kernel<NW, HPA_FEPI_LOGITS, MT, NTW><<<grid, block, 0, hpa_stream()>>>(p); break;
+        case HPA_FEPI_SCORE: gemm_b16_kernel<NW, HPA_FEPI_SCORE, MT, NTW><<<grid, block, 0, hpa_stream()>>>(p); break;
         default: return hpa_fail(__FILE__, __LINE__, "gemm_fused bf16: unknown epilogue");
     }
     HPA_LAUNCH_CHECK();

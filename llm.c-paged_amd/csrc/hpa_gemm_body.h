@@ -43,6 +43,7 @@ struct FG {
     int* pick_tokens;
     int* pick_pos;
     int* pick_count;
+    const int* score_tgt;  // SCORE: target column per GEMM row (-1 / NULL: none); its partials go to part_out
 };
 
 // XCD-aware workgroup order (MI355X_MICROARCH.md "Workgroup dispatch":
@@ -99,6 +100,8 @@ __device__ __forceinline__ void row_sums_publish(float s1, float s2, float* wsum
 // Thread t owns e = t + i*NT.  Accumulator acc[j*MT + r] holds (tile j, block r).
 template <int NW, int EPI, int MT, int NTW = 1>
 struct Epi {
+    // LOGITS and SCORE: the bare product (no bias, no folded LN)
+    static constexpr bool BARE = EPI == HPA_FEPI_LOGITS || EPI == HPA_FEPI_SCORE;
     static constexpr int NT = NW * 64;
     static constexpr int R = MT * 16;
     static constexpr int TE = MT * 256;                    // elements per column tile
@@ -125,9 +128,9 @@ struct Epi {
             int j, lrow, lcol, row, col;
             where(e, nt0, row0, j, lrow, lcol, row, col);
             const bool in = e < NTW * TE;
-            pre_bias[i] = (EPI != HPA_FEPI_LOGITS && in && p.bias && col < p.N) ? p.bias[col] : 0.f;
+            pre_bias[i] = (!BARE && in && p.bias && col < p.N) ? p.bias[col] : 0.f;
             pre_res[i] = 0.f;
-            pre_c1[i] = (EPI != HPA_FEPI_LOGITS && in && p.fold_c1 && col < p.N) ? p.fold_c1[col] : 0.f;
+            pre_c1[i] = (!BARE && in && p.fold_c1 && col < p.N) ? p.fold_c1[col] : 0.f;
             if (EPI == HPA_FEPI_RESID && in && row < p.M && col < p.N)
                 pre_res[i] = p.res_in[hpa::frag_index(row, col, p.N)];
         }
@@ -177,7 +180,7 @@ struct Epi {
                 int j, lrow, lcol, row, col;
                 where(e, nt0, row0, j, lrow, lcol, row, col);
                 const bool live = row < p.M && col < p.N;
-                if (EPI != HPA_FEPI_LOGITS && p.fold_c1) {  // sum_k LN(x)_k W_nk = rstd*(sum_k x_k W'_nk - mean*c1_n)
+                if (!BARE && p.fold_c1) {  // sum_k LN(x)_k W_nk = rstd*(sum_k x_k W'_nk - mean*c1_n)
                     float S1 = wsum[2 * lrow], S2 = wsum[2 * lrow + 1];
 #pragma unroll
                     for (int ww = 1; ww < NW; ++ww) {
@@ -215,9 +218,61 @@ struct Epi {
                     val = live ? pre_res[i] + val : 0.f;  // residual_forward(out, res, proj)
                     if (row < p.Mp && col < p.N) p.out[hpa::frag_index(row, col, p.N)] = val;
                     tile[(j * R + lrow) * 17 + lcol] = val;
+                } else if (EPI == HPA_FEPI_SCORE) {  // the logits stay in LDS: only their row partials leave
+                    tile[(j * R + lrow) * 17 + lcol] = live ? val : -INFINITY;
                 } else {  // LOGITS (row_seq: the output row of each GEMM row)
                     if (live) p.out[(size_t)(p.row_seq ? p.row_seq[row] : row) * p.N + col] = val;
                     tile[(j * R + lrow) * 17 + lcol] = live ? val : -INFINITY;
+                }
+            }
+        }
+        if (EPI == HPA_FEPI_SCORE) {
+            // the log-softmax partial of every (column tile, row) in LDS: (max m, sum of
+            // exp(v - m), the target's logit or -inf, first-max column).  Four adjacent
+            // lanes per (tile, row), four columns each (NTW * R * 4 and NT are multiples of
+            // 4: a quad is whole): quad maximum (lowest column wins, as LOGITS), then each
+            // lane's four terms added in column order and the lanes' sums as
+            // (q0 + q1) + (q2 + q3).  __expf (v_exp_f32 of the product with log2 e: 1 ulp,
+            // and the product's rounding moves a term e^d by |d| e^d 2^-24 <= 2.2e-8 of the
+            // maximum's term): the full-range expf cost four times the LOGITS epilogue here.
+            __syncthreads();
+            for (int t4 = threadIdx.x; t4 < NTW * R * 4; t4 += NT) {
+                const int t = t4 >> 2, q = t4 & 3;
+                const int j = t / R, lr = t - j * R;
+                const int row = row0 + lr, nt = nt0 + j;
+                const float* tr = tile + t * 17;
+                float bv = tr[4 * q];
+                int bi = 4 * q;
+#pragma unroll
+                for (int c = 1; c < 4; ++c)
+                    if (tr[4 * q + c] > bv) {
+                        bv = tr[4 * q + c];
+                        bi = 4 * q + c;
+                    }
+#pragma unroll
+                for (int o = 1; o <= 2; o <<= 1) {
+                    const float v2 = __shfl_xor(bv, o, 64);
+                    const int i2 = __shfl_xor(bi, o, 64);
+                    if (v2 > bv || (v2 == bv && i2 < bi)) {
+                        bv = v2;
+                        bi = i2;
+                    }
+                }
+                float s = 0.f;
+                if (bv != -INFINITY) {  // an all-masked tile (row >= M) would sum exp(-inf - -inf)
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) s += __expf(tr[4 * q + c] - bv);  // masked columns: exp(-inf) = 0
+                }
+                s += __shfl_xor(s, 1, 64);
+                s += __shfl_xor(s, 2, 64);
+                if (q == 0 && row < p.Mp && nt < p.ntn) {
+                    float tl = -INFINITY;
+                    if (p.score_tgt && row < p.M) {
+                        const int tc = p.score_tgt[row] - nt * 16;
+                        if (tc >= 0 && tc < 16) tl = tr[tc];
+                    }
+                    reinterpret_cast<float4*>(p.part_out)[(size_t)nt * p.Mp + row] =
+                        make_float4(bv, s, tl, __int_as_float(nt * 16 + bi));
                 }
             }
         }
@@ -635,7 +690,7 @@ int launch_sk(const FG& p, int epi);
 bool sk_eligible(int Mp, int ntn, int K16);
 
 static inline int fused_prepare(const HpaFusedGemm* g, FG* p) {
-    HPA_REQUIRE(g && g->x && g->w && g->out, "gemm_fused: null operand");
+    HPA_REQUIRE(g && g->x && g->w && (g->out || g->epilogue == HPA_FEPI_SCORE), "gemm_fused: null operand");
     HPA_REQUIRE(g->M > 0 && g->N > 0 && g->K > 0 && g->K % 16 == 0, "gemm_fused: K % 16 != 0");
     HPA_REQUIRE(!g->ln_stats || (g->ln_w && g->ln_b && g->ln_ntiles > 0), "gemm_fused: LN params");
     HPA_REQUIRE(!g->ln_stats || g->K <= HPA_FUSED_LN_KMAX, "gemm_fused: LN over K > 2048");
@@ -673,7 +728,9 @@ static inline int fused_prepare(const HpaFusedGemm* g, FG* p) {
     p->pick_tokens = g->pick_tokens;
     p->pick_pos = g->pick_pos;
     p->pick_count = g->pick_count;
-    HPA_REQUIRE(!g->ln_fold_c1 || g->epilogue != HPA_FEPI_LOGITS, "gemm_fused: ln_fold_c1 with LOGITS");
+    p->score_tgt = nullptr;
+    HPA_REQUIRE(!g->ln_fold_c1 || (g->epilogue != HPA_FEPI_LOGITS && g->epilogue != HPA_FEPI_SCORE),
+                "gemm_fused: ln_fold_c1 with LOGITS / SCORE");
     if (g->epilogue == HPA_FEPI_QKV) {
         const HpaKVPool* pool = g->pool;
         HPA_REQUIRE(pool && pool->base && pool->head_size == 64 &&
@@ -692,6 +749,13 @@ static inline int fused_prepare(const HpaFusedGemm* g, FG* p) {
     }
     if (g->epilogue == HPA_FEPI_RESID) HPA_REQUIRE(g->res_in, "gemm_fused RESID: res_in");
     if (g->epilogue == HPA_FEPI_LOGITS) HPA_REQUIRE(g->part_out, "gemm_fused LOGITS: part_out");
+    if (g->epilogue == HPA_FEPI_SCORE) {
+        HPA_REQUIRE(g->score_part && ((size_t)g->score_part & 15) == 0 && !g->bias,
+                    "gemm_fused SCORE: score_part (16-byte aligned), no bias");
+        p->out = nullptr;
+        p->part_out = g->score_part;
+        p->score_tgt = g->score_target;
+    }
     p->gx = p->gy = 0;
     return 0;
 }

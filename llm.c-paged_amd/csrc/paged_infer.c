@@ -711,7 +711,18 @@ struct GPT2Decode {
     /* gpt2_decode_step_traced: the residual stream entering every layer and
      * the final one, row-major [L+1][B][C], written during that one step */
     float* trace_x;
+    /* scoring (gpt2_decode_score): rows per SCORE GEMM (0: DEC_SCORE_CHUNK) and the
+     * workspace of one chunk of sc_cap rows, allocated on first use: the chunk's
+     * rows gathered out of the prefill activations (frag [sc_cap][C] and their LNf
+     * statistics), row and target tables, the SCORE partials, the results */
+    int sc_chunk, sc_cap;
+    float *sc_x, *sc_st, *sc_part, *sc_lp;
+    int *sc_rows, *sc_tgt, *sc_top;
+    /* gpt2_decode_set_logprobs: the chosen ids' log-probabilities [B] (NULL until first enabled) */
+    int logprobs;
+    float* d_lp;
 };
+#define DEC_SCORE_CHUNK 1024 /* partials at V = 50257: 3142 tiles x 1024 rows x 16 B = 49.1 MiB */
 
 /* the manager's page index -> pool slot: a fixed pseudo-random permutation,
  * so that whatever order pages are allocated in (first-fit hands each
@@ -760,6 +771,14 @@ static void dec_prefill_free(GPT2Decode* d) {
     d->pf_cap = 0;
 }
 
+static void dec_score_free(GPT2Decode* d) {
+    hpa_free(d->sc_x); hpa_free(d->sc_st); hpa_free(d->sc_part); hpa_free(d->sc_lp);
+    hpa_free(d->sc_rows); hpa_free(d->sc_tgt); hpa_free(d->sc_top);
+    d->sc_x = d->sc_st = d->sc_part = d->sc_lp = NULL;
+    d->sc_rows = d->sc_tgt = d->sc_top = NULL;
+    d->sc_cap = 0;
+}
+
 static void dec_shard_free(GPT2Decode* d) {
     DecShard* s = d->shard;
     if (!s) return;
@@ -800,6 +819,8 @@ static void dec_free(GPT2Decode* d) {
     }
     dec_shard_free(d);
     dec_prefill_free(d);
+    dec_score_free(d);
+    hpa_free(d->d_lp);
     for (int k = 0; k < 2; k++) {
         hpa_event_destroy(d->prof_ev[k]);
         hpa_event_destroy(d->ev_tok[k]);
@@ -1665,7 +1686,7 @@ static int dec_gemm(GPT2* model, int l, int which) {
 
 /* greedy or sampled next token; active (nullable): rows with active[b] <= 0
  * are left untouched */
-static int dec_pick(GPT2* model, const int* active) {
+static int dec_pick_ids(GPT2* model, const int* active) {
     GPT2Decode* d = model->decode;
     const int V = model->config.vocab_size;
     if (d->sample == 2)
@@ -1678,6 +1699,17 @@ static int dec_pick(GPT2* model, const int* active) {
     const int npart = hpa_logits_partials(&g); /* per-tile or per-workgroup partials */
     if (npart <= 0) return 1;
     return hpa_argmax_final(d->part, npart, d->Mp, d->B, d->d_next, d->d_tokens, d->d_pos, active);
+}
+
+/* the pick and, with gpt2_decode_set_logprobs on, the chosen ids'
+ * log-probabilities (the pick has advanced pos and written d_next; the
+ * log-probability kernel reads d_logits and d_next only) */
+static int dec_pick(GPT2* model, const int* active) {
+    GPT2Decode* d = model->decode;
+    int rc = dec_pick_ids(model, active);
+    if (d->logprobs && !rc)
+        rc = hpa_logprob_rows(d->d_logits, d->B, model->config.vocab_size, d->d_next, active, d->d_lp);
+    return rc;
 }
 
 /* one decode-attention launch: the (sequence, head, context range) grid,
@@ -1842,6 +1874,44 @@ int gpt2_decode_set_sampling(GPT2* model, int enable, unsigned long long seed) {
         d->graph = NULL;
         if (dec_rezero(d)) return 1;
     }
+    return 0;
+}
+
+/* the chosen ids' log-probabilities after every pick (dec_pick): one more
+ * launch in the step, so a captured graph is dropped like set_sampling's */
+int gpt2_decode_set_logprobs(GPT2* model, int enable) {
+    GPT2Decode* d = model->decode;
+    if (!d) return 1;
+    if (hpa_synchronize()) return 1;
+    if (enable && !d->d_lp) {
+        d->d_lp = (float*)hpa_malloc(d->B * sizeof(float));
+        if (!d->d_lp || hpa_memset_async(d->d_lp, 0, d->B * sizeof(float))) return 1;
+    }
+    if (d->logprobs == (enable != 0)) return 0;
+    d->logprobs = enable != 0;
+    if (d->graph) { /* recapture with / without the launch */
+        hpa_graph_destroy(d->graph);
+        d->graph = NULL;
+        if (dec_rezero(d)) return 1;
+    }
+    return 0;
+}
+
+int gpt2_decode_logprobs(GPT2* model, float* host_out) {
+    GPT2Decode* d = model->decode;
+    if (!d || !d->logprobs || !d->d_lp) return 1;
+    if (!host_out) return 0;
+    return hpa_synchronize() || hpa_memcpy(host_out, d->d_lp, d->B * sizeof(float));
+}
+
+int gpt2_decode_set_score_chunk(GPT2* model, int rows) {
+    GPT2Decode* d = model->decode;
+    if (!d) return 1;
+    if (rows < 0 || rows % 16) {
+        fprintf(stderr, "[paged_infer] set_score_chunk: %d is not 0 or a positive multiple of 16\n", rows);
+        return 1;
+    }
+    d->sc_chunk = rows;
     return 0;
 }
 
@@ -2077,8 +2147,84 @@ static int prefill_all_logits(GPT2* model, int R, float* rows_out, const int* ou
  * lens[b] > 0 through the logits and the greedy / sampled pick.  Sequences
  * with lens[b] = 0 are untouched (position, next token, sampler state).
  * all_logits (device [R][V], nullable): every row's logits too. */
+/* what gpt2_decode_score adds to a prefill: host arrays packed like tokens */
+typedef struct {
+    const int* targets;
+    float* logprobs;
+    int* top_ids; /* nullable */
+} DecScore;
+
+/* the workspace of one SCORE chunk of `rows` (a multiple of 16) */
+static int dec_score_reserve(GPT2* model, int rows) {
+    GPT2Decode* d = model->decode;
+    if (rows <= d->sc_cap) return 0;
+    dec_score_free(d);
+    const size_t C = model->config.channels, ct = C / 16;
+    size_t pf = 0;
+    if (hpa_score_workspace(model->config.vocab_size, rows, &pf)) return 1;
+    d->sc_x = (float*)hpa_malloc((size_t)rows * C * 4);
+    d->sc_st = (float*)hpa_malloc(ct * rows * 2 * 4);
+    d->sc_part = (float*)hpa_malloc(pf * sizeof(float));
+    d->sc_lp = (float*)hpa_malloc(rows * sizeof(float));
+    d->sc_rows = (int*)hpa_malloc(rows * sizeof(int));
+    d->sc_tgt = (int*)hpa_malloc(rows * sizeof(int));
+    d->sc_top = (int*)hpa_malloc(rows * sizeof(int));
+    if (!d->sc_x || !d->sc_st || !d->sc_part || !d->sc_lp || !d->sc_rows || !d->sc_tgt || !d->sc_top ||
+        hpa_memset_async(d->sc_x, 0, (size_t)rows * C * 4)) { /* rows past a chunk's end: finite, masked */
+        dec_score_free(d);
+        return 1;
+    }
+    d->sc_cap = rows;
+    return 0;
+}
+
+/* every prefill row's log-probability and greedy id: LNf(res) . wte^T over the
+ * R packed rows of pf_res in chunks, each chunk's rows gathered (with their
+ * LNf statistics) into the chunk workspace, one SCORE GEMM (the log-softmax
+ * epilogue: no logits stored) and one hpa_score_final */
+static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
+    GPT2Decode* d = model->decode;
+    const GPT2Config c = model->config;
+    const int C = c.channels, V = c.vocab_size;
+    const int Rp = (R + 15) / 16 * 16;
+    int chunk = d->sc_chunk ? d->sc_chunk : DEC_SCORE_CHUNK;
+    if (chunk > Rp) chunk = Rp;
+    if (dec_score_reserve(model, chunk)) return 1;
+    int* hrows = (int*)malloc((size_t)chunk * sizeof(int));
+    if (!hrows) return 1;
+    int rc = 0;
+    for (int r0 = 0; r0 < R && !rc; r0 += chunk) {
+        const int n = R - r0 < chunk ? R - r0 : chunk, np = (n + 15) / 16 * 16;
+        for (int i = 0; i < n; i++) hrows[i] = r0 + i;
+        rc |= hpa_memcpy(d->sc_rows, hrows, n * sizeof(int));
+        rc |= hpa_memcpy(d->sc_tgt, sc->targets + r0, n * sizeof(int));
+        rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->sc_rows, n, d->sc_x, d->sc_st, np, C);
+        HpaFusedGemm g;
+        memset(&g, 0, sizeof(g));
+        g.M = n;
+        g.w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
+        g.epilogue = HPA_FEPI_SCORE;
+        g.x = d->sc_x;
+        g.K = C;
+        g.ln_stats = d->sc_st;
+        g.ln_ntiles = C / 16;
+        g.ln_w = model->params.lnfw;
+        g.ln_b = model->params.lnfb;
+        g.w = wpack_at(d, d->wpack_off[4]);
+        g.N = V;
+        g.score_target = d->sc_tgt;
+        g.score_part = d->sc_part;
+        rc |= hpa_gemm_fused(&g);
+        rc |= hpa_score_final(d->sc_part, (V + 15) / 16, np, n, d->sc_lp, NULL, d->sc_top, NULL);
+        rc |= hpa_memcpy(sc->logprobs + r0, d->sc_lp, n * sizeof(float)); /* synchronous: the tables are free again */
+        if (sc->top_ids) rc |= hpa_memcpy(sc->top_ids + r0, d->sc_top, n * sizeof(int));
+    }
+    free(hrows);
+    return rc;
+}
+
 static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int* next_tokens, float* all_logits,
-                            const int* all_rows) {
+                            const int* all_rows, const DecScore* score) {
     GPT2Decode* d = model->decode;
     if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
     const GPT2Config c = model->config;
@@ -2099,6 +2245,12 @@ static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int
     for (long i = 0; i < R; i++)
         if (tokens[i] < 0 || tokens[i] >= c.vocab_size) {
             fprintf(stderr, "[paged_infer] token out of range\n"); /* :591-596 */
+            return 1;
+        }
+    for (long i = 0; score && i < R; i++)
+        if (score->targets[i] < -1 || score->targets[i] >= c.vocab_size) {
+            fprintf(stderr, "[paged_infer] score: target %d of row %ld is outside [-1, %d)\n", score->targets[i], i,
+                    c.vocab_size);
             return 1;
         }
     for (int b = 0; b < B; b++)
@@ -2139,6 +2291,7 @@ static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int
         rc |= prefill_gemm(model, l, G_FCPROJ, (int)R);
     }
     if (all_logits && !rc) rc |= prefill_all_logits(model, (int)R, all_logits, all_rows);
+    if (score && !rc) rc |= dec_score_rows(model, (int)R, score);
     /* last row of every active sequence -> the decode rows, logits, pick; the
      * pick advances pos by one: set pos = start + len - 1 first */
     for (int b = 0; b < B; b++) hst[b] = d->h_pos[b] + (lens[b] > 0 ? lens[b] - 1 : 0);
@@ -2162,7 +2315,7 @@ int gpt2_decode_prefill(GPT2* model, const int* tokens, int T, int* next_tokens)
     int* lens = (int*)malloc(d->B * sizeof(int));
     if (!lens) return 1;
     for (int b = 0; b < d->B; b++) lens[b] = T;
-    const int rc = dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL);
+    const int rc = dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, NULL);
     free(lens);
     return rc;
 }
@@ -2170,7 +2323,15 @@ int gpt2_decode_prefill(GPT2* model, const int* tokens, int T, int* next_tokens)
 int gpt2_decode_prefill_ragged(GPT2* model, const int* tokens, const int* lens, int* next_tokens) {
     if (!model->decode) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
     if (!lens || !tokens) return 1;
-    return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL);
+    return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, NULL);
+}
+
+int gpt2_decode_score(GPT2* model, const int* tokens, const int* lens, const int* targets, float* logprobs,
+                      int* top_ids, int* next_tokens) {
+    if (!model->decode) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (!lens || !tokens || !targets || !logprobs) return 1;
+    const DecScore sc = {targets, logprobs, top_ids};
+    return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, &sc);
 }
 
 int gpt2_decode_release(GPT2* model, int seq) {
@@ -2888,7 +3049,7 @@ void gpt2_forward(GPT2* model, int* inputs, int* targets, size_t B, size_t T, si
         /* every row's logits straight into its position's row of pos_logits
          * (the GEMM's output row map): no [B][n_new][V] staging copy */
         PI_CHECK(hpa_memcpy(d_map, map, B * (size_t)n_new * sizeof(int)));
-        if (dec_prefill_rows(model, toks, lens, NULL, d->pos_logits, d_map)) PI_FATAL("window prefill failed");
+        if (dec_prefill_rows(model, toks, lens, NULL, d->pos_logits, d_map, NULL)) PI_FATAL("window prefill failed");
         if (gpt2_decode_evicted(model, NULL) > 0) PI_FATAL("gpt2_forward: page pool too small, a sequence was evicted");
         hpa_free(d_map);
         free(map);

@@ -60,10 +60,10 @@ class HpaFusedGemm(ctypes.Structure):
                 ("row_blocks", ctypes.c_int), ("variant", ctypes.c_int), ("col_tiles", ctypes.c_int),
                 ("row_seq", _V), ("ln_fold_c1", _V), ("sk_slab", _V), ("sk_count", _V),
                 ("w_dtype", ctypes.c_int), ("pick_next", _V), ("pick_tokens", _V), ("pick_pos", _V),
-                ("pick_count", _V)]
+                ("pick_count", _V), ("score_target", _V), ("score_part", _V)]
 
 
-HPA_FEPI_QKV, HPA_FEPI_RESID, HPA_FEPI_GELU, HPA_FEPI_LOGITS = 0, 1, 2, 3
+HPA_FEPI_QKV, HPA_FEPI_RESID, HPA_FEPI_GELU, HPA_FEPI_LOGITS, HPA_FEPI_SCORE = 0, 1, 2, 3, 4
 HPA_COMM_SEND, HPA_COMM_RECV, HPA_COMM_COPY = 0, 1, 2
 
 
@@ -249,6 +249,13 @@ def lib():
     _sig(L, "hpa_frag_bf16_elems", ctypes.c_size_t, [i, i])
     _sig(L, "gpt2_decode_prefill", i, [v, _I, i, _I])
     _sig(L, "gpt2_decode_prefill_ragged", i, [v, _I, _I, _I])
+    _sig(L, "gpt2_decode_score", i, [v, _I, _I, _I, _F, _I, _I])
+    _sig(L, "gpt2_decode_set_score_chunk", i, [v, i])
+    _sig(L, "gpt2_decode_set_logprobs", i, [v, i])
+    _sig(L, "gpt2_decode_logprobs", i, [v, _F])
+    _sig(L, "hpa_score_workspace", i, [i, i, ctypes.POINTER(ctypes.c_size_t)])
+    _sig(L, "hpa_score_final", i, [v, i, i, i, v, v, v, v])
+    _sig(L, "hpa_logprob_rows", i, [v, i, i, v, v, v])
     _sig(L, "gpt2_decode_release", i, [v, i])
     _sig(L, "gpt2_decode_set_sampling", i, [v, i, ctypes.c_ulonglong])
     _sig(L, "gpt2_decode_set_sampling_params", i, [v, i, ctypes.c_float, i, ctypes.c_float])
@@ -919,6 +926,49 @@ class Model:
         check(lib().gpt2_decode_prefill_ragged(self.h, flat.ctypes.data_as(_I), lens.ctypes.data_as(_I),
                                                nxt.ctypes.data_as(_I)), "prefill_ragged")
         return nxt
+
+    def score(self, seqs, targets=None):
+        """gpt2_decode_score: prefill_ragged(seqs) that also returns every
+        token's log-probability.  targets: per sequence, the id whose
+        log-probability each position reports (-1: none, 0.0 returned);
+        None shifts: the target of token t is token t + 1 and the last token
+        has none, so len(seq) - 1 values are meaningful.  Returns (logprobs,
+        top_ids, next_ids): per-sequence float32 / int32 arrays of len(seq)
+        (top_ids: each position's greedy id) and the next ids (B,)."""
+        assert len(seqs) == self.B
+        seqs = [np.asarray(t, np.int32).reshape(-1) for t in seqs]
+        if targets is None:
+            targets = [np.concatenate([t[1:], np.full(1, -1, np.int32)]) if len(t) else t for t in seqs]
+        targets = [np.asarray(t, np.int32).reshape(-1) for t in targets]
+        assert len(targets) == self.B and all(len(a) == len(b) for a, b in zip(seqs, targets))
+        lens = np.array([len(t) for t in seqs], np.int32)
+        R = int(lens.sum())
+        flat = np.ascontiguousarray(np.concatenate(seqs) if R else np.zeros(1, np.int32), np.int32)
+        tgt = np.ascontiguousarray(np.concatenate(targets) if R else np.full(1, -1, np.int32), np.int32)
+        lp = np.zeros(max(R, 1), np.float32)
+        top = np.zeros(max(R, 1), np.int32)
+        nxt = np.zeros(self.B, np.int32)
+        check(lib().gpt2_decode_score(self.h, flat.ctypes.data_as(_I), lens.ctypes.data_as(_I), tgt.ctypes.data_as(_I),
+                                      lp.ctypes.data_as(_F), top.ctypes.data_as(_I), nxt.ctypes.data_as(_I)), "score")
+        cuts = np.cumsum(lens)[:-1]
+        return np.split(lp[:R], cuts), np.split(top[:R], cuts), nxt
+
+    def set_score_chunk(self, rows=0):
+        """rows per SCORE GEMM of score(): 0 = the default, else a positive
+        multiple of 16"""
+        check(lib().gpt2_decode_set_score_chunk(self.h, int(rows)), "set_score_chunk")
+
+    def set_logprobs(self, enable=True):
+        """after every pick also compute the chosen id's log-probability
+        (raw model distribution: temperature 1, no filter); see logprobs()"""
+        check(lib().gpt2_decode_set_logprobs(self.h, int(bool(enable))), "set_logprobs")
+
+    def logprobs(self):
+        """(B,) log-probabilities of the ids the last pick chose (sequences a
+        ragged call left untouched keep their value); set_logprobs first"""
+        out = np.zeros(self.B, np.float32)
+        check(lib().gpt2_decode_logprobs(self.h, out.ctypes.data_as(_F)), "logprobs")
+        return out
 
     def release(self, seq):
         """retire sequence seq: pages back to the pool, position 0"""
