@@ -18,6 +18,7 @@
  *   ./decode_main [-c checkpoint.bin] [-k tokenizer.bin] [-t tokens.bin]
  *                 [-b B] [-p prompt_len] [-n new_tokens] [-g] [-o ids.bin] [-q]
  *                 [--temperature X] [--top-k N] [--top-p X] [--perplexity] [--logprobs]
+ *                 [--speculate K]
  *     -g greedy (default: sampling as the reference), -o writes the B x
  *     (prompt + new) token ids as int32, -q prints only the summary line.
  *     --temperature / --top-k / --top-p: any of them selects filtered
@@ -28,6 +29,13 @@
  *     and its exp per sequence and overall.  --logprobs: prints sequence 0's
  *     log-probability beside each generated token (gpt2_decode_set_logprobs:
  *     the raw model distribution, whatever the sampling settings).
+ *     --speculate K (1..7, with -g only): speculative greedy decoding.  Every
+ *     pass drafts up to K tokens per sequence with the n-gram drafter
+ *     (gpt2_ngram_draft over prompt + output, n-grams of 3 down to 1 tokens)
+ *     and verifies them in one gpt2_decode_verify pass, which emits the
+ *     accepted drafts and one token of the model's own.  The ids are those of
+ *     plain greedy decoding; one more line reports passes, tokens and the mean
+ *     number of accepted drafts per sequence and pass.  Not with --logprobs.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -35,6 +43,7 @@
 #include <time.h>
 
 #include "block_manager.h"
+#include "hip_paged_attn.h"
 #include "paged_infer.h"
 
 static double now_s(void) {
@@ -62,7 +71,7 @@ static void print_token(Tokenizer* tk, int id) {
 int main(int argc, char** argv) {
     const char *ckpt = NULL, *tok_path = NULL, *tokens_path = NULL, *ids_out = NULL;
     int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
-    int perplexity = 0, logprobs = 0;
+    int perplexity = 0, logprobs = 0, speculate = 0;
     float temperature = 1.0f, top_p = 1.0f;
     for (int i = 1; i < argc; i++) {
         const char* a = argv[i];
@@ -82,8 +91,20 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--temperature")) { temperature = (float)atof(v); filtered = 1; }
         else if (!strcmp(a, "--top-k")) { top_k = atoi(v); filtered = 1; }
         else if (!strcmp(a, "--top-p")) { top_p = (float)atof(v); filtered = 1; }
+        else if (!strcmp(a, "--speculate")) speculate = atoi(v);
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         i++;
+    }
+    if (speculate) {
+        if (speculate < 1 || speculate > HPA_VERIFY_MAX_ROWS - 1) {
+            fprintf(stderr, "--speculate takes 1..%d drafts\n", HPA_VERIFY_MAX_ROWS - 1);
+            return 2;
+        }
+        if (!greedy || filtered || logprobs) {
+            fprintf(stderr, "--speculate is greedy only: give -g, and none of --temperature, --top-k, --top-p, "
+                            "--logprobs\n");
+            return 2;
+        }
     }
     GPT2 model;
     if (ckpt) {
@@ -174,7 +195,46 @@ int main(int argc, char** argv) {
         if (new_tokens > 0) gen[(size_t)b * total + prompt_len] = next[b];
     }
     if (!quiet) printf("\ngenerating:\n---\n");
-    for (int t = 1; t < new_tokens; t++) {
+    long spec_passes = 0, spec_live = 0, spec_accepted = 0, spec_tokens = 0;
+    if (speculate && new_tokens > 0) {
+        /* count[b] tokens of sequence b are out (the prefill's pick is the first and is b's pending id) */
+        int* count = (int*)malloc(B * sizeof(int));
+        int* n_draft = (int*)malloc(B * sizeof(int));
+        int* n_acc = (int*)malloc(B * sizeof(int));
+        int* drafts = (int*)malloc((size_t)B * HPA_VERIFY_MAX_ROWS * sizeof(int));
+        int* out = (int*)malloc((size_t)B * HPA_VERIFY_MAX_ROWS * sizeof(int));
+        if (!count || !n_draft || !n_acc || !drafts || !out) return 1;
+        for (int b = 0; b < B; b++) count[b] = 1;
+        if (!quiet) print_token(&tk, next[0]);
+        for (;;) {
+            int live = 0, nd = 0;
+            for (int b = 0; b < B; b++) {
+                const int left = new_tokens - count[b]; /* a pass emits up to n_draft + 1 tokens */
+                n_draft[b] = -1;
+                if (left <= 0) continue;
+                const int k = speculate < left - 1 ? speculate : left - 1;
+                n_draft[b] = gpt2_ngram_draft(gen + (size_t)b * total, prompt_len + count[b], 3, 1, k, drafts + nd);
+                nd += n_draft[b];
+                live++;
+            }
+            if (!live) break;
+            if (gpt2_decode_verify(&model, drafts, n_draft, n_acc, out, NULL)) return 1;
+            spec_passes++;
+            spec_live += live;
+            for (int b = 0; b < B; b++) {
+                if (n_draft[b] < 0) continue;
+                spec_accepted += n_acc[b];
+                for (int i = 0; i <= n_acc[b]; i++) {
+                    const int id = out[b * HPA_VERIFY_MAX_ROWS + i];
+                    gen[(size_t)b * total + prompt_len + count[b]++] = id;
+                    if (b == 0 && !quiet) print_token(&tk, id);
+                }
+                spec_tokens += n_acc[b] + 1;
+            }
+        }
+        free(count); free(n_draft); free(n_acc); free(drafts); free(out);
+    }
+    for (int t = 1; t < new_tokens && !speculate; t++) {
         if (!quiet) print_token(&tk, next[0]);
         if (!quiet && logprobs) printf("[%.4f] ", lp[0]);
         /* the previous ids stay on the device and feed this step */
@@ -182,13 +242,16 @@ int main(int argc, char** argv) {
         if (logprobs && gpt2_decode_logprobs(&model, lp)) return 1;
         for (int b = 0; b < B; b++) gen[(size_t)b * total + prompt_len + t] = next[b];
     }
-    if (!quiet && new_tokens > 0) print_token(&tk, next[0]);
+    if (!quiet && new_tokens > 0 && !speculate) print_token(&tk, next[0]);
     if (!quiet && logprobs && new_tokens > 0) printf("[%.4f] ", lp[0]);
     double t2 = now_s();
     if (!quiet) printf("\n---\nFinished!\n");
     printf("prefill %d x %d tokens in %.3f ms; generated %d tokens x %d sequences (%s) in %.3f ms: "
            "%.1f tokens/s\n", B, prompt_len, 1e3 * (t1 - t0), new_tokens, B, greedy ? "greedy" : "sampled",
            1e3 * (t2 - t0), new_tokens > 1 ? (double)(new_tokens - 1) * B / (t2 - t1) : 0.0);
+    if (speculate)
+        printf("speculation: %ld passes, %ld tokens emitted, mean accepted %.2f drafts per sequence and pass\n",
+               spec_passes, spec_tokens, spec_live ? (double)spec_accepted / spec_live : 0.0);
     if (ids_out) {
         FILE* f = fopen(ids_out, "wb");
         if (!f || fwrite(gen, sizeof(int), (size_t)B * total, f) != (size_t)B * total) return 1;

@@ -91,6 +91,7 @@ int   hpa_graph_destroy(void* graph_exec);
  * the process: 1, 2, 4, 8 (an override for timing tools); 0 (default): the
  * caller's choice (the engine's hpa_attn_pick_waves, else 4) */
 int   hpa_set_attention_waves(int nw);
+int   hpa_attention_waves(void);        /* the override in force (0: none) */
 int   hpa_device_info(char* name, int name_len, int* num_cus, size_t* total_mem);
 
 /* ---------------- paged KV pool (fast layout) ----------------
@@ -680,6 +681,38 @@ int hpa_paged_attention_prefill(const float* q, const HpaKVPool* pool, int layer
 int hpa_paged_attention_prefill_ragged(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
                                        int bt_stride, const int* start, const int* row0, const int* len, int B,
                                        int T, float* out_frag);
+/* ---------------- speculative decoding (hpa_verify.hip) ----------------
+ * The attention of a verify pass: the ragged contract above (q [rows][C]
+ * row-major, row row0[b] + t at position start[b] + t sees keys 0 ..
+ * start[b] + t, frag output, len[b] == 0 skipped, softmax from the -10000
+ * floor) for 1 <= T = max(len) <= HPA_VERIFY_MAX_ROWS query rows per sequence
+ * over a long context.  The decode kernel's structure: one workgroup per
+ * (sequence, head), 64-token K/V tiles streamed once into registers and used
+ * for every row, queries broadcast from LDS, wave states folded in wave order
+ * (a launch repeats bit for bit); 4 or 8 waves per workgroup as
+ * hpa_attn_pick_waves says, or as hpa_set_attention_waves(4 or 8) names them.
+ * fp32 pools, head size 64, page size 8, 16,
+ * 32 or 64, no context splits; anything else returns nonzero and launches
+ * nothing (bf16 / fp8 pools: hpa_paged_attention_prefill_ragged). */
+#define HPA_VERIFY_MAX_ROWS 8
+int hpa_paged_attention_verify(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
+                               int bt_stride, const int* start, const int* row0, const int* len, int B,
+                               int T, float* out_frag);
+/* row tables of a verify pass (device arrays): row row0[b] of sequence b with
+ * len[b] > 0 is its pending id next[b], rows row0[b] + 1 .. + len[b] - 1 its
+ * drafts drafts[draft0[b] ..]; tok / pos / seq: the row's token, position
+ * start[b] + t and sequence; target: the next row's token (the id the row must
+ * predict for that draft to be accepted), -1 for a sequence's last row */
+int hpa_verify_rows(const int* next, const int* drafts, const int* draft0, const int* start, const int* row0,
+                    const int* len, int B, int* tok, int* pos, int* seq, int* target);
+/* the accept decision from the rows' greedy ids top_id: n_accepted[b] = the
+ * largest a with tok[row0[b] + i] == top_id[row0[b] + i - 1] for 1 <= i <= a;
+ * cont_row[b] = row0[b] + a, the row decoding continues from; pos[b] =
+ * start[b] + a (the pick that follows advances it by one).  len[b] == 0:
+ * n_accepted[b] = cont_row[b] = -1, pos[b] untouched. */
+int hpa_verify_accept(const int* tok, const int* top_id, const int* start, const int* row0, const int* len, int B,
+                      int* n_accepted, int* cont_row, int* pos);
+
 /* rows[i] of a frag-layout [src_Mp][C] matrix and of its LN statistics
  * ([C/16][src_Mp][2]) -> row i of dst / dst_stats (n rows; prefill -> logits);
  * rows[i] < 0 leaves row i of dst as it is */

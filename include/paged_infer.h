@@ -203,6 +203,60 @@ int  gpt2_decode_score(GPT2* model, const int* tokens, const int* lens, const in
 /* rows per SCORE GEMM: 0 = the default (1024: 50 MiB of partials at
  * V = 50257), else a positive multiple of 16 (anything else: nonzero) */
 int  gpt2_decode_set_score_chunk(GPT2* model, int rows);
+/* Speculative greedy decoding: one pass verifies up to HPA_VERIFY_MAX_ROWS - 1
+ * drafted tokens per sequence and emits what the model itself would have
+ * emitted token by token -- the accepted drafts and one token of its own --
+ * while reading each sequence's K/V once.
+ * n_draft[b] in [-1, HPA_VERIFY_MAX_ROWS - 1]: -1 leaves sequence b untouched
+ * (position, next id, logits row, sampler state, log-probability: lens[b] = 0
+ * of the ragged call); 0 is a plain decode step of b through this path.
+ * drafts: the drafted ids packed in sequence order (sum of the positive
+ * n_draft; NULL when there are none).
+ * The pass is the ragged pass over n_draft[b] + 1 rows per sequence: row 0 is
+ * b's pending next id (the device's, as gpt2_decode_step(model, NULL, ..)
+ * would feed it), rows 1.. its drafts; the K/V of every row is appended.  The
+ * rows' greedy ids come from the SCORE GEMM (no dense logits), the accept
+ * decision is taken on the device (hpa_verify_accept): a = the number of
+ * leading drafts equal to the greedy id of the row before them.  Then the
+ * ragged pass's tail from row a: logits GEMM and pick.
+ *   n_accepted[b] = a (-1: untouched)
+ *   out_tokens[b * HPA_VERIFY_MAX_ROWS + i], i <= a: the a accepted drafts,
+ *     then the model's own next token (the pick: b's new pending id)
+ *   draft_logprobs (nullable, same stride): entry i < n_draft[b] =
+ *     log p(draft_{i+1} | pending, draft_1..i) under the raw distribution, for
+ *     every drafted row, accepted or not (conditioned on the drafted prefix)
+ * Afterwards pos[b] += a + 1 and the state is what a + 1 calls of
+ * gpt2_decode_step(model, NULL, ..) would leave for b (gpt2_decode_logits row
+ * b, and with gpt2_decode_set_logprobs on the pending token's
+ * log-probability).  The slots past the new position hold the rejected rows'
+ * K/V: no kernel reads them and later appends overwrite them; pages taken for
+ * rejected rows stay with the sequence, as after gpt2_decode_set_positions.
+ * Eviction and shared pages as in gpt2_decode_prefill_ragged.  Eager and
+ * host-synchronous like the prefill; a captured decode graph stays valid.
+ * Refused (message, nonzero, nothing changed): a sampling mode other than 0
+ * (rejection sampling is not implemented), n_draft out of range, a draft id
+ * outside [0, vocab_size), pos[b] + n_draft[b] + 1 > max_ctx, no engine.
+ * The pending id must be valid: for a fresh slot or a fork of a shorter
+ * prefix it is not, and that is the caller's responsibility, as with
+ * tokens == NULL in gpt2_decode_step. */
+int  gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
+                        float* draft_logprobs);
+/* The attention kernel of a verify pass of at most max_rows rows per sequence,
+ * pure: 1 hpa_paged_attention_verify (the decode kernel's K/V streaming, every
+ * tile used for all rows), 0 hpa_paged_attention_prefill_ragged.  request: 0
+ * auto, 1 the prefill kernel, 2 the verify kernel -- still refused (0) where
+ * it does not apply: bf16 and fp8 pools (their tile loops are not written:
+ * the prefill kernel is correct there, and slower), head size != 64, a page
+ * size other than 8, 16, 32 or 64, more than HPA_VERIFY_MAX_ROWS rows. */
+int  gpt2_decode_verify_plan(int max_rows, int kv_dtype, int page_size, int head_size, int request);
+/* the request gpt2_decode_verify passes to the plan (default 0) */
+int  gpt2_decode_set_verify_attention(GPT2* model, int request);
+/* n-gram (prompt-lookup) drafter, host only (no device, allocation or I/O):
+ * for g from max_ngram down to min_ngram, the most recent earlier occurrence
+ * of the last g tokens of history[0..n) that has at least one token after it;
+ * up to k of the tokens that followed it are copied to draft.  Returns how
+ * many (0: no match, k <= 0, n too short). */
+int  gpt2_ngram_draft(const int* history, int n, int max_ngram, int min_ngram, int k, int* draft);
 /* enable != 0: every pick (decode step, prefill, ragged prefill, score) is
  * followed by one hpa_logprob_rows launch: the log-probability of the chosen
  * id under the raw model distribution (temperature 1, no filter, in every

@@ -721,6 +721,15 @@ struct GPT2Decode {
     /* gpt2_decode_set_logprobs: the chosen ids' log-probabilities [B] (NULL until first enabled) */
     int logprobs;
     float* d_lp;
+    /* speculative decoding (gpt2_decode_verify): the attention request
+     * (gpt2_decode_set_verify_attention) and the pass's device tables, allocated on
+     * first use: vf_int = drafts [B * 7], draft0 [B], accepted [B], then per row
+     * (B * HPA_VERIFY_MAX_ROWS) the SCORE targets and greedy ids; vf_lp the
+     * rows' log-probabilities; h_vf the host staging of the same */
+    int vf_request;
+    int* vf_int;
+    float* vf_lp;
+    int* h_vf;
 };
 #define DEC_SCORE_CHUNK 1024 /* partials at V = 50257: 3142 tiles x 1024 rows x 16 B = 49.1 MiB */
 
@@ -779,6 +788,12 @@ static void dec_score_free(GPT2Decode* d) {
     d->sc_cap = 0;
 }
 
+static void dec_verify_free(GPT2Decode* d) {
+    hpa_free(d->vf_int); hpa_free(d->vf_lp);
+    free(d->h_vf);
+    d->vf_int = NULL; d->vf_lp = NULL; d->h_vf = NULL;
+}
+
 static void dec_shard_free(GPT2Decode* d) {
     DecShard* s = d->shard;
     if (!s) return;
@@ -820,6 +835,7 @@ static void dec_free(GPT2Decode* d) {
     dec_shard_free(d);
     dec_prefill_free(d);
     dec_score_free(d);
+    dec_verify_free(d);
     hpa_free(d->d_lp);
     for (int k = 0; k < 2; k++) {
         hpa_event_destroy(d->prof_ev[k]);
@@ -2152,6 +2168,11 @@ typedef struct {
     const int* targets;
     float* logprobs;
     int* top_ids; /* nullable */
+    /* gpt2_decode_verify: the targets are on the device already and the
+     * results stay there (targets / logprobs above are then NULL) */
+    const int* d_targets;
+    float* d_logprobs;
+    int* d_top_ids;
 } DecScore;
 
 /* the workspace of one SCORE chunk of `rows` (a multiple of 16) */
@@ -2197,7 +2218,7 @@ static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
         const int n = R - r0 < chunk ? R - r0 : chunk, np = (n + 15) / 16 * 16;
         for (int i = 0; i < n; i++) hrows[i] = r0 + i;
         rc |= hpa_memcpy(d->sc_rows, hrows, n * sizeof(int));
-        rc |= hpa_memcpy(d->sc_tgt, sc->targets + r0, n * sizeof(int));
+        rc |= hpa_memcpy(d->sc_tgt, (sc->d_targets ? sc->d_targets : sc->targets) + r0, n * sizeof(int));
         rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->sc_rows, n, d->sc_x, d->sc_st, np, C);
         HpaFusedGemm g;
         memset(&g, 0, sizeof(g));
@@ -2216,10 +2237,37 @@ static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
         g.score_part = d->sc_part;
         rc |= hpa_gemm_fused(&g);
         rc |= hpa_score_final(d->sc_part, (V + 15) / 16, np, n, d->sc_lp, NULL, d->sc_top, NULL);
-        rc |= hpa_memcpy(sc->logprobs + r0, d->sc_lp, n * sizeof(float)); /* synchronous: the tables are free again */
+        /* synchronous copies: the tables are free again */
+        if (sc->logprobs) rc |= hpa_memcpy(sc->logprobs + r0, d->sc_lp, n * sizeof(float));
         if (sc->top_ids) rc |= hpa_memcpy(sc->top_ids + r0, d->sc_top, n * sizeof(int));
+        if (sc->d_logprobs) rc |= hpa_memcpy(sc->d_logprobs + r0, d->sc_lp, n * sizeof(float));
+        if (sc->d_top_ids) rc |= hpa_memcpy(sc->d_top_ids + r0, d->sc_top, n * sizeof(int));
     }
     free(hrows);
+    return rc;
+}
+
+/* the R packed rows of the uploaded row tables (pf_tok, pf_pos, pf_seq;
+ * pf_start: start, row0, len) through the embedding and every layer; T =
+ * max(len).  verify_attn: the few-row kernel (gpt2_decode_verify_plan) in
+ * place of the MFMA prefill kernel */
+static int dec_prefill_layers(GPT2* model, int R, int T, int verify_attn) {
+    GPT2Decode* d = model->decode;
+    const int B = d->B, C = model->config.channels, L = model->config.num_layers;
+    const int* d_row0 = d->pf_start + B;
+    const int* d_len = d->pf_start + 2 * B;
+    const ParameterTensors* w = &model->params;
+    int rc = hpa_embed_frag(d->pf_tok, d->pf_pos, w->wte, w->wpe, d->pf_res, d->pf_st1, R, C);
+    for (int l = 0; l < L && !rc; l++) {
+        rc |= prefill_gemm(model, l, G_QKV, R);
+        rc |= verify_attn ? hpa_paged_attention_verify(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
+                                                       d_len, B, T, d->pf_att)
+                          : hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start,
+                                                               d_row0, d_len, B, T, d->pf_att);
+        rc |= prefill_gemm(model, l, G_ATTPROJ, R);
+        rc |= prefill_gemm(model, l, G_FC, R);
+        rc |= prefill_gemm(model, l, G_FCPROJ, R);
+    }
     return rc;
 }
 
@@ -2228,7 +2276,7 @@ static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int
     GPT2Decode* d = model->decode;
     if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
     const GPT2Config c = model->config;
-    const int B = d->B, C = c.channels, L = c.num_layers;
+    const int B = d->B, C = c.channels;
     long R = 0;
     int T = 0;
     for (int b = 0; b < B; b++) {
@@ -2278,18 +2326,8 @@ static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int
         hpa_memcpy(d->pf_seq, hs, R * sizeof(int)) || hpa_memcpy(d->pf_start, hst, 3 * (size_t)B * sizeof(int)) ||
         hpa_memcpy(d->pf_last, hl, B * sizeof(int)))
         return 1;
-    const int* d_row0 = d->pf_start + B;
     const int* d_len = d->pf_start + 2 * B;
-    const ParameterTensors* w = &model->params;
-    int rc = hpa_embed_frag(d->pf_tok, d->pf_pos, w->wte, w->wpe, d->pf_res, d->pf_st1, (int)R, C);
-    for (int l = 0; l < L && !rc; l++) {
-        rc |= prefill_gemm(model, l, G_QKV, (int)R);
-        rc |= hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
-                                                 d_len, B, T, d->pf_att);
-        rc |= prefill_gemm(model, l, G_ATTPROJ, (int)R);
-        rc |= prefill_gemm(model, l, G_FC, (int)R);
-        rc |= prefill_gemm(model, l, G_FCPROJ, (int)R);
-    }
+    int rc = dec_prefill_layers(model, (int)R, T, 0);
     if (all_logits && !rc) rc |= prefill_all_logits(model, (int)R, all_logits, all_rows);
     if (score && !rc) rc |= dec_score_rows(model, (int)R, score);
     /* last row of every active sequence -> the decode rows, logits, pick; the
@@ -2330,8 +2368,136 @@ int gpt2_decode_score(GPT2* model, const int* tokens, const int* lens, const int
                       int* top_ids, int* next_tokens) {
     if (!model->decode) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
     if (!lens || !tokens || !targets || !logprobs) return 1;
-    const DecScore sc = {targets, logprobs, top_ids};
+    const DecScore sc = {targets, logprobs, top_ids, NULL, NULL, NULL};
     return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, &sc);
+}
+
+/* ---- speculative greedy decoding ----
+ * One ragged pass over the pending id and the drafts of every sequence
+ * (dec_prefill_layers), every row's greedy id from the SCORE GEMM (no dense
+ * logits), the accept decision on the device (hpa_verify_accept), then the
+ * ragged pass's tail from the accepted row: gather -> logits GEMM -> pick. */
+
+/* The attention kernel of a verify pass, pure: 1 the few-row kernel
+ * (hpa_paged_attention_verify), 0 the MFMA prefill kernel.  The few-row
+ * kernel has fp32 tile loops only (bf16 and fp8 pools take the prefill
+ * kernel: correct, slower), head size 64, the decode kernel's page sizes and
+ * at most HPA_VERIFY_MAX_ROWS rows.  Auto keeps it for a shape only where it
+ * beat the prefill kernel by more than the larger of the two spreads; it did
+ * at every shape measured (GPT-2 124M, page 16, ctx 1000, B = 64 and 8, 2 / 4 /
+ * 8 rows: 62 / 73 / 91 us against 211..215 us at B = 64, 16 / 20 / 28 against
+ * 131 us at B = 8; profiles/r11/verify.txt), so no fp32 shape goes to the
+ * prefill kernel */
+int gpt2_decode_verify_plan(int max_rows, int kv_dtype, int page_size, int head_size, int request) {
+    if (request == 1) return 0;
+    if (max_rows < 1 || max_rows > HPA_VERIFY_MAX_ROWS) return 0;
+    if (kv_dtype != HPA_F32 || head_size != 64) return 0;
+    if (page_size != 8 && page_size != 16 && page_size != 32 && page_size != 64) return 0;
+    return 1; /* auto (0) and an explicit request (2) */
+}
+
+int gpt2_decode_set_verify_attention(GPT2* model, int request) {
+    GPT2Decode* d = model->decode;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (request < 0 || request > 2) { fprintf(stderr, "[paged_infer] verify attention: request 0, 1 or 2\n"); return 1; }
+    d->vf_request = request;
+    return 0;
+}
+
+int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
+                       float* draft_logprobs) {
+    GPT2Decode* d = model->decode;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (!n_draft || !n_accepted || !out_tokens) return 1;
+    if (d->sample) {
+        fprintf(stderr, "[paged_infer] verify: greedy decoding only (sampling mode %d is on)\n", d->sample);
+        return 1;
+    }
+    const GPT2Config c = model->config;
+    const int B = d->B, C = c.channels, MR = HPA_VERIFY_MAX_ROWS;
+    int R = 0, T = 0, ND = 0;
+    for (int b = 0; b < B; b++) {
+        if (n_draft[b] < -1 || n_draft[b] > MR - 1) {
+            fprintf(stderr, "[paged_infer] verify: n_draft[%d] = %d is outside [-1, %d]\n", b, n_draft[b], MR - 1);
+            return 1;
+        }
+        if (d->h_pos[b] + n_draft[b] + 1 > d->max_ctx) {
+            fprintf(stderr, "[paged_infer] verify: %d drafts overflow sequence %d\n", n_draft[b], b);
+            return 1;
+        }
+        R += n_draft[b] + 1;
+        if (n_draft[b] > 0) ND += n_draft[b];
+        if (n_draft[b] + 1 > T) T = n_draft[b] + 1;
+    }
+    if (ND && !drafts) return 1;
+    for (int i = 0; i < ND; i++)
+        if (drafts[i] < 0 || drafts[i] >= c.vocab_size) {
+            fprintf(stderr, "[paged_infer] verify: draft %d (%d) is outside [0, %d)\n", i, drafts[i], c.vocab_size);
+            return 1;
+        }
+    if (R == 0) {
+        for (int b = 0; b < B; b++) n_accepted[b] = -1;
+        return 0;
+    }
+    /* tables: drafts [B * (MR - 1)], draft0 [B], accepted [B], targets [B * MR], greedy ids [B * MR] */
+    const size_t n_int = (size_t)B * (MR - 1) + 2 * (size_t)B + 2 * (size_t)B * MR;
+    if (!d->vf_int) {
+        d->vf_int = (int*)hpa_malloc(n_int * sizeof(int));
+        d->vf_lp = (float*)hpa_malloc((size_t)B * MR * sizeof(float));
+        d->h_vf = (int*)malloc((n_int + 4 * (size_t)B) * sizeof(int));
+        if (!d->vf_int || !d->vf_lp || !d->h_vf) { dec_verify_free(d); return 1; }
+    }
+    int *v_drafts = d->vf_int, *v_d0 = v_drafts + (size_t)B * (MR - 1), *v_acc = v_d0 + B, *v_tgt = v_acc + B,
+        *v_top = v_tgt + (size_t)B * MR;
+    int *hst = d->h_vf, *hr0 = hst + B, *hln = hr0 + B, *hd0 = hln + B, *hacc = hd0 + B;
+    float* hlp = (float*)(hacc + B); /* [B * MR]: fits the n_int tail */
+    for (int b = 0; b < B; b++) hln[b] = n_draft[b] + 1;
+    for (int b = 0; b < B; b++)
+        if (hln[b] > 0 && dec_grow(d, b, hln[b], hln, NULL)) return 1;
+    if (dec_sync_block_table(d)) return 1;
+    if (dec_prefill_reserve(model, R)) return 1;
+    int r = 0, nd = 0;
+    for (int b = 0; b < B; b++) {
+        hst[b] = d->h_pos[b];
+        hr0[b] = r;
+        hd0[b] = nd;
+        r += hln[b];
+        if (n_draft[b] > 0) nd += n_draft[b];
+    }
+    if (hpa_memcpy(d->pf_start, hst, 3 * (size_t)B * sizeof(int)) || hpa_memcpy(v_d0, hd0, B * sizeof(int)) ||
+        (ND && hpa_memcpy(v_drafts, drafts, (size_t)ND * sizeof(int))))
+        return 1;
+    const int* d_row0 = d->pf_start + B;
+    const int* d_len = d->pf_start + 2 * B;
+    const int Rp = (R + 15) / 16 * 16;
+    int rc = hpa_verify_rows(d->d_next, v_drafts, v_d0, d->pf_start, d_row0, d_len, B, d->pf_tok, d->pf_pos, d->pf_seq,
+                             v_tgt);
+    if (!rc)
+        rc = dec_prefill_layers(model, R, T,
+                                gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request));
+    const DecScore sc = {NULL, NULL, NULL, v_tgt, d->vf_lp, v_top};
+    if (!rc) rc = dec_score_rows(model, R, &sc);
+    /* the accepted row of every live sequence -> the decode rows, logits, pick
+     * (which advances pos by one from start + accepted) */
+    rc |= hpa_verify_accept(d->pf_tok, v_top, d->pf_start, d_row0, d_len, B, v_acc, d->pf_last, d->d_pos);
+    rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->pf_last, B, d->res, d->st1, d->Mp, C);
+    rc |= dec_gemm(model, 0, G_LOGITS);
+    rc |= dec_pick(model, d_len);
+    if (rc) return 1;
+    if (hpa_memcpy(hacc, v_acc, B * sizeof(int)) || hpa_memcpy(d->h_next, d->d_next, B * sizeof(int)) ||
+        (draft_logprobs && hpa_memcpy(hlp, d->vf_lp, (size_t)R * sizeof(float))))
+        return 1;
+    for (int b = 0; b < B; b++) {
+        n_accepted[b] = hacc[b];
+        if (hln[b] <= 0) continue;
+        const int a = hacc[b];
+        if (a < 0 || a > n_draft[b]) return 1;
+        for (int i = 0; i < a; i++) out_tokens[b * MR + i] = drafts[hd0[b] + i];
+        out_tokens[b * MR + a] = d->h_next[b];
+        for (int i = 0; draft_logprobs && i < n_draft[b]; i++) draft_logprobs[b * MR + i] = hlp[hr0[b] + i];
+        d->h_pos[b] += a + 1;
+    }
+    return hpa_synchronize();
 }
 
 int gpt2_decode_release(GPT2* model, int seq) {

@@ -264,6 +264,14 @@ def lib():
     _sig(L, "hpa_paged_attention_prefill", i, [_F, v, i, _I, i, _I, i, i, _F])
     _sig(L, "hpa_paged_attention_prefill_ragged", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
     _sig(L, "hpa_gather_rows_frag", i, [_F, _F, i, _I, i, _F, _F, i, i])
+    _sig(L, "hpa_attention_waves", i, [])
+    _sig(L, "hpa_paged_attention_verify", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
+    _sig(L, "hpa_verify_rows", i, [_I, _I, _I, _I, _I, _I, i, _I, _I, _I, _I])
+    _sig(L, "hpa_verify_accept", i, [_I, _I, _I, _I, _I, i, _I, _I, _I])
+    _sig(L, "gpt2_decode_verify", i, [v, _I, _I, _I, _I, _F])
+    _sig(L, "gpt2_decode_verify_plan", i, [i, i, i, i, i])
+    _sig(L, "gpt2_decode_set_verify_attention", i, [v, i])
+    _sig(L, "gpt2_ngram_draft", i, [_I, i, i, i, i, _I])
     _sig(L, "gpt2_decode_step", i, [v, _I, _I])
     _sig(L, "gpt2_decode_step_async", i, [v, _I])
     _sig(L, "gpt2_decode_step_traced", i, [v, _I, _I, _F])
@@ -380,6 +388,28 @@ def layer_plan(request, B, C, num_heads, max_ctx, kv_dtype=0, w_bf16=False, num_
 
 
 # ---------------------------------------------------------------- device buffers
+VERIFY_MAX_ROWS = 8  # HPA_VERIFY_MAX_ROWS
+
+
+def verify_plan(max_rows, kv_dtype=0, page_size=16, head_size=64, request=0):
+    """the attention kernel of a verify pass (gpt2_decode_verify_plan, pure): 1
+    hpa_paged_attention_verify, 0 hpa_paged_attention_prefill_ragged.  request:
+    0 auto, 1 the prefill kernel, 2 the verify kernel where it applies"""
+    return int(lib().gpt2_decode_verify_plan(int(max_rows), int(kv_dtype), int(page_size), int(head_size),
+                                             int(request)))
+
+
+def ngram_draft(history, k, max_ngram=3, min_ngram=1):
+    """gpt2_ngram_draft (host only): up to k tokens that followed the most
+    recent earlier occurrence of the longest matching suffix of `history`
+    (n-grams of max_ngram down to min_ngram tokens); [] without a match"""
+    h = np.ascontiguousarray(np.asarray(history, np.int32).reshape(-1))
+    out = np.zeros(max(int(k), 1), np.int32)
+    n = lib().gpt2_ngram_draft(h.ctypes.data_as(_I), int(h.size), int(max_ngram), int(min_ngram), int(k),
+                               out.ctypes.data_as(_I))
+    return out[:n].tolist()
+
+
 class DeviceBuffer:
     """hpa_malloc'd memory with numpy-typed upload/download helpers."""
 
@@ -952,6 +982,35 @@ class Model:
                                       lp.ctypes.data_as(_F), top.ctypes.data_as(_I), nxt.ctypes.data_as(_I)), "score")
         cuts = np.cumsum(lens)[:-1]
         return np.split(lp[:R], cuts), np.split(top[:R], cuts), nxt
+
+    def verify(self, drafts, want_logprobs=False):
+        """gpt2_decode_verify: one speculative greedy pass.  drafts: per
+        sequence a list of up to VERIFY_MAX_ROWS - 1 drafted ids ([]: a plain
+        decode step of that sequence) or None (sequence untouched).  Returns
+        (n_accepted, tokens, logprobs), per-sequence lists with None for an
+        untouched sequence: tokens[b] = the accepted drafts and then the
+        model's own next token (n_accepted[b] + 1 ids); logprobs[b] (None
+        unless want_logprobs) = log p(draft i | pending id, drafts before it)
+        for every drafted id, accepted or not."""
+        assert len(drafts) == self.B
+        nd = np.array([-1 if t is None else len(t) for t in drafts], np.int32)
+        parts = [np.asarray(t, np.int32).reshape(-1) for t in drafts if t is not None and len(t)]
+        flat = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(1, np.int32), np.int32)
+        acc = np.zeros(self.B, np.int32)
+        toks = np.zeros((self.B, VERIFY_MAX_ROWS), np.int32)
+        lp = np.zeros((self.B, VERIFY_MAX_ROWS), np.float32)
+        check(lib().gpt2_decode_verify(self.h, flat.ctypes.data_as(_I), nd.ctypes.data_as(_I), acc.ctypes.data_as(_I),
+                                       toks.ctypes.data_as(_I), lp.ctypes.data_as(_F) if want_logprobs else None),
+              "verify")
+        live = [int(n) >= 0 for n in nd]
+        return ([int(acc[b]) if live[b] else None for b in range(self.B)],
+                [toks[b, :acc[b] + 1].tolist() if live[b] else None for b in range(self.B)],
+                [lp[b, :nd[b]].copy() if live[b] and want_logprobs else None for b in range(self.B)])
+
+    def set_verify_attention(self, request=0):
+        """the attention kernel of verify(): 0 auto, 1 the prefill kernel, 2 the
+        few-row verify kernel where it applies (verify_plan)"""
+        check(lib().gpt2_decode_set_verify_attention(self.h, int(request)), "set_verify_attention")
 
     def set_score_chunk(self, rows=0):
         """rows per SCORE GEMM of score(): 0 = the default, else a positive
