@@ -63,6 +63,19 @@ class HpaFusedGemm(ctypes.Structure):
                 ("pick_count", _V), ("score_target", _V), ("score_part", _V)]
 
 
+class HpaChainB16Args(ctypes.Structure):
+    """include/hip_paged_attn.h HpaChainB16Args, member for member (the bf16-weight
+    decode chain, hpa_chain_b16.hip)"""
+    _fields_ = [("B", ctypes.c_int), ("layer", ctypes.c_int), ("last", ctypes.c_int),
+                ("pool", ctypes.POINTER(HpaKVPool)), ("block_table", _V), ("bt_stride", ctypes.c_int),
+                ("pos", _V), ("att", _V), ("res", _V), ("res2", _V), ("fch", _V),
+                ("w_ap", _V), ("w_fc", _V), ("w_fp", _V), ("w_qkv", _V),
+                ("b_ap", _V), ("ln2_w", _V), ("ln2_b", _V), ("b_fc", _V), ("b_fp", _V),
+                ("ln1_w", _V), ("ln1_b", _V), ("b_qkv", _V),
+                ("q_out", _V), ("stats_out", _V), ("stats_mp", ctypes.c_int), ("slab", _V),
+                ("counters", _V), ("err", _V), ("err_sticky", _V)]
+
+
 HPA_FEPI_QKV, HPA_FEPI_RESID, HPA_FEPI_GELU, HPA_FEPI_LOGITS, HPA_FEPI_SCORE = 0, 1, 2, 3, 4
 HPA_COMM_SEND, HPA_COMM_RECV, HPA_COMM_COPY = 0, 1, 2
 
@@ -93,6 +106,22 @@ def to_frag(a, pad=16):
 def from_frag(f, rows, K):
     m, k = np.meshgrid(np.arange(rows), np.arange(K), indexing="ij")
     return f[frag_index(m, k, K)]
+
+
+def frag_bf16_index(m, k, K):
+    """element (m, k) of a [rows][K] matrix in the bf16 frag layout (hip_paged_attn.h;
+    vectorised over m, k): the 16-byte fragment of lane m % 16 + 16 * ((k % 16) / 4) of
+    (row block m / 16, 32-deep step k / 32), half (k % 32) / 16 of it"""
+    m = np.asarray(m)
+    k = np.asarray(k)
+    return ((((m >> 4) * (K >> 5) + (k >> 5)) * 64 + ((m & 15) + 16 * ((k >> 2) & 3))) << 3) + (k & 3) + \
+        4 * ((k >> 4) & 1)
+
+
+def from_frag_bf16(bits_u16, rows, K):
+    """bf16 frag layout (hpa_pack_frag_bf16, the chain's fch) -> [rows][K] bf16 bit patterns"""
+    m, k = np.meshgrid(np.arange(rows), np.arange(K), indexing="ij")
+    return np.asarray(bits_u16, np.uint16)[frag_bf16_index(m, k, K)]
 
 
 GPT2_124M = dict(maxT=1024, V=50257, L=12, NH=12, C=768)
@@ -298,6 +327,11 @@ def lib():
     _sig(L, "hpa_decode_layer_pick_splits", i, [i, i, i])
     _sig(L, "hpa_decode_layer_trace", i, [v, i])
     _sig(L, "hpa_decode_chain_b16_trace", i, [v, i])
+    _sig(L, "hpa_decode_chain_b16_eligible", i, [i, i, i])
+    _sig(L, "hpa_decode_chain_b16_eligible_cus", i, [i, i, i, i])
+    _sig(L, "hpa_decode_chain_b16_sizes", i, [i, ctypes.POINTER(sz)])
+    _sig(L, "hpa_decode_chain_b16", i, [ctypes.POINTER(HpaChainB16Args)])
+    _sig(L, "hpa_decode_chain_b16_first", i, [ctypes.POINTER(HpaChainB16Args), v, v, v, v, sz])
     _sig(L, "hpa_decode_cx_wave_trace", i, [v])
     _sig(L, "hpa_logits_trace", i, [v])
     _sig(L, "gpt2_decode_evicted", i, [v, _I])
