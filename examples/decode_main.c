@@ -18,7 +18,8 @@
  *   ./decode_main [-c checkpoint.bin] [-k tokenizer.bin] [-t tokens.bin]
  *                 [-b B] [-p prompt_len] [-n new_tokens] [-g] [-o ids.bin] [-q]
  *                 [--temperature X] [--top-k N] [--top-p X] [--perplexity] [--logprobs]
- *                 [--speculate K]
+ *                 [--speculate K] [--repetition-penalty R] [--presence-penalty X]
+ *                 [--frequency-penalty X] [--ban ID]...
  *     -g greedy (default: sampling as the reference), -o writes the B x
  *     (prompt + new) token ids as int32, -q prints only the summary line.
  *     --temperature / --top-k / --top-p: any of them selects filtered
@@ -36,6 +37,13 @@
  *     accepted drafts and one token of the model's own.  The ids are those of
  *     plain greedy decoding; one more line reports passes, tokens and the mean
  *     number of accepted drafts per sequence and pass.  Not with --logprobs.
+ *     --repetition-penalty R (> 0, 1 = off; the HF rule), --presence-penalty X,
+ *     --frequency-penalty X (0 = off; the OpenAI rule) and --ban ID (repeatable,
+ *     up to HPA_LOGIT_BIAS_MAX ids that are never produced): any of them turns
+ *     the logit processors on (gpt2_decode_set_processors) with these settings
+ *     for every sequence.  The window starts at position 0, so the prompt's
+ *     tokens count.  They apply in every mode, -g included (GPT-2 124M loops
+ *     within a few dozen greedy tokens without them).  Not with --speculate.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -73,6 +81,8 @@ int main(int argc, char** argv) {
     int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
     int perplexity = 0, logprobs = 0, speculate = 0;
     float temperature = 1.0f, top_p = 1.0f;
+    int processors = 0, n_ban = 0, ban[HPA_LOGIT_BIAS_MAX];
+    float repetition = 1.0f, presence = 0.0f, frequency = 0.0f, ban_value[HPA_LOGIT_BIAS_MAX];
     for (int i = 1; i < argc; i++) {
         const char* a = argv[i];
         const char* v = i + 1 < argc ? argv[i + 1] : NULL;
@@ -92,6 +102,15 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--top-k")) { top_k = atoi(v); filtered = 1; }
         else if (!strcmp(a, "--top-p")) { top_p = (float)atof(v); filtered = 1; }
         else if (!strcmp(a, "--speculate")) speculate = atoi(v);
+        else if (!strcmp(a, "--repetition-penalty")) { repetition = (float)atof(v); processors = 1; }
+        else if (!strcmp(a, "--presence-penalty")) { presence = (float)atof(v); processors = 1; }
+        else if (!strcmp(a, "--frequency-penalty")) { frequency = (float)atof(v); processors = 1; }
+        else if (!strcmp(a, "--ban")) {
+            if (n_ban >= HPA_LOGIT_BIAS_MAX) { fprintf(stderr, "at most %d --ban ids\n", HPA_LOGIT_BIAS_MAX); return 2; }
+            ban[n_ban] = atoi(v);
+            ban_value[n_ban++] = -1.0f / 0.0f; /* -inf: a hard ban */
+            processors = 1;
+        }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         i++;
     }
@@ -103,6 +122,11 @@ int main(int argc, char** argv) {
         if (!greedy || filtered || logprobs) {
             fprintf(stderr, "--speculate is greedy only: give -g, and none of --temperature, --top-k, --top-p, "
                             "--logprobs\n");
+            return 2;
+        }
+        if (processors) {
+            fprintf(stderr, "--speculate does not go with --repetition-penalty, --presence-penalty, "
+                            "--frequency-penalty or --ban: a verify pass has no per-row counts\n");
             return 2;
         }
     }
@@ -127,6 +151,11 @@ int main(int argc, char** argv) {
     if (!greedy && gpt2_decode_set_sampling(&model, filtered ? 2 : 1, 1337ULL)) return 1; /* rng_state = 1337 (:975) */
     if (!greedy && filtered && gpt2_decode_set_sampling_params(&model, -1, temperature, top_k, top_p)) return 2;
     if (logprobs && gpt2_decode_set_logprobs(&model, 1)) return 1;
+    if (processors) { /* bad values are refused with a message by the setters */
+        if (gpt2_decode_set_processors(&model, 1)) return 1;
+        if (gpt2_decode_set_penalties(&model, -1, repetition, presence, frequency, 0)) return 2;
+        if (gpt2_decode_set_logit_bias(&model, -1, ban, ban_value, n_ban)) return 2;
+    }
     gpt2_decode_set_graph(&model, 1);
 
     int* gen = (int*)malloc((size_t)B * total * sizeof(int));

@@ -661,6 +661,45 @@ int hpa_sample_final_serial(const float* logits, int B, int V, unsigned long lon
 int hpa_sample_filtered(const float* logits, int B, int V, const float* temperature, const int* top_k,
                         const float* top_p, unsigned long long* state, int* next, int* tokens, int* pos,
                         const int* active, int* n_kept, float* cut);
+/* ---------------- logit processors (hpa_process.hip) ----------------
+ * Repetition, presence and frequency penalties and a sparse logit bias, per
+ * row, from the raw logits [B][V] and a dense count table counts [B][V]
+ * (uint16, 4-byte aligned base).  For an active row b and column t, x = the raw
+ * logit, c = counts[b][t], in fp32, every step rounded on its own, in this order:
+ *     if c > 0:  x = x > 0 ? x / repetition[b] : x * repetition[b]
+ *     x = x - frequency[b] * (float)c - (c > 0 ? presence[b] : 0)
+ *     if t is in b's bias list:  x = x + its value        (finite, or -inf: a ban)
+ * With repetition 1, frequency = presence = 0 and no bias the processed row is
+ * the raw row bit for bit.  The bias list of row b is bias_ids / bias_values
+ * [b][HPA_LOGIT_BIAS_MAX], its first bias_n[b] entries (ids distinct and in
+ * [0, V); an id outside is ignored; bias_n NULL: no list).
+ * Outputs: processed [B][V] (nullable) and, per (slice, row), the slice's
+ * (max, argmax) at part[(slice * Mp + b) * 2] (value, then the column's bits) --
+ * the layout hpa_argmax_final reads with ntiles = slices; the larger value
+ * wins, then the lower column; a slice without a value above -inf leaves
+ * (-inf, INT_MAX), so a row with none gets id 0 (part nullable).  active as
+ * hpa_argmax_final: an inactive row keeps its processed row and its partials.
+ * slices: column ranges per row, one workgroup each (<= 0: by
+ * hpa_logits_process_slices on this device); a slice may hold at most 65528
+ * columns.  Reductions run in a fixed order: a launch repeats bit for bit. */
+#define HPA_LOGIT_BIAS_MAX 300
+int hpa_logits_process(const float* logits, int B, int V, const unsigned short* counts, const float* repetition,
+                       const float* presence, const float* frequency, const int* bias_ids, const float* bias_values,
+                       const int* bias_n, const int* active, float* processed, float* part, int Mp, int slices);
+/* slices per row for hpa_logits_process, pure host arithmetic: about four
+ * workgroups per CU over the launch (B = 8 still fills 256 CUs, B = 64 is not
+ * split further than that), no slice under 1024 columns, none over the limit
+ * above.  0 on bad arguments; num_cus <= 0 counts as 256. */
+int hpa_logits_process_slices(int B, int V, int num_cus);
+/* R fed tokens: history[seq[i]][pos[i]] = tok[i] (history [B][max_ctx]) and,
+ * where pos[i] >= from_pos[seq[i]], counts[seq[i]][tok[i]] += 1 (an integer
+ * atomic: the sums do not depend on the order).  seq NULL: row i is sequence
+ * i.  A row outside the tables is skipped.  max_ctx <= 65535. */
+int hpa_token_record(int* history, int max_ctx, unsigned short* counts, int V, int B, const int* from_pos,
+                     const int* seq, const int* pos, const int* tok, int R);
+/* counts[seq][*] = 0, then += 1 for every history[seq][p], from <= p < n
+ * (n <= from: the row is only zeroed) */
+int hpa_token_recount(const int* history, int max_ctx, unsigned short* counts, int V, int seq, int from, int n);
 /* paged decode attention writing its output in frag layout ([B][C]) */
 int hpa_paged_attention_decode_frag(const float* q, const HpaKVPool* pool, int layer,
                                     const int* block_table, int bt_stride, const int* pos,

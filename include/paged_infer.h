@@ -445,6 +445,72 @@ int    gpt2_decode_sampling_params(GPT2* model, int seq, float* temperature, int
  * gpt2_decode_set_sampling call (no states yet) and for seq out of range.
  * Waits for queued work. */
 int    gpt2_decode_seed_sequence(GPT2* model, int seq, unsigned long long seed);
+/* ---------------- logit processors ----------------
+ * Repetition (CTRL / HF rule), presence and frequency (OpenAI rule) penalties
+ * and a logit bias, per sequence, applied on the device before every pick.
+ * Off by default; while off a step's launches and bits are what they were.
+ *
+ * While on, the engine keeps on the device a history int32 [B][max_ctx]
+ * (history[b][p]: the token whose K/V sits at position p) and a count table
+ * uint16 [B][V]: count[b][t] = the positions p in [from_pos[b], pos[b]) with
+ * history[b][p] == t.  A token is recorded when it is FED: the decode step's
+ * token (uploaded or fed back on the device) and every row of a prefill /
+ * ragged / score pass; the pending id is not counted until it is fed.  So at
+ * pick time the window holds every token fed so far, this pass's included.
+ *
+ * The processed logit of an active row b, column t (x = raw logit, c =
+ * count[b][t]), in fp32 in this order (hpa_logits_process):
+ *     if c > 0:  x = x > 0 ? x / repetition : x * repetition
+ *     x = x - frequency * (float)c - (c > 0 ? presence : 0)
+ *     if t is in b's bias list:  x = x + bias            (-inf: a hard ban)
+ * Neutral settings (1, 0, 0, no bias) give the raw row bit for bit.  Every
+ * mode then picks from the processed row: mode 0 its argmax (lowest index on
+ * ties; 0 for a row with nothing above -inf), mode 1 hpa_sample_final, mode 2
+ * hpa_sample_filtered (temperature and filters after the processors, as vLLM /
+ * HF do; a banned id has probability 0).  The raw logits stay raw:
+ * gpt2_decode_logits, gpt2_decode_logprobs and gpt2_decode_score's outputs keep
+ * their meaning; the processed rows are gpt2_decode_processed_logits.  A ragged
+ * call's lens[b] = 0 row keeps its processed row, counts and next id.
+ *
+ * gpt2_decode_release, gpt2_decode_reset and an LRU eviction zero the
+ * sequence's counts (settings stay, like the sampling settings);
+ * gpt2_decode_fork gives dst history[src][0..n) counted over dst's own from_pos;
+ * gpt2_decode_set_positions recounts a moved sequence and refuses a position
+ * above the recorded history; gpt2_decode_fill_random* and gpt2_decode_verify
+ * are refused while on (each: message, nonzero, nothing changed).
+ *
+ * gpt2_decode_set_processors(1) needs every sequence at position 0 (a fresh
+ * engine or after gpt2_decode_reset) and max_ctx <= 65535; toggling drops a
+ * captured graph.  Buffers are allocated on first enable ((6 V + 4 max_ctx) B
+ * bytes) and freed with the engine. */
+int    gpt2_decode_set_processors(GPT2* model, int enable);
+int    gpt2_decode_processors(GPT2* model);
+/* sequence seq's penalties, or every sequence's (seq = -1).  Valid: repetition
+ * finite and > 0 (1 = off), presence and frequency finite (0 = off), 0 <=
+ * from_pos <= max_ctx (the window's first position: 0 counts the prompt as HF
+ * does, the prompt length counts generated tokens only as OpenAI does);
+ * anything else returns nonzero with a message and changes nothing.  The
+ * settings live in device arrays, so the captured graph stays; they may be set
+ * while processors are off.  Changing from_pos recounts the sequence.  Waits
+ * for queued work. */
+int    gpt2_decode_set_penalties(GPT2* model, int seq, float repetition, float presence, float frequency,
+                                 int from_pos);
+/* each out pointer nullable; nonzero for seq out of range */
+int    gpt2_decode_penalties(GPT2* model, int seq, float* repetition, float* presence, float* frequency,
+                             int* from_pos);
+/* replaces sequence seq's (-1: every sequence's) whole bias list; n = 0 clears
+ * it.  Valid: 0 <= n <= HPA_LOGIT_BIAS_MAX (300), ids distinct and in [0, V),
+ * values finite or -inf (NaN and +inf refused); else nonzero, a message,
+ * nothing changed.  Keeps the captured graph; waits for queued work. */
+int    gpt2_decode_set_logit_bias(GPT2* model, int seq, const int* ids, const float* values, int n);
+/* ids, values: room for HPA_LOGIT_BIAS_MAX entries (each nullable); *n entries are written */
+int    gpt2_decode_logit_bias(GPT2* model, int seq, int* ids, float* values, int* n);
+/* the processed rows, device [B][V]; NULL while processors are off */
+float* gpt2_decode_processed_logits(GPT2* model);
+/* readbacks (nonzero while off): the *n = pos[seq] recorded tokens of seq
+ * (host_tokens nullable: only n), and its counts as ints [V] */
+int    gpt2_decode_history(GPT2* model, int seq, int* host_tokens, int* n);
+int    gpt2_decode_token_counts(GPT2* model, int seq, int* host_counts);
 /* algorithmic HBM bytes one step reads+writes at the current positions
  * (SURVEY.md 8d formula) and the attention kernel's share of them */
 double gpt2_decode_step_bytes(GPT2* model, double* attention_bytes);

@@ -730,7 +730,30 @@ struct GPT2Decode {
     int* vf_int;
     float* vf_lp;
     int* h_vf;
+    /* logit processors (gpt2_decode_set_processors).  The settings' host
+     * mirrors exist from gpt2_decode_init on (they may be set while off); the
+     * device tables are allocated on first enable: the fed tokens pr_hist
+     * [B][max_ctx], their counts pr_cnt [B][V], the processed rows pr_logits
+     * [B][V], the slices' (max, argmax) partials pr_part [pr_slices][Mp][2], and
+     * the settings the captured step reads: pr_f = repetition, presence,
+     * frequency [3][B]; pr_i = from_pos [B], bias n [B], bias ids
+     * [B][HPA_LOGIT_BIAS_MAX]; pr_bias = the bias values.  h_pr_rec [B]: how many
+     * positions of a sequence's history have been recorded (set_positions may
+     * not move above it) */
+    int proc, pr_slices, pr_V;
+    int* pr_hist;
+    unsigned short* pr_cnt;
+    float *pr_logits, *pr_part, *pr_f, *pr_bias;
+    int* pr_i;
+    float *h_pr_f, *h_pr_bias;
+    int *h_pr_i, *h_pr_rec;
 };
+static size_t dec_pr_cnt_bytes(const GPT2Decode* d) { /* uint16 [B][V], whole 8-byte words */
+    return ((size_t)d->B * d->pr_V * sizeof(unsigned short) + 7) & ~(size_t)7;
+}
+static int dec_pr_zero(GPT2Decode* d, int seq);
+static int dec_pr_recount(GPT2Decode* d, int seq);
+static void dec_pr_note(GPT2Decode* d);
 #define DEC_SCORE_CHUNK 1024 /* partials at V = 50257: 3142 tiles x 1024 rows x 16 B = 49.1 MiB */
 
 /* the manager's page index -> pool slot: a fixed pseudo-random permutation,
@@ -837,6 +860,9 @@ static void dec_free(GPT2Decode* d) {
     dec_score_free(d);
     dec_verify_free(d);
     hpa_free(d->d_lp);
+    hpa_free(d->pr_hist); hpa_free(d->pr_cnt); hpa_free(d->pr_logits); hpa_free(d->pr_part);
+    hpa_free(d->pr_f); hpa_free(d->pr_bias); hpa_free(d->pr_i);
+    free(d->h_pr_f); free(d->h_pr_bias); free(d->h_pr_i); free(d->h_pr_rec);
     for (int k = 0; k < 2; k++) {
         hpa_event_destroy(d->prof_ev[k]);
         hpa_event_destroy(d->ev_tok[k]);
@@ -1427,6 +1453,15 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
         for (int b = 0; b < B; b++) { d->h_samp_t[b] = 1.0f; d->h_samp_k[b] = 0; d->h_samp_p[b] = 1.0f; }
         ok = dec_upload_sampling_params(d) == 0;
     }
+    if (ok) { /* logit processors: repetition 1, presence = frequency = 0, window from 0, no bias */
+        d->pr_V = V;
+        d->h_pr_f = (float*)calloc(3 * (size_t)B, sizeof(float));
+        d->h_pr_bias = (float*)calloc((size_t)B * HPA_LOGIT_BIAS_MAX, sizeof(float));
+        d->h_pr_i = (int*)calloc((size_t)B * (2 + HPA_LOGIT_BIAS_MAX), sizeof(int));
+        d->h_pr_rec = (int*)calloc(B, sizeof(int));
+        ok = d->h_pr_f && d->h_pr_bias && d->h_pr_i && d->h_pr_rec;
+        for (int b = 0; ok && b < B; b++) d->h_pr_f[b] = 1.0f;
+    }
     /* logits GEMM: the activation-resident kernel where it applies (C = 768,
      * B <= 64); stream-K where its shape limits allow (XL at B <= 64), which
      * needs a slab and zeroed counters; else the looped kernel */
@@ -1535,6 +1570,7 @@ static int dec_note_eviction(GPT2Decode* d, int ev, const int* busy, int* evicte
     d->h_evicted[ev] = 1;
     d->h_pos[ev] = 0;
     if (hpa_memcpy(d->d_pos + ev, &d->h_pos[ev], sizeof(int))) return 1;
+    if (dec_pr_zero(d, ev)) return 1;
     if (busy && busy[ev]) {
         fprintf(stderr, "[paged_infer] sequence %d of this batch was evicted: pool too small\n", ev);
         return 1;
@@ -1705,11 +1741,21 @@ static int dec_gemm(GPT2* model, int l, int which) {
 static int dec_pick_ids(GPT2* model, const int* active) {
     GPT2Decode* d = model->decode;
     const int V = model->config.vocab_size;
+    const float* lg = d->d_logits;
+    if (d->proc) { /* every mode picks from the processed rows; the raw logits stay where they are */
+        const int B = d->B;
+        if (hpa_logits_process(d->d_logits, B, V, d->pr_cnt, d->pr_f, d->pr_f + B, d->pr_f + 2 * B, d->pr_i + 2 * B,
+                               d->pr_bias, d->pr_i + B, active, d->pr_logits, d->pr_part, d->Mp, d->pr_slices))
+            return 1;
+        if (!d->sample)
+            return hpa_argmax_final(d->pr_part, d->pr_slices, d->Mp, B, d->d_next, d->d_tokens, d->d_pos, active);
+        lg = d->pr_logits;
+    }
     if (d->sample == 2)
-        return hpa_sample_filtered(d->d_logits, d->B, V, d->d_samp_t, d->d_samp_k, d->d_samp_p, d->d_rng, d->d_next,
+        return hpa_sample_filtered(lg, d->B, V, d->d_samp_t, d->d_samp_k, d->d_samp_p, d->d_rng, d->d_next,
                                    d->d_tokens, d->d_pos, active, NULL, NULL);
     if (d->sample)
-        return hpa_sample_final(d->d_logits, d->B, V, d->d_rng, d->d_next, d->d_tokens, d->d_pos, active);
+        return hpa_sample_final(lg, d->B, V, d->d_rng, d->d_next, d->d_tokens, d->d_pos, active);
     HpaFusedGemm g;
     dec_gemm_desc(model, 0, G_LOGITS, &g);
     const int npart = hpa_logits_partials(&g); /* per-tile or per-workgroup partials */
@@ -1835,7 +1881,11 @@ static int dec_launch(GPT2* model) {
     const int pl = p.form != 0;
     /* persistent layers: the first launch also zeroes their hand-off counters */
     const size_t zb = (DEC_ERR_INTS + (size_t)L * d->pl_ctr_ints) * sizeof(int);
-    int rc = p.first == 2 ? dec_first_b16(model, zb)
+    int rc = 0;
+    if (d->proc) /* the fed tokens into the history and the counts, before the pick advances pos */
+        rc = hpa_token_record(d->pr_hist, d->max_ctx, d->pr_cnt, d->pr_V, d->B, d->pr_i, NULL, d->d_pos, d->d_tokens,
+                              d->B);
+    rc |= p.first == 2 ? dec_first_b16(model, zb)
            : p.first == 1 ? dec_first(model, zb)
            : !pl ? hpa_embed_frag(d->d_tokens, d->d_pos, w->wte, w->wpe, d->res, d->st1, d->B, C)
                  : hpa_embed_frag_zero(d->d_tokens, d->d_pos, w->wte, w->wpe, d->res, d->st1, d->B, C, d->pl_ctr, zb);
@@ -1964,6 +2014,206 @@ int gpt2_decode_sampling_params(GPT2* model, int seq, float* temperature, int* t
     return 0;
 }
 
+/* ---- logit processors: penalties by what a sequence was fed, logit bias ----
+ * The contract is in paged_infer.h.  dec_pick_ids is the one place the
+ * processed rows are made and picked from; tokens are recorded where they are
+ * fed (dec_launch, dec_prefill_rows); everything that moves a position by
+ * other means zeroes or recounts the sequence's counts here. */
+
+/* the settings of every sequence -> the device tables (when they exist) */
+static int dec_pr_upload(GPT2Decode* d) {
+    if (!d->pr_f) return 0;
+    const size_t B = d->B;
+    return hpa_memcpy(d->pr_f, d->h_pr_f, 3 * B * sizeof(float)) ||
+           hpa_memcpy(d->pr_i, d->h_pr_i, B * (2 + HPA_LOGIT_BIAS_MAX) * sizeof(int)) ||
+           hpa_memcpy(d->pr_bias, d->h_pr_bias, B * HPA_LOGIT_BIAS_MAX * sizeof(float));
+}
+
+/* sequence seq restarts at position 0: no counts, no recorded history */
+static int dec_pr_zero(GPT2Decode* d, int seq) {
+    if (!d->proc) return 0;
+    d->h_pr_rec[seq] = 0;
+    return hpa_token_recount(d->pr_hist, d->max_ctx, d->pr_cnt, d->pr_V, seq, 0, 0);
+}
+
+/* sequence seq's counts again from its history over [from_pos, pos) */
+static int dec_pr_recount(GPT2Decode* d, int seq) {
+    if (!d->proc) return 0;
+    return hpa_token_recount(d->pr_hist, d->max_ctx, d->pr_cnt, d->pr_V, seq, d->h_pr_i[seq], d->h_pos[seq]);
+}
+
+/* positions have advanced by feeding: so has the recorded history */
+static void dec_pr_note(GPT2Decode* d) {
+    if (!d->proc) return;
+    for (int b = 0; b < d->B; b++)
+        if (d->h_pos[b] > d->h_pr_rec[b]) d->h_pr_rec[b] = d->h_pos[b];
+}
+
+int gpt2_decode_set_processors(GPT2* model, int enable) {
+    GPT2Decode* d = model->decode;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    enable = enable != 0;
+    if (d->proc == enable) return 0;
+    const int B = d->B, V = d->pr_V;
+    if (enable) {
+        if (d->max_ctx > 65535) {
+            fprintf(stderr, "[paged_infer] set_processors: max_ctx %d is above 65535 (the counts are uint16)\n", d->max_ctx);
+            return 1;
+        }
+        for (int b = 0; b < B; b++)
+            if (d->h_pos[b] != 0) {
+                fprintf(stderr, "[paged_infer] set_processors: sequence %d holds cached tokens (gpt2_decode_reset first)\n", b);
+                return 1;
+            }
+    }
+    if (hpa_synchronize()) return 1;
+    if (enable && !d->pr_hist) {
+        int ncu = 0;
+        hpa_device_info(NULL, 0, &ncu, NULL);
+        d->pr_slices = hpa_logits_process_slices(B, V, ncu);
+        d->pr_hist = (int*)hpa_malloc((size_t)B * d->max_ctx * sizeof(int));
+        d->pr_cnt = (unsigned short*)hpa_malloc(dec_pr_cnt_bytes(d));
+        d->pr_logits = (float*)hpa_malloc((size_t)B * V * sizeof(float));
+        d->pr_part = (float*)hpa_malloc((size_t)d->pr_slices * d->Mp * 2 * sizeof(float));
+        d->pr_f = (float*)hpa_malloc(3 * (size_t)B * sizeof(float));
+        d->pr_i = (int*)hpa_malloc((size_t)B * (2 + HPA_LOGIT_BIAS_MAX) * sizeof(int));
+        d->pr_bias = (float*)hpa_malloc((size_t)B * HPA_LOGIT_BIAS_MAX * sizeof(float));
+        if (d->pr_slices < 1 || !d->pr_hist || !d->pr_cnt || !d->pr_logits || !d->pr_part || !d->pr_f || !d->pr_i ||
+            !d->pr_bias || hpa_memset_async(d->pr_hist, 0, (size_t)B * d->max_ctx * sizeof(int)) ||
+            hpa_memset_async(d->pr_logits, 0, (size_t)B * V * sizeof(float)) ||
+            hpa_memset_async(d->pr_part, 0, (size_t)d->pr_slices * d->Mp * 2 * sizeof(float)) || dec_pr_upload(d)) {
+            hpa_free(d->pr_hist); hpa_free(d->pr_cnt); hpa_free(d->pr_logits); hpa_free(d->pr_part);
+            hpa_free(d->pr_f); hpa_free(d->pr_i); hpa_free(d->pr_bias);
+            d->pr_hist = NULL; d->pr_cnt = NULL; d->pr_logits = d->pr_part = d->pr_f = d->pr_bias = NULL; d->pr_i = NULL;
+            return 1;
+        }
+    }
+    if (enable) { /* every sequence is at position 0 */
+        if (hpa_memset_async(d->pr_cnt, 0, dec_pr_cnt_bytes(d))) return 1;
+        memset(d->h_pr_rec, 0, B * sizeof(int));
+    }
+    d->proc = enable;
+    if (d->graph) { /* recapture with / without the launches */
+        hpa_graph_destroy(d->graph);
+        d->graph = NULL;
+        if (dec_rezero(d)) return 1;
+    }
+    return hpa_synchronize();
+}
+
+int gpt2_decode_processors(GPT2* model) { return model->decode ? model->decode->proc : 0; }
+
+int gpt2_decode_set_penalties(GPT2* model, int seq, float repetition, float presence, float frequency, int from_pos) {
+    GPT2Decode* d = model->decode;
+    if (!d) return 1;
+    if (seq < -1 || seq >= d->B) {
+        fprintf(stderr, "[paged_infer] set_penalties: sequence %d out of range\n", seq);
+        return 1;
+    }
+    if (!(repetition > 0.0f) || isinf(repetition) || !isfinite(presence) || !isfinite(frequency) || from_pos < 0 ||
+        from_pos > d->max_ctx) {
+        fprintf(stderr, "[paged_infer] set_penalties: need repetition finite and > 0, presence and frequency finite, "
+                        "0 <= from_pos <= %d (got %g, %g, %g, %d)\n", d->max_ctx, (double)repetition, (double)presence,
+                (double)frequency, from_pos);
+        return 1;
+    }
+    if (hpa_synchronize()) return 1; /* queued steps still read the old values */
+    const int B = d->B;
+    for (int b = seq < 0 ? 0 : seq; b < (seq < 0 ? B : seq + 1); b++) {
+        d->h_pr_f[b] = repetition;
+        d->h_pr_f[B + b] = presence + 0.0f; /* -0 as +0: the neutral settings keep a row's bits */
+        d->h_pr_f[2 * B + b] = frequency + 0.0f;
+        const int moved = d->h_pr_i[b] != from_pos;
+        d->h_pr_i[b] = from_pos;
+        if (moved && dec_pr_recount(d, b)) return 1;
+    }
+    return dec_pr_upload(d);
+}
+
+int gpt2_decode_penalties(GPT2* model, int seq, float* repetition, float* presence, float* frequency, int* from_pos) {
+    GPT2Decode* d = model->decode;
+    if (!d || seq < 0 || seq >= d->B) return 1;
+    if (repetition) *repetition = d->h_pr_f[seq];
+    if (presence) *presence = d->h_pr_f[d->B + seq];
+    if (frequency) *frequency = d->h_pr_f[2 * d->B + seq];
+    if (from_pos) *from_pos = d->h_pr_i[seq];
+    return 0;
+}
+
+int gpt2_decode_set_logit_bias(GPT2* model, int seq, const int* ids, const float* values, int n) {
+    GPT2Decode* d = model->decode;
+    if (!d) return 1;
+    if (seq < -1 || seq >= d->B) {
+        fprintf(stderr, "[paged_infer] set_logit_bias: sequence %d out of range\n", seq);
+        return 1;
+    }
+    if (n < 0 || n > HPA_LOGIT_BIAS_MAX || (n > 0 && (!ids || !values))) {
+        fprintf(stderr, "[paged_infer] set_logit_bias: need 0 <= n <= %d and both tables (got %d)\n", HPA_LOGIT_BIAS_MAX, n);
+        return 1;
+    }
+    for (int i = 0; i < n; i++) {
+        if (ids[i] < 0 || ids[i] >= d->pr_V) {
+            fprintf(stderr, "[paged_infer] set_logit_bias: id %d is outside [0, %d)\n", ids[i], d->pr_V);
+            return 1;
+        }
+        for (int j = 0; j < i; j++)
+            if (ids[j] == ids[i]) {
+                fprintf(stderr, "[paged_infer] set_logit_bias: id %d is listed twice\n", ids[i]);
+                return 1;
+            }
+        if (isnan(values[i]) || (isinf(values[i]) && values[i] > 0.0f)) {
+            fprintf(stderr, "[paged_infer] set_logit_bias: the bias of id %d is NaN or +inf (finite, or -inf to ban)\n",
+                    ids[i]);
+            return 1;
+        }
+    }
+    if (hpa_synchronize()) return 1; /* queued steps still read the old list */
+    const int B = d->B;
+    for (int b = seq < 0 ? 0 : seq; b < (seq < 0 ? B : seq + 1); b++) {
+        d->h_pr_i[B + b] = n;
+        for (int i = 0; i < n; i++) {
+            d->h_pr_i[2 * B + (size_t)b * HPA_LOGIT_BIAS_MAX + i] = ids[i];
+            d->h_pr_bias[(size_t)b * HPA_LOGIT_BIAS_MAX + i] = values[i];
+        }
+    }
+    return dec_pr_upload(d);
+}
+
+int gpt2_decode_logit_bias(GPT2* model, int seq, int* ids, float* values, int* n) {
+    GPT2Decode* d = model->decode;
+    if (!d || seq < 0 || seq >= d->B) return 1;
+    const int B = d->B, k = d->h_pr_i[B + seq];
+    if (n) *n = k;
+    if (ids) memcpy(ids, d->h_pr_i + 2 * B + (size_t)seq * HPA_LOGIT_BIAS_MAX, k * sizeof(int));
+    if (values) memcpy(values, d->h_pr_bias + (size_t)seq * HPA_LOGIT_BIAS_MAX, k * sizeof(float));
+    return 0;
+}
+
+float* gpt2_decode_processed_logits(GPT2* model) {
+    return model->decode && model->decode->proc ? model->decode->pr_logits : NULL;
+}
+
+int gpt2_decode_history(GPT2* model, int seq, int* host_tokens, int* n) {
+    GPT2Decode* d = model->decode;
+    if (!d || !d->proc || seq < 0 || seq >= d->B) return 1;
+    if (n) *n = d->h_pos[seq];
+    if (!host_tokens || d->h_pos[seq] == 0) return 0;
+    return hpa_synchronize() ||
+           hpa_memcpy(host_tokens, d->pr_hist + (size_t)seq * d->max_ctx, d->h_pos[seq] * sizeof(int));
+}
+
+int gpt2_decode_token_counts(GPT2* model, int seq, int* host_counts) {
+    GPT2Decode* d = model->decode;
+    if (!d || !d->proc || seq < 0 || seq >= d->B || !host_counts) return 1;
+    const int V = d->pr_V;
+    unsigned short* h = (unsigned short*)malloc(V * sizeof(unsigned short));
+    if (!h) return 1;
+    const int rc = hpa_synchronize() || hpa_memcpy(h, d->pr_cnt + (size_t)seq * V, V * sizeof(unsigned short));
+    for (int t = 0; t < V && !rc; t++) host_counts[t] = h[t];
+    free(h);
+    return rc;
+}
+
 /* restart sequence seq's coin stream at `seed` (a request admitted into a
  * released slot gets a reproducible stream of its own) */
 int gpt2_decode_seed_sequence(GPT2* model, int seq, unsigned long long seed) {
@@ -2036,6 +2286,7 @@ static int dec_enqueue(GPT2* model, const int* tokens) {
         return 1;
     }
     for (int b = 0; b < d->B; b++) d->h_pos[b]++;
+    dec_pr_note(d);
     return 0;
 }
 
@@ -2327,7 +2578,11 @@ static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int
         hpa_memcpy(d->pf_last, hl, B * sizeof(int)))
         return 1;
     const int* d_len = d->pf_start + 2 * B;
-    int rc = dec_prefill_layers(model, (int)R, T, 0);
+    int rc = 0;
+    if (d->proc)
+        rc = hpa_token_record(d->pr_hist, d->max_ctx, d->pr_cnt, d->pr_V, B, d->pr_i, d->pf_seq, d->pf_pos, d->pf_tok,
+                              (int)R);
+    rc |= dec_prefill_layers(model, (int)R, T, 0);
     if (all_logits && !rc) rc |= prefill_all_logits(model, (int)R, all_logits, all_rows);
     if (score && !rc) rc |= dec_score_rows(model, (int)R, score);
     /* last row of every active sequence -> the decode rows, logits, pick; the
@@ -2339,6 +2594,7 @@ static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int
     rc |= dec_pick(model, d_len);
     if (rc) return 1;
     for (int b = 0; b < B; b++) d->h_pos[b] += lens[b];
+    dec_pr_note(d);
     if (next_tokens) {
         if (hpa_memcpy(d->h_next, d->d_next, B * sizeof(int))) return 1;
         memcpy(next_tokens, d->h_next, B * sizeof(int));
@@ -2411,6 +2667,11 @@ int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* 
     if (!n_draft || !n_accepted || !out_tokens) return 1;
     if (d->sample) {
         fprintf(stderr, "[paged_infer] verify: greedy decoding only (sampling mode %d is on)\n", d->sample);
+        return 1;
+    }
+    if (d->proc) {
+        fprintf(stderr, "[paged_infer] verify: not with logit processors on (the drafted rows' greedy ids would need "
+                        "per-row counts)\n");
         return 1;
     }
     const GPT2Config c = model->config;
@@ -2508,6 +2769,7 @@ int gpt2_decode_release(GPT2* model, int seq) {
     if (d->bm->prompt_block_count[seq]) free_blocks_for_prompt(d->bm, seq);
     d->h_pos[seq] = 0;
     if (hpa_memcpy(d->d_pos + seq, &d->h_pos[seq], sizeof(int))) return 1;
+    if (dec_pr_zero(d, seq)) return 1;
     return dec_sync_block_table(d);
 }
 
@@ -2562,6 +2824,13 @@ int gpt2_decode_fork(GPT2* model, int src, int dst, int n_tokens) {
     }
     d->h_pos[dst] = n_tokens;
     if (hpa_memcpy_async(d->d_pos + dst, &d->h_pos[dst], sizeof(int))) return 1;
+    if (d->proc) { /* the prefix's tokens, counted over dst's own window */
+        if (hpa_memcpy_async(d->pr_hist + (size_t)dst * d->max_ctx, d->pr_hist + (size_t)src * d->max_ctx,
+                             (size_t)n_tokens * sizeof(int)))
+            return 1;
+        d->h_pr_rec[dst] = n_tokens;
+        if (dec_pr_recount(d, dst)) return 1;
+    }
     if (n_tokens == d->h_pos[src]) { /* the source's pending next id is the fork's too */
         if (hpa_memcpy_async(d->d_next + dst, d->d_next + src, sizeof(int)) ||
             hpa_memcpy_async(d->d_tokens + dst, d->d_tokens + src, sizeof(int)))
@@ -2671,6 +2940,10 @@ int gpt2_decode_reset(GPT2* model) {
         d->h_pos[b] = 0;
     }
     if (hpa_memset_async(d->d_pos, 0, d->B * sizeof(int))) return 1;
+    if (d->proc) {
+        if (hpa_memset_async(d->pr_cnt, 0, dec_pr_cnt_bytes(d))) return 1;
+        memset(d->h_pr_rec, 0, d->B * sizeof(int));
+    }
     return dec_sync_block_table(d) || hpa_synchronize();
 }
 
@@ -2687,6 +2960,10 @@ int gpt2_decode_fill_random_ex(GPT2* model, int ctx, unsigned long long seed, in
     }
     if (bm_shared_pages(d->bm)) {
         fprintf(stderr, "[paged_infer] fill_random: pages are shared between sequences (release the forks first)\n");
+        return 1;
+    }
+    if (d->proc) {
+        fprintf(stderr, "[paged_infer] fill_random: not with logit processors on (random K/V has no token history)\n");
         return 1;
     }
     if (gpt2_decode_reset(model)) return 1;
@@ -3306,8 +3583,18 @@ int gpt2_decode_set_positions(GPT2* model, const int* pos) {
     for (int b = 0; b < d->B; b++) {
         if (pos[b] < 0 || pos[b] >= d->max_ctx) return 1;
         if (d->bm->prompt_block_count[b] * d->P < pos[b]) return 1;
+        if (d->proc && pos[b] > d->h_pr_rec[b]) {
+            fprintf(stderr, "[paged_infer] set_positions: %d is above sequence %d's recorded history (%d tokens) "
+                            "while logit processors are on\n", pos[b], b, d->h_pr_rec[b]);
+            return 1;
+        }
     }
-    for (int b = 0; b < d->B; b++) d->h_pos[b] = pos[b];
+    if (d->proc && hpa_synchronize()) return 1; /* queued steps still count into the old windows */
+    for (int b = 0; b < d->B; b++) {
+        const int moved = d->h_pos[b] != pos[b];
+        d->h_pos[b] = pos[b];
+        if (moved && dec_pr_recount(d, b)) return 1;
+    }
     return hpa_memcpy(d->d_pos, d->h_pos, d->B * sizeof(int));
 }
 

@@ -290,6 +290,19 @@ def lib():
     _sig(L, "gpt2_decode_set_sampling_params", i, [v, i, ctypes.c_float, i, ctypes.c_float])
     _sig(L, "gpt2_decode_sampling_params", i, [v, i, _F, _I, _F])
     _sig(L, "gpt2_decode_seed_sequence", i, [v, i, ctypes.c_ulonglong])
+    _sig(L, "gpt2_decode_set_processors", i, [v, i])
+    _sig(L, "gpt2_decode_processors", i, [v])
+    _sig(L, "gpt2_decode_set_penalties", i, [v, i, ctypes.c_float, ctypes.c_float, ctypes.c_float, i])
+    _sig(L, "gpt2_decode_penalties", i, [v, i, _F, _F, _F, _I])
+    _sig(L, "gpt2_decode_set_logit_bias", i, [v, i, _I, _F, i])
+    _sig(L, "gpt2_decode_logit_bias", i, [v, i, _I, _F, _I])
+    _sig(L, "gpt2_decode_processed_logits", v, [v])
+    _sig(L, "gpt2_decode_history", i, [v, i, _I, _I])
+    _sig(L, "gpt2_decode_token_counts", i, [v, i, _I])
+    _sig(L, "hpa_logits_process", i, [v, i, i, v, v, v, v, v, v, v, v, v, v, i, i])
+    _sig(L, "hpa_logits_process_slices", i, [i, i, i])
+    _sig(L, "hpa_token_record", i, [v, i, v, i, i, v, v, v, v, i])
+    _sig(L, "hpa_token_recount", i, [v, i, v, i, i, i, i])
     _sig(L, "hpa_paged_attention_prefill", i, [_F, v, i, _I, i, _I, i, i, _F])
     _sig(L, "hpa_paged_attention_prefill_ragged", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
     _sig(L, "hpa_gather_rows_frag", i, [_F, _F, i, _I, i, _F, _F, i, i])
@@ -1102,6 +1115,70 @@ class Model:
     def seed_sequence(self, seq, seed):
         """restart sequence seq's coin stream at seed"""
         check(lib().gpt2_decode_seed_sequence(self.h, int(seq), int(seed)), "seed_sequence")
+
+    def set_processors(self, enable=True):
+        """logit processors (penalties by the fed tokens, logit bias) before
+        every pick; needs every sequence at position 0 (paged_infer.h)"""
+        check(lib().gpt2_decode_set_processors(self.h, int(bool(enable))), "set_processors")
+
+    def processors(self):
+        return bool(lib().gpt2_decode_processors(self.h))
+
+    def set_penalties(self, seq=-1, repetition=1.0, presence=0.0, frequency=0.0, from_pos=0):
+        """sequence seq's (-1: every sequence's) penalties over the tokens fed
+        at positions >= from_pos: repetition > 0 (1 = off, HF rule), presence
+        and frequency (0 = off, OpenAI rule)"""
+        check(lib().gpt2_decode_set_penalties(self.h, int(seq), float(repetition), float(presence),
+                                              float(frequency), int(from_pos)), "set_penalties")
+
+    def penalties(self, seq):
+        """(repetition, presence, frequency, from_pos) of sequence seq"""
+        r, p, f, w = ctypes.c_float(), ctypes.c_float(), ctypes.c_float(), ctypes.c_int()
+        check(lib().gpt2_decode_penalties(self.h, int(seq), ctypes.byref(r), ctypes.byref(p), ctypes.byref(f),
+                                          ctypes.byref(w)), "penalties")
+        return r.value, p.value, f.value, w.value
+
+    def set_logit_bias(self, seq, ids, values):
+        """replace sequence seq's (-1: every sequence's) bias list: at most
+        300 distinct ids, values finite or -inf (a ban); empty lists clear it"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        values = np.ascontiguousarray(values, np.float32).reshape(-1)
+        if ids.size != values.size:
+            raise ValueError("set_logit_bias: ids and values differ in length")
+        check(lib().gpt2_decode_set_logit_bias(self.h, int(seq), ids.ctypes.data_as(_I), values.ctypes.data_as(_F),
+                                               int(ids.size)), "set_logit_bias")
+
+    def logit_bias(self, seq):
+        """(ids, values) of sequence seq's bias list"""
+        ids, values, n = np.zeros(300, np.int32), np.zeros(300, np.float32), ctypes.c_int()
+        check(lib().gpt2_decode_logit_bias(self.h, int(seq), ids.ctypes.data_as(_I), values.ctypes.data_as(_F),
+                                           ctypes.byref(n)), "logit_bias")
+        return ids[:n.value].copy(), values[:n.value].copy()
+
+    def processed_logits(self):
+        """(B, V) rows the last pick read, or None while processors are off"""
+        ptr = lib().gpt2_decode_processed_logits(self.h)
+        if not ptr:
+            return None
+        out = np.empty((self.B, self.cfg.vocab_size), np.float32)
+        check(lib().hpa_synchronize(), "synchronize")
+        check(lib().hpa_memcpy(out.ctypes.data, ptr, out.nbytes), "processed logits download")
+        return out
+
+    def history(self, seq):
+        """the tokens fed to sequence seq at positions [0, pos)"""
+        n = ctypes.c_int()
+        check(lib().gpt2_decode_history(self.h, int(seq), None, ctypes.byref(n)), "history")
+        out = np.zeros(n.value, np.int32)
+        if n.value:
+            check(lib().gpt2_decode_history(self.h, int(seq), out.ctypes.data_as(_I), ctypes.byref(n)), "history")
+        return out
+
+    def token_counts(self, seq):
+        """(V,) how often each token was fed to sequence seq inside its window"""
+        out = np.zeros(self.cfg.vocab_size, np.int32)
+        check(lib().gpt2_decode_token_counts(self.h, int(seq), out.ctypes.data_as(_I)), "token_counts")
+        return out
 
     def gemm_config(self, waves=None, row_blocks=None, col_tiles=None):
         """fused GEMM launch shapes [qkv, attproj, fc, fcproj, logits]:
