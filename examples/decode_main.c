@@ -19,7 +19,7 @@
  *                 [-b B] [-p prompt_len] [-n new_tokens] [-g] [-o ids.bin] [-q]
  *                 [--temperature X] [--top-k N] [--top-p X] [--perplexity] [--logprobs]
  *                 [--speculate K] [--repetition-penalty R] [--presence-penalty X]
- *                 [--frequency-penalty X] [--ban ID]...
+ *                 [--frequency-penalty X] [--ban ID]... [--top-logprobs K]
  *     -g greedy (default: sampling as the reference), -o writes the B x
  *     (prompt + new) token ids as int32, -q prints only the summary line.
  *     --temperature / --top-k / --top-p: any of them selects filtered
@@ -44,6 +44,12 @@
  *     for every sequence.  The window starts at position 0, so the prompt's
  *     tokens count.  They apply in every mode, -g included (GPT-2 124M loops
  *     within a few dozen greedy tokens without them).  Not with --speculate.
+ *     --top-logprobs K (1..HPA_TOP_LOGPROBS_MAX): prints sequence 0's K most
+ *     likely ids with their log-probabilities beside each generated token
+ *     (gpt2_decode_set_top_logprobs: the raw model distribution, whatever the
+ *     sampling settings and processors); with --perplexity the prompt pass is
+ *     gpt2_decode_score_top and every prompt position of sequence 0 prints its
+ *     K alternatives.  Not with --speculate.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -76,10 +82,22 @@ static void print_token(Tokenizer* tk, int id) {
     else printf("%d ", id);
 }
 
+/* " {id or text: logprob, ...}": the k alternatives of one row, most likely first */
+static void print_alternatives(Tokenizer* tk, const int* ids, const float* lps, int k) {
+    printf(" {");
+    for (int j = 0; j < k; j++) {
+        if (j) printf(", ");
+        if (tk->init_ok) { printf("'"); safe_printf(tokenizer_decode(tk, (unsigned)ids[j])); printf("'"); }
+        else printf("%d", ids[j]);
+        printf(": %.4f", lps[j]);
+    }
+    printf("}");
+}
+
 int main(int argc, char** argv) {
     const char *ckpt = NULL, *tok_path = NULL, *tokens_path = NULL, *ids_out = NULL;
     int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
-    int perplexity = 0, logprobs = 0, speculate = 0;
+    int perplexity = 0, logprobs = 0, speculate = 0, top_lp = 0;
     float temperature = 1.0f, top_p = 1.0f;
     int processors = 0, n_ban = 0, ban[HPA_LOGIT_BIAS_MAX];
     float repetition = 1.0f, presence = 0.0f, frequency = 0.0f, ban_value[HPA_LOGIT_BIAS_MAX];
@@ -102,6 +120,13 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--top-k")) { top_k = atoi(v); filtered = 1; }
         else if (!strcmp(a, "--top-p")) { top_p = (float)atof(v); filtered = 1; }
         else if (!strcmp(a, "--speculate")) speculate = atoi(v);
+        else if (!strcmp(a, "--top-logprobs")) {
+            top_lp = atoi(v);
+            if (top_lp < 1 || top_lp > HPA_TOP_LOGPROBS_MAX) {
+                fprintf(stderr, "--top-logprobs takes 1..%d\n", HPA_TOP_LOGPROBS_MAX);
+                return 2;
+            }
+        }
         else if (!strcmp(a, "--repetition-penalty")) { repetition = (float)atof(v); processors = 1; }
         else if (!strcmp(a, "--presence-penalty")) { presence = (float)atof(v); processors = 1; }
         else if (!strcmp(a, "--frequency-penalty")) { frequency = (float)atof(v); processors = 1; }
@@ -119,9 +144,9 @@ int main(int argc, char** argv) {
             fprintf(stderr, "--speculate takes 1..%d drafts\n", HPA_VERIFY_MAX_ROWS - 1);
             return 2;
         }
-        if (!greedy || filtered || logprobs) {
+        if (!greedy || filtered || logprobs || top_lp) {
             fprintf(stderr, "--speculate is greedy only: give -g, and none of --temperature, --top-k, --top-p, "
-                            "--logprobs\n");
+                            "--logprobs, --top-logprobs\n");
             return 2;
         }
         if (processors) {
@@ -151,6 +176,7 @@ int main(int argc, char** argv) {
     if (!greedy && gpt2_decode_set_sampling(&model, filtered ? 2 : 1, 1337ULL)) return 1; /* rng_state = 1337 (:975) */
     if (!greedy && filtered && gpt2_decode_set_sampling_params(&model, -1, temperature, top_k, top_p)) return 2;
     if (logprobs && gpt2_decode_set_logprobs(&model, 1)) return 1;
+    if (top_lp && gpt2_decode_set_top_logprobs(&model, top_lp)) return 1;
     if (processors) { /* bad values are refused with a message by the setters */
         if (gpt2_decode_set_processors(&model, 1)) return 1;
         if (gpt2_decode_set_penalties(&model, -1, repetition, presence, frequency, 0)) return 2;
@@ -162,7 +188,9 @@ int main(int argc, char** argv) {
     int* prompt = (int*)malloc((size_t)B * prompt_len * sizeof(int));
     int* next = (int*)malloc(B * sizeof(int));
     float* lp = (float*)malloc(B * sizeof(float));
-    if (!gen || !prompt || !next || !lp) return 1;
+    int* alt_ids = (int*)malloc((size_t)B * HPA_TOP_LOGPROBS_MAX * sizeof(int));
+    float* alt_lps = (float*)malloc((size_t)B * HPA_TOP_LOGPROBS_MAX * sizeof(float));
+    if (!gen || !prompt || !next || !lp || !alt_ids || !alt_lps) return 1;
     if (tokens_path) { /* int32 tokens, e.g. a prepro_tinyshakespeare.py .bin */
         FILE* f = fopen(tokens_path, "rb");
         if (!f || fread(prompt, sizeof(int), (size_t)B * prompt_len, f) != (size_t)B * prompt_len) {
@@ -198,7 +226,23 @@ int main(int argc, char** argv) {
             for (int t = 0; t < prompt_len; t++)
                 targets[(size_t)b * prompt_len + t] = t + 1 < prompt_len ? prompt[(size_t)b * prompt_len + t + 1] : -1;
         }
-        if (gpt2_decode_score(&model, prompt, lens, targets, score, NULL, next)) return 1;
+        if (top_lp) { /* the dense route: every prompt row's alternatives too */
+            int* row_ids = (int*)malloc(R * top_lp * sizeof(int));
+            float* row_lps = (float*)malloc(R * top_lp * sizeof(float));
+            if (!row_ids || !row_lps) return 1;
+            if (gpt2_decode_score_top(&model, prompt, lens, targets, score, top_lp, row_ids, row_lps, next)) return 1;
+            for (int t = 0; t < prompt_len && !quiet; t++) { /* sequence 0's rows come first */
+                printf("position %d after ", t);
+                print_token(&tk, prompt[t]);
+                printf(":");
+                print_alternatives(&tk, row_ids + (size_t)t * top_lp, row_lps + (size_t)t * top_lp, top_lp);
+                printf("\n");
+            }
+            free(row_ids);
+            free(row_lps);
+        } else if (gpt2_decode_score(&model, prompt, lens, targets, score, NULL, next)) {
+            return 1;
+        }
         double all = 0.0;
         for (int b = 0; b < B && prompt_len > 1; b++) {
             double nll = 0.0;
@@ -219,6 +263,7 @@ int main(int argc, char** argv) {
     }
     double t1 = now_s();
     if (logprobs && gpt2_decode_logprobs(&model, lp)) return 1;
+    if (top_lp && gpt2_decode_top_logprobs(&model, alt_ids, alt_lps)) return 1;
     for (int b = 0; b < B; b++) {
         memcpy(gen + (size_t)b * total, prompt + (size_t)b * prompt_len, prompt_len * sizeof(int));
         if (new_tokens > 0) gen[(size_t)b * total + prompt_len] = next[b];
@@ -266,13 +311,16 @@ int main(int argc, char** argv) {
     for (int t = 1; t < new_tokens && !speculate; t++) {
         if (!quiet) print_token(&tk, next[0]);
         if (!quiet && logprobs) printf("[%.4f] ", lp[0]);
+        if (!quiet && top_lp) { print_alternatives(&tk, alt_ids, alt_lps, top_lp); printf("\n"); }
         /* the previous ids stay on the device and feed this step */
         if (gpt2_decode_step(&model, NULL, next)) return 1;
         if (logprobs && gpt2_decode_logprobs(&model, lp)) return 1;
+        if (top_lp && gpt2_decode_top_logprobs(&model, alt_ids, alt_lps)) return 1;
         for (int b = 0; b < B; b++) gen[(size_t)b * total + prompt_len + t] = next[b];
     }
     if (!quiet && new_tokens > 0 && !speculate) print_token(&tk, next[0]);
     if (!quiet && logprobs && new_tokens > 0) printf("[%.4f] ", lp[0]);
+    if (!quiet && top_lp && new_tokens > 0) print_alternatives(&tk, alt_ids, alt_lps, top_lp);
     double t2 = now_s();
     if (!quiet) printf("\n---\nFinished!\n");
     printf("prefill %d x %d tokens in %.3f ms; generated %d tokens x %d sequences (%s) in %.3f ms: "
@@ -291,6 +339,8 @@ int main(int argc, char** argv) {
     free(prompt);
     free(next);
     free(lp);
+    free(alt_ids);
+    free(alt_lps);
     gpt2_free(&model);         /* does not free the manager (reference ownership) */
     destroy_block_manager(bm);
     return 0;

@@ -620,6 +620,38 @@ int hpa_score_final(const float* part, int ntiles, int Mp, int M, float* logprob
  * per row, sums in double in a fixed order.  active as hpa_argmax_final: rows
  * with active[b] <= 0 are left untouched.  An id outside [0, V) gives 0. */
 int hpa_logprob_rows(const float* logits, int B, int V, const int* ids, const int* active, float* logprob);
+/* ---------------- top log-probabilities (hpa_top.hip) ----------------
+ * The k best columns of every row of logits [rows][V] (row stride V, rows
+ * 4-byte aligned, finite values) and their log-probabilities.  Entry j of a
+ * row is its j-th element under: logit descending as a float comparison (-0.0
+ * and +0.0 tie), equal logits by ascending column; entry 0 is hpa_argmax_final's
+ * pick.  top_lps[r][j] = (float)((double)x[id] - lse_r), lse_r the row's
+ * log-sum-exp summed in double in a fixed order (a launch repeats bit for bit;
+ * within 4e-6 + 2^-22 max(|lse|, |x[id]|) of the float64 log-softmax).
+ *   active    nullable: rows with active[r] <= 0 are left untouched
+ *   targets   nullable: per row a column in [0, V) or -1
+ *   target_lp nullable with targets: [rows], 0.0 where target == -1
+ *   lse       nullable: [rows]
+ * Nonzero and nothing launched: k < 1, k > HPA_TOP_LOGPROBS_MAX, k > V, a null
+ * required pointer, rows <= 0; also V > 262144 (a row is cut into at most 256
+ * slices of 1024 columns).  Two launches (one wave per slice of a row: its k
+ * candidates and its (max, sum exp); then one workgroup per row that merges
+ * the slices) through a workspace:
+ * hpa_top_logprobs keeps one of its own, grown on demand (a growth waits for
+ * the stream and cannot happen while a graph is captured);
+ * hpa_top_logprobs_ws takes the caller's, 8-byte aligned, of at least
+ * hpa_top_logprobs_workspace bytes (enough for every launch of at most that
+ * many rows and that k), and the slice count (0: hpa_top_logprobs_slices; any
+ * other count needs rows * slices * (12 + 8 k) bytes and gives the same ids). */
+#define HPA_TOP_LOGPROBS_MAX 20
+int hpa_top_logprobs(const float* logits, int rows, int V, int k, const int* active, const int* targets, int* top_ids,
+                     float* top_lps, float* target_lp, float* lse);
+int hpa_top_logprobs_workspace(int rows, int V, int k, size_t* bytes);
+int hpa_top_logprobs_ws(const float* logits, int rows, int V, int k, const int* active, const int* targets,
+                        int* top_ids, float* top_lps, float* target_lp, float* lse, void* ws, size_t ws_bytes,
+                        int slices);
+/* slices a row is cut into at (rows, V) on num_cus CUs (<= 0: 256); host arithmetic only */
+int hpa_top_logprobs_slices(int rows, int V, int num_cus);
 /* multinomial draw per row from softmax(logits) with the reference's
  * generator and arithmetic order (softmax_forward :259-286, sample_mult
  * :837-848, random_f32 :826-835), one xorshift state per row advanced on the

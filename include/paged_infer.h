@@ -267,6 +267,33 @@ int  gpt2_decode_set_logprobs(GPT2* model, int enable);
 /* host_out [B] <- those log-probabilities (waits for the queued work);
  * host_out NULL: only the status.  Nonzero unless gpt2_decode_set_logprobs is on. */
 int  gpt2_decode_logprobs(GPT2* model, float* host_out);
+/* top log-probabilities (the alternatives: `top_logprobs` of the OpenAI API).
+ * k in [0, HPA_TOP_LOGPROBS_MAX]; 0 = off (default).  While on, every pick (decode
+ * step, prefill, ragged prefill, score, the tail of a verify pass) is followed
+ * by one hpa_top_logprobs pass over the raw logits rows [B][V]: the raw model
+ * distribution whatever the sampling mode, filters or logit processors, like
+ * gpt2_decode_logprobs.  Entry j of a row is the j-th column under (logit
+ * descending, column ascending on equal logits).  Rows a ragged call leaves
+ * untouched keep their values; a change of k clears every row to zeros until a
+ * pick rewrites it.  Changing k drops a captured graph; k out of range:
+ * nonzero, message, nothing changed.  Buffers allocated on first enable, freed
+ * with the engine. */
+int  gpt2_decode_set_top_logprobs(GPT2* model, int k);
+int  gpt2_decode_top_logprobs_k(GPT2* model);              /* -1 without an engine */
+/* host [B][k] each (either nullable); waits for queued work; nonzero while off */
+int  gpt2_decode_top_logprobs(GPT2* model, int* ids, float* logprobs);
+/* gpt2_decode_score, and for every packed row r the k best columns and their
+ * log-probabilities: top_ids / top_lps host [sum(lens)][k].  logprobs / targets
+ * as in gpt2_decode_score (targets required; -1 = none).  k in [1, HPA_TOP_LOGPROBS_MAX].
+ * The SCORE epilogue keeps one maximum per 16-column tile, so this call takes
+ * the dense route in chunks: per chunk of gpt2_decode_set_score_chunk rows
+ * (default here 256: 51 MB at V = 50257) one LOGITS GEMM into a [chunk][V]
+ * workspace (allocated on first use, freed with the engine) and one
+ * hpa_top_logprobs with the chunk's targets.  Everything else is the ragged
+ * pass.  Bad k, a target outside [-1, vocab_size) or a null output: nonzero,
+ * nothing changed. */
+int  gpt2_decode_score_top(GPT2* model, const int* tokens, const int* lens, const int* targets, float* logprobs,
+                           int k, int* top_ids, float* top_lps, int* next_tokens);
 /* retire sequence seq: its pages go back to the pool (block_manager.c:78-90),
  * its position restarts at 0, so the slot can admit a new prompt.  The slot's
  * sampler state and sampling settings (gpt2_decode_set_sampling_params) stay

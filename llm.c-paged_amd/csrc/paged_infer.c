@@ -721,6 +721,22 @@ struct GPT2Decode {
     /* gpt2_decode_set_logprobs: the chosen ids' log-probabilities [B] (NULL until first enabled) */
     int logprobs;
     float* d_lp;
+    /* gpt2_decode_set_top_logprobs: top_k alternatives per pick (0: off); ids and
+     * log-probabilities [B][HPA_TOP_LOGPROBS_MAX] capacity (rows of top_k entries in
+     * use) and the kernel's workspace, allocated on first enable */
+    int top_k;
+    int* d_top_ids;
+    float* d_top_lps;
+    void* d_top_ws;
+    size_t top_ws_bytes;
+    /* gpt2_decode_score_top: the dense logits of one chunk [st_cap][V], its rows'
+     * alternatives [st_cap][HPA_TOP_LOGPROBS_MAX] and the kernel's workspace,
+     * allocated on first use */
+    int st_cap;
+    float *st_logits, *st_lps;
+    int* st_ids;
+    void* st_ws;
+    size_t st_ws_bytes;
     /* speculative decoding (gpt2_decode_verify): the attention request
      * (gpt2_decode_set_verify_attention) and the pass's device tables, allocated on
      * first use: vf_int = drafts [B * 7], draft0 [B], accepted [B], then per row
@@ -754,6 +770,7 @@ static size_t dec_pr_cnt_bytes(const GPT2Decode* d) { /* uint16 [B][V], whole 8-
 static int dec_pr_zero(GPT2Decode* d, int seq);
 static int dec_pr_recount(GPT2Decode* d, int seq);
 static void dec_pr_note(GPT2Decode* d);
+#define DEC_SCORE_TOP_CHUNK 256 /* dense logits at V = 50257: 256 rows x 201 KB = 51.5 MB */
 #define DEC_SCORE_CHUNK 1024 /* partials at V = 50257: 3142 tiles x 1024 rows x 16 B = 49.1 MiB */
 
 /* the manager's page index -> pool slot: a fixed pseudo-random permutation,
@@ -811,6 +828,16 @@ static void dec_score_free(GPT2Decode* d) {
     d->sc_cap = 0;
 }
 
+static void dec_top_free(GPT2Decode* d) {
+    hpa_free(d->d_top_ids); hpa_free(d->d_top_lps); hpa_free(d->d_top_ws);
+    hpa_free(d->st_logits); hpa_free(d->st_lps); hpa_free(d->st_ids); hpa_free(d->st_ws);
+    d->d_top_ids = d->st_ids = NULL;
+    d->d_top_lps = d->st_logits = d->st_lps = NULL;
+    d->d_top_ws = d->st_ws = NULL;
+    d->top_ws_bytes = d->st_ws_bytes = 0;
+    d->st_cap = d->top_k = 0;
+}
+
 static void dec_verify_free(GPT2Decode* d) {
     hpa_free(d->vf_int); hpa_free(d->vf_lp);
     free(d->h_vf);
@@ -859,6 +886,7 @@ static void dec_free(GPT2Decode* d) {
     dec_prefill_free(d);
     dec_score_free(d);
     dec_verify_free(d);
+    dec_top_free(d);
     hpa_free(d->d_lp);
     hpa_free(d->pr_hist); hpa_free(d->pr_cnt); hpa_free(d->pr_logits); hpa_free(d->pr_part);
     hpa_free(d->pr_f); hpa_free(d->pr_bias); hpa_free(d->pr_i);
@@ -1765,12 +1793,16 @@ static int dec_pick_ids(GPT2* model, const int* active) {
 
 /* the pick and, with gpt2_decode_set_logprobs on, the chosen ids'
  * log-probabilities (the pick has advanced pos and written d_next; the
- * log-probability kernel reads d_logits and d_next only) */
+ * log-probability kernel reads d_logits and d_next only); with
+ * gpt2_decode_set_top_logprobs on, the raw rows' k best columns */
 static int dec_pick(GPT2* model, const int* active) {
     GPT2Decode* d = model->decode;
     int rc = dec_pick_ids(model, active);
     if (d->logprobs && !rc)
         rc = hpa_logprob_rows(d->d_logits, d->B, model->config.vocab_size, d->d_next, active, d->d_lp);
+    if (d->top_k && !rc)
+        rc = hpa_top_logprobs_ws(d->d_logits, d->B, model->config.vocab_size, d->top_k, active, NULL, d->d_top_ids,
+                                 d->d_top_lps, NULL, NULL, d->d_top_ws, d->top_ws_bytes, 0);
     return rc;
 }
 
@@ -1968,6 +2000,62 @@ int gpt2_decode_logprobs(GPT2* model, float* host_out) {
     if (!d || !d->logprobs || !d->d_lp) return 1;
     if (!host_out) return 0;
     return hpa_synchronize() || hpa_memcpy(host_out, d->d_lp, d->B * sizeof(float));
+}
+
+/* the k best columns of every pick's raw row (dec_pick): two more launches in
+ * the step, so a captured graph is dropped when k changes */
+int gpt2_decode_set_top_logprobs(GPT2* model, int k) {
+    GPT2Decode* d = model->decode;
+    if (!d) return 1;
+    const int V = model->config.vocab_size;
+    if (k < 0 || k > HPA_TOP_LOGPROBS_MAX || k > V) {
+        fprintf(stderr, "[paged_infer] set_top_logprobs: k = %d is outside [0, %d]\n", k,
+                V < HPA_TOP_LOGPROBS_MAX ? V : HPA_TOP_LOGPROBS_MAX);
+        return 1;
+    }
+    if (hpa_synchronize()) return 1;
+    if (k && !d->d_top_ids) { /* sized for every k, so a change of k allocates nothing */
+        const int kmax = V < HPA_TOP_LOGPROBS_MAX ? V : HPA_TOP_LOGPROBS_MAX;
+        const size_t n = (size_t)d->B * HPA_TOP_LOGPROBS_MAX;
+        size_t wsb = 0;
+        if (hpa_top_logprobs_workspace(d->B, V, kmax, &wsb)) return 1;
+        int* ids = (int*)hpa_malloc(n * sizeof(int));
+        float* lps = (float*)hpa_malloc(n * sizeof(float));
+        void* ws = hpa_malloc(wsb);
+        if (!ids || !lps || !ws || hpa_memset_async(ids, 0, n * sizeof(int)) ||
+            hpa_memset_async(lps, 0, n * sizeof(float)) || hpa_synchronize()) {
+            hpa_free(ids); hpa_free(lps); hpa_free(ws);
+            return 1;
+        }
+        d->d_top_ids = ids;
+        d->d_top_lps = lps;
+        d->d_top_ws = ws;
+        d->top_ws_bytes = wsb;
+    }
+    if (d->top_k == k) return 0;
+    if (k) { /* rows change their stride: a row no pick has rewritten since reads as zeros */
+        const size_t n = (size_t)d->B * HPA_TOP_LOGPROBS_MAX;
+        if (hpa_memset_async(d->d_top_ids, 0, n * sizeof(int)) || hpa_memset_async(d->d_top_lps, 0, n * sizeof(float)))
+            return 1;
+    }
+    d->top_k = k;
+    if (d->graph) { /* recapture with / without the launches */
+        hpa_graph_destroy(d->graph);
+        d->graph = NULL;
+        if (dec_rezero(d)) return 1;
+    }
+    return 0;
+}
+
+int gpt2_decode_top_logprobs_k(GPT2* model) { return model->decode ? model->decode->top_k : -1; }
+
+int gpt2_decode_top_logprobs(GPT2* model, int* ids, float* logprobs) {
+    GPT2Decode* d = model->decode;
+    if (!d || !d->top_k || !d->d_top_ids) return 1;
+    const size_t n = (size_t)d->B * d->top_k;
+    if (hpa_synchronize()) return 1;
+    return (ids && hpa_memcpy(ids, d->d_top_ids, n * sizeof(int))) ||
+           (logprobs && hpa_memcpy(logprobs, d->d_top_lps, n * sizeof(float)));
 }
 
 int gpt2_decode_set_score_chunk(GPT2* model, int rows) {
@@ -2424,6 +2512,11 @@ typedef struct {
     const int* d_targets;
     float* d_logprobs;
     int* d_top_ids;
+    /* gpt2_decode_score_top: k > 0 takes the dense route (dec_score_top_rows) and
+     * fills the rows' alternatives, host [R][k] each */
+    int k;
+    int* alt_ids;
+    float* alt_lps;
 } DecScore;
 
 /* the workspace of one SCORE chunk of `rows` (a multiple of 16) */
@@ -2493,6 +2586,85 @@ static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
         if (sc->top_ids) rc |= hpa_memcpy(sc->top_ids + r0, d->sc_top, n * sizeof(int));
         if (sc->d_logprobs) rc |= hpa_memcpy(sc->d_logprobs + r0, d->sc_lp, n * sizeof(float));
         if (sc->d_top_ids) rc |= hpa_memcpy(sc->d_top_ids + r0, d->sc_top, n * sizeof(int));
+    }
+    free(hrows);
+    return rc;
+}
+
+/* the dense workspace of one gpt2_decode_score_top chunk of `rows` */
+static int dec_score_top_reserve(GPT2* model, int rows) {
+    GPT2Decode* d = model->decode;
+    if (rows <= d->st_cap) return 0;
+    const int V = model->config.vocab_size;
+    hpa_free(d->st_logits); hpa_free(d->st_lps); hpa_free(d->st_ids); hpa_free(d->st_ws);
+    d->st_cap = 0;
+    size_t wsb = 0;
+    const int kmax = V < HPA_TOP_LOGPROBS_MAX ? V : HPA_TOP_LOGPROBS_MAX;
+    d->st_logits = d->st_lps = NULL;
+    d->st_ids = NULL;
+    d->st_ws = NULL;
+    if (hpa_top_logprobs_workspace(rows, V, kmax, &wsb)) return 1;
+    d->st_logits = (float*)hpa_malloc((size_t)rows * V * sizeof(float));
+    d->st_lps = (float*)hpa_malloc((size_t)rows * HPA_TOP_LOGPROBS_MAX * sizeof(float));
+    d->st_ids = (int*)hpa_malloc((size_t)rows * HPA_TOP_LOGPROBS_MAX * sizeof(int));
+    d->st_ws = hpa_malloc(wsb);
+    if (!d->st_logits || !d->st_lps || !d->st_ids || !d->st_ws) {
+        hpa_free(d->st_logits); hpa_free(d->st_lps); hpa_free(d->st_ids); hpa_free(d->st_ws);
+        d->st_logits = d->st_lps = NULL;
+        d->st_ids = NULL;
+        d->st_ws = NULL;
+        return 1;
+    }
+    d->st_ws_bytes = wsb;
+    d->st_cap = rows;
+    return 0;
+}
+
+/* every prefill row's target log-probability and k best columns: the dense
+ * route in chunks.  Per chunk the rows gathered as in dec_score_rows, one LOGITS
+ * GEMM into the chunk's [n][V] workspace (prefill_all_logits' call; its argmax
+ * partials go to the SCORE chunk's partial buffer and are not read: entry 0 comes
+ * from the selection kernel) and one hpa_top_logprobs with the chunk's targets */
+static int dec_score_top_rows(GPT2* model, int R, const DecScore* sc) {
+    GPT2Decode* d = model->decode;
+    const GPT2Config c = model->config;
+    const int C = c.channels, V = c.vocab_size, k = sc->k;
+    const int Rp = (R + 15) / 16 * 16;
+    int chunk = d->sc_chunk ? d->sc_chunk : DEC_SCORE_TOP_CHUNK;
+    if (chunk > Rp) chunk = Rp;
+    if (dec_score_reserve(model, chunk) || dec_score_top_reserve(model, chunk)) return 1;
+    int* hrows = (int*)malloc((size_t)chunk * sizeof(int));
+    if (!hrows) return 1;
+    int rc = 0;
+    for (int r0 = 0; r0 < R && !rc; r0 += chunk) {
+        const int n = R - r0 < chunk ? R - r0 : chunk, np = (n + 15) / 16 * 16;
+        for (int i = 0; i < n; i++) hrows[i] = r0 + i;
+        rc |= hpa_memcpy(d->sc_rows, hrows, n * sizeof(int));
+        rc |= hpa_memcpy(d->sc_tgt, sc->targets + r0, n * sizeof(int));
+        rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->sc_rows, n, d->sc_x, d->sc_st, np, C);
+        HpaFusedGemm g;
+        memset(&g, 0, sizeof(g));
+        g.M = n;
+        g.w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
+        g.epilogue = HPA_FEPI_LOGITS;
+        g.x = d->sc_x;
+        g.K = C;
+        g.ln_stats = d->sc_st;
+        g.ln_ntiles = C / 16;
+        g.ln_w = model->params.lnfw;
+        g.ln_b = model->params.lnfb;
+        g.w = wpack_at(d, d->wpack_off[4]);
+        g.N = V;
+        g.out = d->st_logits;
+        g.part_out = d->sc_part; /* (V + 15) / 16 * np * 2 floats: half the SCORE partials' room */
+        rc |= hpa_gemm_fused(&g);
+        if (!rc)
+            rc |= hpa_top_logprobs_ws(d->st_logits, n, V, k, NULL, d->sc_tgt, d->st_ids, d->st_lps, d->sc_lp, NULL,
+                                      d->st_ws, d->st_ws_bytes, 0);
+        /* synchronous copies: the tables are free again */
+        if (sc->logprobs) rc |= hpa_memcpy(sc->logprobs + r0, d->sc_lp, n * sizeof(float));
+        rc |= hpa_memcpy(sc->alt_ids + (size_t)r0 * k, d->st_ids, (size_t)n * k * sizeof(int));
+        rc |= hpa_memcpy(sc->alt_lps + (size_t)r0 * k, d->st_lps, (size_t)n * k * sizeof(float));
     }
     free(hrows);
     return rc;
@@ -2584,7 +2756,7 @@ static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int
                               (int)R);
     rc |= dec_prefill_layers(model, (int)R, T, 0);
     if (all_logits && !rc) rc |= prefill_all_logits(model, (int)R, all_logits, all_rows);
-    if (score && !rc) rc |= dec_score_rows(model, (int)R, score);
+    if (score && !rc) rc |= score->k ? dec_score_top_rows(model, (int)R, score) : dec_score_rows(model, (int)R, score);
     /* last row of every active sequence -> the decode rows, logits, pick; the
      * pick advances pos by one: set pos = start + len - 1 first */
     for (int b = 0; b < B; b++) hst[b] = d->h_pos[b] + (lens[b] > 0 ? lens[b] - 1 : 0);
@@ -2624,7 +2796,19 @@ int gpt2_decode_score(GPT2* model, const int* tokens, const int* lens, const int
                       int* top_ids, int* next_tokens) {
     if (!model->decode) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
     if (!lens || !tokens || !targets || !logprobs) return 1;
-    const DecScore sc = {targets, logprobs, top_ids, NULL, NULL, NULL};
+    const DecScore sc = {targets, logprobs, top_ids, NULL, NULL, NULL, 0, NULL, NULL};
+    return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, &sc);
+}
+
+int gpt2_decode_score_top(GPT2* model, const int* tokens, const int* lens, const int* targets, float* logprobs,
+                          int k, int* top_ids, float* top_lps, int* next_tokens) {
+    if (!model->decode) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (!lens || !tokens || !targets || !logprobs || !top_ids || !top_lps) return 1;
+    if (k < 1 || k > HPA_TOP_LOGPROBS_MAX || k > model->config.vocab_size) {
+        fprintf(stderr, "[paged_infer] score_top: k = %d is outside [1, %d]\n", k, HPA_TOP_LOGPROBS_MAX);
+        return 1;
+    }
+    const DecScore sc = {targets, logprobs, NULL, NULL, NULL, NULL, k, top_ids, top_lps};
     return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, &sc);
 }
 
@@ -2736,7 +2920,7 @@ int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* 
     if (!rc)
         rc = dec_prefill_layers(model, R, T,
                                 gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request));
-    const DecScore sc = {NULL, NULL, NULL, v_tgt, d->vf_lp, v_top};
+    const DecScore sc = {NULL, NULL, NULL, v_tgt, d->vf_lp, v_top, 0, NULL, NULL};
     if (!rc) rc = dec_score_rows(model, R, &sc);
     /* the accepted row of every live sequence -> the decode rows, logits, pick
      * (which advances pos by one from start + accepted) */

@@ -285,6 +285,14 @@ def lib():
     _sig(L, "hpa_score_workspace", i, [i, i, ctypes.POINTER(ctypes.c_size_t)])
     _sig(L, "hpa_score_final", i, [v, i, i, i, v, v, v, v])
     _sig(L, "hpa_logprob_rows", i, [v, i, i, v, v, v])
+    _sig(L, "gpt2_decode_set_top_logprobs", i, [v, i])
+    _sig(L, "gpt2_decode_top_logprobs_k", i, [v])
+    _sig(L, "gpt2_decode_top_logprobs", i, [v, _I, _F])
+    _sig(L, "gpt2_decode_score_top", i, [v, _I, _I, _I, _F, i, _I, _F, _I])
+    _sig(L, "hpa_top_logprobs", i, [v, i, i, i, v, v, v, v, v, v])
+    _sig(L, "hpa_top_logprobs_workspace", i, [i, i, i, ctypes.POINTER(ctypes.c_size_t)])
+    _sig(L, "hpa_top_logprobs_ws", i, [v, i, i, i, v, v, v, v, v, v, v, ctypes.c_size_t, i])
+    _sig(L, "hpa_top_logprobs_slices", i, [i, i, i])
     _sig(L, "gpt2_decode_release", i, [v, i])
     _sig(L, "gpt2_decode_set_sampling", i, [v, i, ctypes.c_ulonglong])
     _sig(L, "gpt2_decode_set_sampling_params", i, [v, i, ctypes.c_float, i, ctypes.c_float])
@@ -436,6 +444,7 @@ def layer_plan(request, B, C, num_heads, max_ctx, kv_dtype=0, w_bf16=False, num_
 
 # ---------------------------------------------------------------- device buffers
 VERIFY_MAX_ROWS = 8  # HPA_VERIFY_MAX_ROWS
+TOP_LOGPROBS_MAX = 20  # HPA_TOP_LOGPROBS_MAX
 
 
 def verify_plan(max_rows, kv_dtype=0, page_size=16, head_size=64, request=0):
@@ -1075,6 +1084,52 @@ class Model:
         out = np.zeros(self.B, np.float32)
         check(lib().gpt2_decode_logprobs(self.h, out.ctypes.data_as(_F)), "logprobs")
         return out
+
+    def set_top_logprobs(self, k):
+        """after every pick also select the k (0..TOP_LOGPROBS_MAX, 0 = off) most
+        likely ids of the raw model distribution with their log-probabilities;
+        see top_logprobs()"""
+        check(lib().gpt2_decode_set_top_logprobs(self.h, int(k)), "set_top_logprobs")
+
+    def top_logprobs(self):
+        """(ids (B, k) int32, logprobs (B, k) float32) of the last pick's rows:
+        entry j is the j-th most likely id (equal logits: the lower id first);
+        sequences a ragged call left untouched keep their values;
+        set_top_logprobs first"""
+        k = lib().gpt2_decode_top_logprobs_k(self.h)
+        if k <= 0:
+            raise RuntimeError("top_logprobs: off (set_top_logprobs(k) first)")
+        ids = np.zeros((self.B, k), np.int32)
+        lps = np.zeros((self.B, k), np.float32)
+        check(lib().gpt2_decode_top_logprobs(self.h, ids.ctypes.data_as(_I), lps.ctypes.data_as(_F)), "top_logprobs")
+        return ids, lps
+
+    def score_top(self, seqs, k, targets=None):
+        """gpt2_decode_score_top: score(seqs, targets) that also returns every
+        position's k most likely ids and their log-probabilities.  Returns
+        (logprobs, top_ids, top_lps, next_ids): per-sequence arrays of
+        len(seq), (len(seq), k) int32 and (len(seq), k) float32, and the next
+        ids (B,)."""
+        assert len(seqs) == self.B
+        seqs = [np.asarray(t, np.int32).reshape(-1) for t in seqs]
+        if targets is None:
+            targets = [np.concatenate([t[1:], np.full(1, -1, np.int32)]) if len(t) else t for t in seqs]
+        targets = [np.asarray(t, np.int32).reshape(-1) for t in targets]
+        assert len(targets) == self.B and all(len(a) == len(b) for a, b in zip(seqs, targets))
+        lens = np.array([len(t) for t in seqs], np.int32)
+        R = int(lens.sum())
+        k = int(k)
+        flat = np.ascontiguousarray(np.concatenate(seqs) if R else np.zeros(1, np.int32), np.int32)
+        tgt = np.ascontiguousarray(np.concatenate(targets) if R else np.full(1, -1, np.int32), np.int32)
+        lp = np.zeros(max(R, 1), np.float32)
+        ids = np.zeros((max(R, 1), max(k, 1)), np.int32)
+        lps = np.zeros((max(R, 1), max(k, 1)), np.float32)
+        nxt = np.zeros(self.B, np.int32)
+        check(lib().gpt2_decode_score_top(self.h, flat.ctypes.data_as(_I), lens.ctypes.data_as(_I),
+                                          tgt.ctypes.data_as(_I), lp.ctypes.data_as(_F), k, ids.ctypes.data_as(_I),
+                                          lps.ctypes.data_as(_F), nxt.ctypes.data_as(_I)), "score_top")
+        cuts = np.cumsum(lens)[:-1]
+        return np.split(lp[:R], cuts), np.split(ids[:R], cuts), np.split(lps[:R], cuts), nxt
 
     def release(self, seq):
         """retire sequence seq: pages back to the pool, position 0"""
