@@ -329,6 +329,16 @@ int  gpt2_decode_step_async(GPT2* model, const int* tokens);
 /* one eager step that also copies the residual stream entering every layer
  * and the final one to host_x, row-major [L+1][B][C] (per-layer parity tests) */
 int  gpt2_decode_step_traced(GPT2* model, const int* tokens, int* next_tokens, float* host_x);
+/* the same for the dense ragged pass: arms the next call of
+ * gpt2_decode_prefill / _prefill_ragged / _score / _score_top / _verify, and
+ * that call only (it disarms on every exit path, refusals included;
+ * gpt2_forward's window prefill is such a pass too and uses it up).  The pass
+ * copies its residual stream after the embedding and after every layer to
+ * host_x, row-major [L+1][R][C], R the pass's packed rows in their order.
+ * floats: the room at host_x; a pass that needs more is refused before it
+ * changes anything (no page, no position).  host_x NULL disarms.  Off (the
+ * default) adds no launch. */
+int  gpt2_decode_trace_next_pass(GPT2* model, float* host_x, size_t floats);
 /* free every sequence's pages and rewind positions to 0 */
 int  gpt2_decode_reset(GPT2* model);
 /* synthetic K/V for positions [0, ctx) of every sequence (benchmark prefill) */

@@ -711,6 +711,10 @@ struct GPT2Decode {
     /* gpt2_decode_step_traced: the residual stream entering every layer and
      * the final one, row-major [L+1][B][C], written during that one step */
     float* trace_x;
+    /* gpt2_decode_trace_next_pass: host room [L+1][R][C] for the residual
+     * stream of the next dense pass (NULL: off), and its size in floats */
+    float* pf_trace_x;
+    size_t pf_trace_floats;
     /* scoring (gpt2_decode_score): rows per SCORE GEMM (0: DEC_SCORE_CHUNK) and the
      * workspace of one chunk of sc_cap rows, allocated on first use: the chunk's
      * rows gathered out of the prefill activations (frag [sc_cap][C] and their LNf
@@ -2670,6 +2674,17 @@ static int dec_score_top_rows(GPT2* model, int R, const DecScore* sc) {
     return rc;
 }
 
+/* an armed trace (gpt2_decode_trace_next_pass) must hold [L+1][R][C] floats:
+ * checked before a pass of R rows changes anything */
+static int dec_trace_fits(GPT2* model, long R) {
+    const GPT2Decode* d = model->decode;
+    if (!d->pf_trace_x) return 0;
+    const size_t need = (size_t)(model->config.num_layers + 1) * (size_t)R * model->config.channels;
+    if (d->pf_trace_floats >= need) return 0;
+    fprintf(stderr, "[paged_infer] trace: %zu floats for a pass of %ld rows, %zu needed\n", d->pf_trace_floats, R, need);
+    return 1;
+}
+
 /* the R packed rows of the uploaded row tables (pf_tok, pf_pos, pf_seq;
  * pf_start: start, row0, len) through the embedding and every layer; T =
  * max(len).  verify_attn: the few-row kernel (gpt2_decode_verify_plan) in
@@ -2681,6 +2696,19 @@ static int dec_prefill_layers(GPT2* model, int R, int T, int verify_attn) {
     const int* d_len = d->pf_start + 2 * B;
     const ParameterTensors* w = &model->params;
     int rc = hpa_embed_frag(d->pf_tok, d->pf_pos, w->wte, w->wpe, d->pf_res, d->pf_st1, R, C);
+    /* gpt2_decode_trace_next_pass: the residual stream after the embedding and
+     * after every layer, unpacked into a staging buffer and copied out (the
+     * copy is synchronous: the staging buffer is free again) */
+    float* stage = NULL;
+    const size_t RC = (size_t)R * C;
+    if (d->pf_trace_x) {
+        stage = (float*)hpa_malloc(RC * sizeof(float));
+        if (!stage) return 1;
+    }
+#define PF_TRACE(i) \
+    if (stage && !rc) \
+        rc |= hpa_unpack_frag(d->pf_res, R, C, stage, C) || hpa_memcpy(d->pf_trace_x + (size_t)(i) * RC, stage, RC * sizeof(float))
+    PF_TRACE(0);
     for (int l = 0; l < L && !rc; l++) {
         rc |= prefill_gemm(model, l, G_QKV, R);
         rc |= verify_attn ? hpa_paged_attention_verify(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
@@ -2690,14 +2718,16 @@ static int dec_prefill_layers(GPT2* model, int R, int T, int verify_attn) {
         rc |= prefill_gemm(model, l, G_ATTPROJ, R);
         rc |= prefill_gemm(model, l, G_FC, R);
         rc |= prefill_gemm(model, l, G_FCPROJ, R);
+        PF_TRACE(l + 1);
     }
+#undef PF_TRACE
+    if (stage) hpa_free(stage);
     return rc;
 }
 
-static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int* next_tokens, float* all_logits,
-                            const int* all_rows, const DecScore* score) {
+static int dec_prefill_rows_armed(GPT2* model, const int* tokens, const int* lens, int* next_tokens, float* all_logits,
+                                  const int* all_rows, const DecScore* score) {
     GPT2Decode* d = model->decode;
-    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
     const GPT2Config c = model->config;
     const int B = d->B, C = c.channels;
     long R = 0;
@@ -2713,6 +2743,7 @@ static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int
     }
     if (R == 0) return 0;
     if (R > (1L << 24)) { fprintf(stderr, "[paged_infer] prefill too large\n"); return 1; }
+    if (dec_trace_fits(model, R)) return 1;
     for (long i = 0; i < R; i++)
         if (tokens[i] < 0 || tokens[i] >= c.vocab_size) {
             fprintf(stderr, "[paged_infer] token out of range\n"); /* :591-596 */
@@ -2774,12 +2805,26 @@ static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int
     return hpa_synchronize();
 }
 
+/* gpt2_decode_trace_next_pass holds for one pass, whatever became of it */
+static int dec_trace_disarm(GPT2Decode* d, int rc) {
+    d->pf_trace_x = NULL;
+    d->pf_trace_floats = 0;
+    return rc;
+}
+
+static int dec_prefill_rows(GPT2* model, const int* tokens, const int* lens, int* next_tokens, float* all_logits,
+                            const int* all_rows, const DecScore* score) {
+    GPT2Decode* d = model->decode;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    return dec_trace_disarm(d, dec_prefill_rows_armed(model, tokens, lens, next_tokens, all_logits, all_rows, score));
+}
+
 int gpt2_decode_prefill(GPT2* model, const int* tokens, int T, int* next_tokens) {
     GPT2Decode* d = model->decode;
     if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    if (T <= 0) return 1;
+    if (T <= 0) return dec_trace_disarm(d, 1);
     int* lens = (int*)malloc(d->B * sizeof(int));
-    if (!lens) return 1;
+    if (!lens) return dec_trace_disarm(d, 1);
     for (int b = 0; b < d->B; b++) lens[b] = T;
     const int rc = dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, NULL);
     free(lens);
@@ -2788,14 +2833,14 @@ int gpt2_decode_prefill(GPT2* model, const int* tokens, int T, int* next_tokens)
 
 int gpt2_decode_prefill_ragged(GPT2* model, const int* tokens, const int* lens, int* next_tokens) {
     if (!model->decode) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    if (!lens || !tokens) return 1;
+    if (!lens || !tokens) return dec_trace_disarm(model->decode, 1);
     return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, NULL);
 }
 
 int gpt2_decode_score(GPT2* model, const int* tokens, const int* lens, const int* targets, float* logprobs,
                       int* top_ids, int* next_tokens) {
     if (!model->decode) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    if (!lens || !tokens || !targets || !logprobs) return 1;
+    if (!lens || !tokens || !targets || !logprobs) return dec_trace_disarm(model->decode, 1);
     const DecScore sc = {targets, logprobs, top_ids, NULL, NULL, NULL, 0, NULL, NULL};
     return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, &sc);
 }
@@ -2803,10 +2848,10 @@ int gpt2_decode_score(GPT2* model, const int* tokens, const int* lens, const int
 int gpt2_decode_score_top(GPT2* model, const int* tokens, const int* lens, const int* targets, float* logprobs,
                           int k, int* top_ids, float* top_lps, int* next_tokens) {
     if (!model->decode) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    if (!lens || !tokens || !targets || !logprobs || !top_ids || !top_lps) return 1;
+    if (!lens || !tokens || !targets || !logprobs || !top_ids || !top_lps) return dec_trace_disarm(model->decode, 1);
     if (k < 1 || k > HPA_TOP_LOGPROBS_MAX || k > model->config.vocab_size) {
         fprintf(stderr, "[paged_infer] score_top: k = %d is outside [1, %d]\n", k, HPA_TOP_LOGPROBS_MAX);
-        return 1;
+        return dec_trace_disarm(model->decode, 1);
     }
     const DecScore sc = {targets, logprobs, NULL, NULL, NULL, NULL, k, top_ids, top_lps};
     return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, &sc);
@@ -2844,10 +2889,9 @@ int gpt2_decode_set_verify_attention(GPT2* model, int request) {
     return 0;
 }
 
-int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
-                       float* draft_logprobs) {
+static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
+                            float* draft_logprobs) {
     GPT2Decode* d = model->decode;
-    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
     if (!n_draft || !n_accepted || !out_tokens) return 1;
     if (d->sample) {
         fprintf(stderr, "[paged_infer] verify: greedy decoding only (sampling mode %d is on)\n", d->sample);
@@ -2884,6 +2928,7 @@ int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* 
         for (int b = 0; b < B; b++) n_accepted[b] = -1;
         return 0;
     }
+    if (dec_trace_fits(model, R)) return 1;
     /* tables: drafts [B * (MR - 1)], draft0 [B], accepted [B], targets [B * MR], greedy ids [B * MR] */
     const size_t n_int = (size_t)B * (MR - 1) + 2 * (size_t)B + 2 * (size_t)B * MR;
     if (!d->vf_int) {
@@ -2943,6 +2988,13 @@ int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* 
         d->h_pos[b] += a + 1;
     }
     return hpa_synchronize();
+}
+
+int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
+                       float* draft_logprobs) {
+    GPT2Decode* d = model->decode;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    return dec_trace_disarm(d, dec_verify_armed(model, drafts, n_draft, n_accepted, out_tokens, draft_logprobs));
 }
 
 int gpt2_decode_release(GPT2* model, int seq) {
@@ -3053,6 +3105,14 @@ int gpt2_decode_step_traced(GPT2* model, const int* tokens, int* next_tokens, fl
     hpa_free(d->trace_x);
     d->trace_x = NULL;
     return rc;
+}
+
+int gpt2_decode_trace_next_pass(GPT2* model, float* host_x, size_t floats) {
+    GPT2Decode* d = model->decode;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    d->pf_trace_x = host_x; /* NULL: disarm */
+    d->pf_trace_floats = host_x ? floats : 0;
+    return 0;
 }
 
 int gpt2_decode_status(GPT2* model) {

@@ -325,6 +325,7 @@ def lib():
     _sig(L, "gpt2_decode_step", i, [v, _I, _I])
     _sig(L, "gpt2_decode_step_async", i, [v, _I])
     _sig(L, "gpt2_decode_step_traced", i, [v, _I, _I, _F])
+    _sig(L, "gpt2_decode_trace_next_pass", i, [v, _F, ctypes.c_size_t])
     _sig(L, "gpt2_decode_reset", i, [v])
     _sig(L, "gpt2_decode_fill_random", i, [v, i, ctypes.c_ulonglong])
     _sig(L, "gpt2_decode_set_graph", i, [v, i])
@@ -849,6 +850,24 @@ class Model:
         check(lib().gpt2_decode_step_traced(self.h, tp, nxt.ctypes.data_as(_I), xs.ctypes.data_as(_F)),
               "gpt2_decode_step_traced")
         return nxt, xs
+
+    def trace_next_pass(self, rows, floats=None):
+        """gpt2_decode_trace_next_pass: arms the next dense pass (prefill,
+        prefill_ragged, score, score_top, verify) and that one only.  Returns
+        the array the pass fills, (L+1, rows, C) float32: the residual stream
+        after the embedding and after every layer, rows in the pass's packed
+        order.  rows must be at least the pass's row count (a verify pass of
+        n drafts has n + 1 rows per live sequence); the first R of them are
+        written when it is more -- then as a flat [L+1][R][C] block at the
+        start of the array -- and a pass that needs more is refused.  floats
+        overrides the room the engine is told of (tests of that refusal).
+        The engine writes into the array's memory during the pass, so the
+        model keeps a reference to it until the next call of this method."""
+        xs = np.zeros((self.cfg.num_layers + 1, int(rows), self.cfg.channels), np.float32)
+        self._trace_xs = xs  # a caller that drops the result must not leave the engine a dangling pointer
+        check(lib().gpt2_decode_trace_next_pass(self.h, xs.ctypes.data_as(_F), xs.size if floats is None else int(floats)),
+              "gpt2_decode_trace_next_pass")
+        return xs
 
     def step_async(self, tokens=None):
         tp = None

@@ -12,6 +12,10 @@ import ctypes
 import numpy as np
 import pytest
 
+from gemm_bounds import bf16_ambiguous as _bf16_ambiguous  # noqa: F401  (shared with tests/dense_ref64.py)
+from gemm_bounds import bf16_operands, fp32_bound
+from gemm_bounds import rbf16 as _rbf16
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,21 +43,6 @@ def _stats_tiles(x, Mp):
         st[i, :M, 0] = blk.sum(1)
         st[i, :M, 1] = (blk * blk).sum(1)
     return st
-
-
-def _rbf16(x):
-    """fp32 -> bf16 value (round to nearest even, finite inputs), as fp32"""
-    u = np.ascontiguousarray(x, np.float32).view(np.uint32).astype(np.uint64)
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return u.astype(np.uint32).view(np.float32)
-
-
-def _bf16_ambiguous(a64):
-    """elements within 1e-5 relative of a bf16 rounding midpoint"""
-    a32 = a64.astype(np.float32)
-    lo = a32.view(np.uint32) & np.uint32(0xFFFF0000)
-    mid = (lo | np.uint32(0x8000)).view(np.float32).astype(np.float64)
-    return np.abs(a64 - mid) <= 1e-5 * np.abs(a64)
 
 
 def test_pack_frag_bf16_layout(hip):
@@ -103,6 +92,7 @@ def test_fused_bf16_weights(hip, epi, M, K, N, waves, rb, ct, ln, variant):
     if epi == "RESID":
         got = hip.from_frag(out.download(Mp * N), M, N)
         assert np.all(np.abs(got - (res + acc)) <= bound + 1e-6)
+        _assert_stats_out(hip, keep, got, M, N)
     elif epi == "GELU":
         got = hip.from_frag(out.download(Mp * N), M, N)
         ref = _gelu_tanh(acc)
@@ -176,6 +166,23 @@ def test_pack_unpack_roundtrip(hip):
     assert np.array_equal(d_b.download(a.shape), a)
 
 
+def _assert_stats_out(hip, keep, got, M, N):
+    """RESID stats_out [N/16][Mp][2] against the stored outputs got (M, N): for
+    every row below M every tile's sum within 2^-19 * sum|got16| of the float64
+    sum and its sum of squares within 2^-19 * sum got16^2.  A 16-term fp32 sum
+    is off by at most 15 * 2^-24 of sum|x|, plus one rounding per square: both
+    under 2^-20, and the bar is doubled from there."""
+    Mp = (M + 15) // 16 * 16
+    g = [k for k in keep if isinstance(k, hip.HpaFusedGemm)][0]
+    buf = [k for k in keep if isinstance(k, hip.DeviceBuffer) and k.ptr == g.stats_out][0]
+    st = buf.download((N // 16, Mp, 2)).astype(np.float64)
+    g16 = got.astype(np.float64).reshape(M, N // 16, 16)
+    err1 = np.abs(st[:, :M, 0].T - g16.sum(-1)) - 2.0 ** -19 * np.abs(g16).sum(-1)
+    err2 = np.abs(st[:, :M, 1].T - (g16 ** 2).sum(-1)) - 2.0 ** -19 * (g16 ** 2).sum(-1)
+    assert np.all(err1 <= 0), (np.unravel_index(np.argmax(err1), err1.shape), float(err1.max()))
+    assert np.all(err2 <= 0), (np.unravel_index(np.argmax(err2), err2.shape), float(err2.max()))
+
+
 def _run(hip, epi, M, K, N, waves, ln, rng, res=None, pool_args=None, rb=0, fixed=None, variant=0, ct=0,
          fold=False, w_bf16=False, sk_ws=False):
     L = hip.lib()
@@ -215,12 +222,7 @@ def _run(hip, epi, M, K, N, waves, ln, rng, res=None, pool_args=None, rb=0, fixe
         # reference: bf16-rounded operands, exact products, f64 sums; an A element
         # whose f64 value sits within 1e-5 relative of a bf16 rounding midpoint may
         # round either way on the GPU (fp32 LN): one bf16 ulp (2^-7 |a| bound) there
-        a32 = a.astype(np.float32)
-        amb = _bf16_ambiguous(a)
-        ab = _rbf16(a32).astype(np.float64)
-        Wb = _rbf16(W).astype(np.float64)
-        extra = (amb * np.abs(a) * 2.0 ** -7) @ np.abs(Wb).T
-        a, W = ab, Wb
+        a, W, extra = bf16_operands(a, W)
     g.bias = dev(bias) if epi != hip.HPA_FEPI_LOGITS else None
     if fold:  # LN folded into the packed weights (hpa_ln_fold_pack)
         assert ln
@@ -242,7 +244,7 @@ def _run(hip, epi, M, K, N, waves, ln, rng, res=None, pool_args=None, rb=0, fixe
     g.col_tiles = ct
     g.epilogue = epi
     acc = a @ W.astype(np.float64).T
-    bound = 4e-6 * (np.abs(a) @ np.abs(W.astype(np.float64)).T) + 2e-6
+    bound = fp32_bound(a, W)
     if w_bf16:
         bound = bound + extra
     if fold:
@@ -266,10 +268,12 @@ def _run(hip, epi, M, K, N, waves, ln, rng, res=None, pool_args=None, rb=0, fixe
     else:
         out = hip.DeviceBuffer(M * (N // 3) * 4)
         g.out = out.ptr
-        pool, bt, pos = pool_args
+        pool, bt, pos = pool_args[:3]
         g.pool = ctypes.pointer(pool.s)
         g.layer = 0
         g.block_table, g.bt_stride, g.pos = dev(bt), bt.shape[1], dev(pos)
+        if len(pool_args) > 3:  # many rows per sequence: row -> row of the block table (the dense pass)
+            g.row_seq = dev(pool_args[3])
     keep.append(out)
     keep.append(g)  # the descriptor (LOGITS: hpa_logits_partials)
     if variant == 3 and waves > 1:  # K-split ring: slab + counters (zeroed once; every launch leaves them zero)
@@ -296,7 +300,11 @@ def _run(hip, epi, M, K, N, waves, ln, rng, res=None, pool_args=None, rb=0, fixe
                                                (100, 512, 96, 16, 4, 1), (3, 48, 32, 16, 1, 1),
                                                (130, 768, 768, 0, 0, 0), (64, 3072, 768, 4, 2, 1),
                                                (48, 1600, 1600, 8, 4, 1), (64, 768, 768, 4, 4, 2),
-                                               (64, 768, 80, 4, 4, 4)])
+                                               (64, 768, 80, 4, 4, 4),
+                                               # the dense pass's launch shape: row blocks 4 -> 1 at 5 of them,
+                                               # 4 -> 1 at 9, second 64-row group
+                                               (70, 768, 768, 8, 4, 2), (70, 3072, 768, 8, 4, 2),
+                                               (130, 768, 768, 8, 4, 2), (130, 3072, 768, 8, 4, 2)])
 def test_fused_resid_with_stats(hip, M, K, N, waves, rb, ct):
     rng = np.random.default_rng(M + waves + rb)
     res = rng.uniform(-1, 1, (M, N)).astype(np.float32)
@@ -306,6 +314,7 @@ def test_fused_resid_with_stats(hip, M, K, N, waves, rb, ct):
     got = hip.from_frag(out.download(Mp * N), M, N)
     ref = res + acc
     assert np.all(np.abs(got - ref) <= bound + 1e-6)
+    _assert_stats_out(hip, keep, got, M, N)
     # padded rows stay zero
     full = out.download(Mp * N)
     if Mp > M:
@@ -659,6 +668,7 @@ def test_fused_stream_k(hip, epi, K, N, fold, M):
             assert np.all(np.abs(got - ref) <= bound + 1e-6)
         else:
             assert np.all(np.abs(got - (acc + res)) <= bound + 1e-6)
+            _assert_stats_out(hip, keep, got, M, N)
     # relaunch: bit-identical (fixed summation order), counters back at zero
     g = [k for k in keep if isinstance(k, hip.HpaFusedGemm)][0]
     hip.check(hip.lib().hpa_gemm_fused(ctypes.byref(g)), "relaunch")
@@ -778,3 +788,125 @@ def test_fused_ring_rejects_unsupported_shape(hip):
         _run(hip, hip.HPA_FEPI_GELU, 64, 768, 256, 1, ln=True, rng=np.random.default_rng(1), variant=3)
     with pytest.raises(RuntimeError):  # 5 K parts
         _run(hip, hip.HPA_FEPI_GELU, 64, 768, 256, 5, ln=False, rng=np.random.default_rng(1), variant=3)
+
+
+# ---------------------------------------------------------------- the dense pass's small kernels
+@pytest.mark.parametrize("C", [128, 768, 1600])
+@pytest.mark.parametrize("B", [1, 37, 130])
+@pytest.mark.parametrize("zero", [False, True], ids=["embed", "embed_zero"])
+def test_embed_frag(hip, B, C, zero):
+    """hpa_embed_frag / hpa_embed_frag_zero at ragged tokens and positions: rows
+    bit-equal to to_frag(wte[tok] + wpe[pos]), padded rows untouched; stats[b]
+    within 2^-14 * sum|x| of the float64 sum and 2^-14 * sum x^2 of the float64
+    sum of squares (up to 1600 fp32 terms in any order are off by less than
+    1600 * 2^-24 < 2^-13 relative to sum|x|; the kernel is a tree of at most 7
+    sequential adds per thread plus the shuffles, which 2^-14 leaves more than
+    100x); _zero: the counter block all zero, the bytes after it untouched"""
+    L = hip.lib()
+    rng = np.random.default_rng(B + C)
+    Vv, maxT = 300, 200
+    wte = rng.uniform(-0.5, 0.5, (Vv, C)).astype(np.float32)
+    wpe = rng.uniform(-0.1, 0.1, (maxT, C)).astype(np.float32)
+    tok = rng.integers(0, Vv, B).astype(np.int32)
+    pos = rng.integers(0, maxT, B).astype(np.int32)
+    tok[0], pos[0] = Vv - 1, maxT - 1
+    Mp = (B + 15) // 16 * 16
+    SENT = np.float32(-77.25)
+    d_res = hip.DeviceBuffer.from_array(np.full(Mp * C, SENT, np.float32))
+    d_st = hip.DeviceBuffer.from_array(np.full(Mp * 2, SENT, np.float32))
+    d_wte, d_wpe = hip.DeviceBuffer.from_array(wte), hip.DeviceBuffer.from_array(wpe)
+    d_tok, d_pos = hip.DeviceBuffer.from_array(tok), hip.DeviceBuffer.from_array(pos)
+    if zero:
+        zb = 4096
+        d_z = hip.DeviceBuffer.from_array(np.full(zb // 4 + 64, 0x5A5A5A5A, np.uint32))
+        hip.check(L.hpa_embed_frag_zero(d_tok.ptr, d_pos.ptr, d_wte.ptr, d_wpe.ptr, d_res.ptr, d_st.ptr, B, C, d_z.ptr, zb),
+                  "embed_frag_zero")
+    else:
+        hip.check(L.hpa_embed_frag(d_tok.ptr, d_pos.ptr, d_wte.ptr, d_wpe.ptr, d_res.ptr, d_st.ptr, B, C), "embed_frag")
+    hip.check(L.hpa_synchronize())
+    x = wte[tok] + wpe[pos]
+    want = np.full((Mp, C), SENT, np.float32)
+    want[:B] = x
+    got = d_res.download(Mp * C)
+    assert np.array_equal(got.view(np.uint32), hip.to_frag(want).view(np.uint32))
+    st = d_st.download((Mp, 2)).astype(np.float64)
+    assert np.all(st[B:] == SENT)
+    x64 = x.astype(np.float64)
+    assert np.all(np.abs(st[:B, 0] - x64.sum(-1)) <= 2.0 ** -14 * np.abs(x64).sum(-1))
+    assert np.all(np.abs(st[:B, 1] - (x64 ** 2).sum(-1)) <= 2.0 ** -14 * (x64 ** 2).sum(-1))
+    if zero:
+        z = d_z.download(zb // 4 + 64, np.uint32)
+        assert not z[:zb // 4].any()
+        assert np.all(z[zb // 4:] == 0x5A5A5A5A)
+
+
+@pytest.mark.parametrize("dst_Mp,n", [(16, 13), (80, 70)])
+def test_gather_rows_frag(hip, dst_Mp, n):
+    """hpa_gather_rows_frag, src_Mp = 144, C = 768: indices with repeats and -1
+    entries; rows and all C/16 statistics tiles bit-equal; -1 rows and the rows
+    at n and above keep their sentinel"""
+    L = hip.lib()
+    rng = np.random.default_rng(dst_Mp)
+    src_Mp, C = 144, 768
+    src = rng.standard_normal((src_Mp, C)).astype(np.float32)
+    sst = rng.standard_normal((C // 16, src_Mp, 2)).astype(np.float32)
+    idx = rng.integers(0, src_Mp, n).astype(np.int32)
+    idx[:8] = [5, 143, -1, 5, 0, 77, -1, 64]  # a repeat, both ends, skipped rows, the second 64-row group's first
+    idx[-1] = 63
+    SENT = np.float32(31.5)
+    d_src, d_sst = hip.DeviceBuffer.from_array(hip.to_frag(src)), hip.DeviceBuffer.from_array(sst)
+    d_idx = hip.DeviceBuffer.from_array(idx)
+    d_dst = hip.DeviceBuffer.from_array(np.full(dst_Mp * C, SENT, np.float32))
+    d_dst_st = hip.DeviceBuffer.from_array(np.full((C // 16, dst_Mp, 2), SENT, np.float32))
+    fp = lambda b: ctypes.cast(b.ptr, ctypes.POINTER(ctypes.c_float))  # noqa: E731  (the binding's typed pointers)
+    hip.check(L.hpa_gather_rows_frag(fp(d_src), fp(d_sst), src_Mp, ctypes.cast(d_idx.ptr, ctypes.POINTER(ctypes.c_int)), n,
+                                     fp(d_dst), fp(d_dst_st), dst_Mp, C), "gather_rows_frag")
+    hip.check(L.hpa_synchronize())
+    want = np.full((dst_Mp, C), SENT, np.float32)
+    want_st = np.full((C // 16, dst_Mp, 2), SENT, np.float32)
+    for i, r in enumerate(idx):
+        if r >= 0:
+            want[i] = src[r]
+            want_st[:, i] = sst[:, r]
+    got = hip.from_frag(d_dst.download(dst_Mp * C), dst_Mp, C)
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))
+    assert np.array_equal(d_dst_st.download((C // 16, dst_Mp, 2)).view(np.uint32), want_st.view(np.uint32))
+
+
+@pytest.mark.parametrize("P", [8, 64])
+def test_fused_qkv_row_seq(hip, P):
+    """the QKV epilogue as the dense pass uses it: 70 rows of 5 sequences
+    (row_seq), positions consecutive per sequence from ragged starts, at the
+    pass's launch shape (8 waves, 4 row blocks -> 1, 2 column tiles -> 1).
+    Every row's K / V, read back from its sequence's pages, within the module's
+    bound; every other slot of every sequence, and the pages of a sixth
+    sequence no row names, bit-identical to what they held"""
+    rng = np.random.default_rng(P)
+    NH, C, CTX = 12, 768, 128
+    lens = np.array([3, 20, 1, 30, 16])
+    start = np.array([0, P - 1, 37, 5, 64 - 9], np.int32)  # 55: rows cross key 64
+    M, K, N = int(lens.sum()), C, 3 * C
+    seq = np.repeat(np.arange(5), lens).astype(np.int32)
+    pos = np.concatenate([start[b] + np.arange(lens[b]) for b in range(5)]).astype(np.int32)
+    pages = CTX // P
+    pool = hip.Pool(1, NH, P, 6 * pages)
+    bt = rng.permutation(6 * pages).astype(np.int32).reshape(6, pages)
+    old = []
+    for b in range(6):
+        k0 = rng.uniform(-1, 1, (CTX, C)).astype(np.float32)
+        v0 = rng.uniform(-1, 1, (CTX, C)).astype(np.float32)
+        pool.write_tokens(0, bt[b], k0, v0)
+        old.append((k0, v0))
+    out, acc, bound, keep = _run(hip, hip.HPA_FEPI_QKV, M, K, N, 8, ln=True, rng=rng, rb=4, ct=2,
+                                 pool_args=(pool, bt, pos, seq))
+    q = out.download((M, C))
+    assert np.all(np.abs(q - acc[:, :C]) <= bound[:, :C])
+    for b in range(6):
+        k, v = pool.read_tokens(0, bt[b], CTX)
+        mine = np.flatnonzero(seq == b)
+        written = np.zeros(CTX, bool)
+        written[pos[mine]] = True
+        for got, o, lo in ((k, old[b][0], C), (v, old[b][1], 2 * C)):
+            assert np.array_equal(got[~written].view(np.uint32), o[~written].view(np.uint32)), b
+            for r in mine:
+                assert np.all(np.abs(got[pos[r]] - acc[r, lo:lo + C]) <= bound[r, lo:lo + C]), (b, r)

@@ -197,8 +197,10 @@ def test_bf16_five_launches(hip, monkeypatch):
 @pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16_weights_and_pool"])
 def test_prefill_ragged_appends(hip, bf16):
     """prefill_ragged of 0, 1, 17 and 40 tokens from ragged positions (C = 768,
-    B = 4, P = 16): (a)/(b) on every layer, (c) on layer 0 from the embedding;
-    the untouched sequence's rows bit-identical"""
+    B = 4, P = 16): (a)/(b) on every layer, (c) from the embedding where no
+    trace is needed; the untouched sequence's rows bit-identical.  (c) on every
+    layer, the layer outputs and the decode rows of the dense pass are held
+    through its trace by tests/test_gpu_dense_pass.py"""
     C, NH, B, P = 768, 12, 4, 16
     cfgd, params, m = _open(hip, C, NH, B, P, bf16, bf16, None, 4 if bf16 else 3)
     ref = ref64.Ref64(cfgd, params, w_bf16=bf16, kv_bf16=bf16)
