@@ -18,7 +18,7 @@
  *   ./decode_main [-c checkpoint.bin] [-k tokenizer.bin] [-t tokens.bin]
  *                 [-b B] [-p prompt_len] [-n new_tokens] [-g] [-o ids.bin] [-q]
  *                 [--temperature X] [--top-k N] [--top-p X] [--perplexity] [--logprobs]
- *                 [--speculate K] [--repetition-penalty R] [--presence-penalty X]
+ *                 [--speculate K] [--speculate-sampled K] [--repetition-penalty R] [--presence-penalty X]
  *                 [--frequency-penalty X] [--ban ID]... [--top-logprobs K]
  *     -g greedy (default: sampling as the reference), -o writes the B x
  *     (prompt + new) token ids as int32, -q prints only the summary line.
@@ -30,6 +30,11 @@
  *     and its exp per sequence and overall.  --logprobs: prints sequence 0's
  *     log-probability beside each generated token (gpt2_decode_set_logprobs:
  *     the raw model distribution, whatever the sampling settings).
+ *     --speculate-sampled K (1..7, without -g): the same loop under filtered
+ *     sampling (mode 2, with --temperature / --top-k / --top-p or their
+ *     defaults): gpt2_decode_verify_sampled accepts a draft with the
+ *     probability the sampler gives it and resamples at the first rejection;
+ *     the emitted tokens are distributed as token-by-token sampling.
  *     --speculate K (1..7, with -g only): speculative greedy decoding.  Every
  *     pass drafts up to K tokens per sequence with the n-gram drafter
  *     (gpt2_ngram_draft over prompt + output, n-grams of 3 down to 1 tokens)
@@ -97,7 +102,7 @@ static void print_alternatives(Tokenizer* tk, const int* ids, const float* lps, 
 int main(int argc, char** argv) {
     const char *ckpt = NULL, *tok_path = NULL, *tokens_path = NULL, *ids_out = NULL;
     int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
-    int perplexity = 0, logprobs = 0, speculate = 0, top_lp = 0;
+    int perplexity = 0, logprobs = 0, speculate = 0, spec_sampled = 0, top_lp = 0;
     float temperature = 1.0f, top_p = 1.0f;
     int processors = 0, n_ban = 0, ban[HPA_LOGIT_BIAS_MAX];
     float repetition = 1.0f, presence = 0.0f, frequency = 0.0f, ban_value[HPA_LOGIT_BIAS_MAX];
@@ -120,6 +125,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--top-k")) { top_k = atoi(v); filtered = 1; }
         else if (!strcmp(a, "--top-p")) { top_p = (float)atof(v); filtered = 1; }
         else if (!strcmp(a, "--speculate")) speculate = atoi(v);
+        else if (!strcmp(a, "--speculate-sampled")) { speculate = atoi(v); spec_sampled = filtered = 1; }
         else if (!strcmp(a, "--top-logprobs")) {
             top_lp = atoi(v);
             if (top_lp < 1 || top_lp > HPA_TOP_LOGPROBS_MAX) {
@@ -144,7 +150,11 @@ int main(int argc, char** argv) {
             fprintf(stderr, "--speculate takes 1..%d drafts\n", HPA_VERIFY_MAX_ROWS - 1);
             return 2;
         }
-        if (!greedy || filtered || logprobs || top_lp) {
+        if (spec_sampled && greedy) {
+            fprintf(stderr, "--speculate-sampled samples (mode 2): not with -g (--speculate is the greedy pass)\n");
+            return 2;
+        }
+        if (!spec_sampled && (!greedy || filtered || logprobs || top_lp)) {
             fprintf(stderr, "--speculate is greedy only: give -g, and none of --temperature, --top-k, --top-p, "
                             "--logprobs, --top-logprobs\n");
             return 2;
@@ -292,7 +302,9 @@ int main(int argc, char** argv) {
                 live++;
             }
             if (!live) break;
-            if (gpt2_decode_verify(&model, drafts, n_draft, n_acc, out, NULL)) return 1;
+            if (spec_sampled ? gpt2_decode_verify_sampled(&model, drafts, n_draft, n_acc, out, NULL)
+                             : gpt2_decode_verify(&model, drafts, n_draft, n_acc, out, NULL))
+                return 1;
             spec_passes++;
             spec_live += live;
             for (int b = 0; b < B; b++) {

@@ -693,6 +693,51 @@ int hpa_sample_final_serial(const float* logits, int B, int V, unsigned long lon
 int hpa_sample_filtered(const float* logits, int B, int V, const float* temperature, const int* top_k,
                         const float* top_p, unsigned long long* state, int* next, int* tokens, int* pos,
                         const int* active, int* n_kept, float* cut);
+/* hpa_sample_filtered with one id per row taken out of the draw: exclude ([B],
+ * nullable; -1 or any id outside [0, V): none).  The filter (kept set, n_kept,
+ * cut) is decided exactly as above; then exclude[b], if kept, is removed and the
+ * draw walks the remaining kept tokens in index order against the total
+ * w_total - w_excluded (the same fixed-point masses, the same single coin).  An
+ * exclusion that would empty the set is dropped (the excluded id is then the
+ * only id left to return); greedy rows ignore it.  n_kept / cut report the
+ * filter, not the removal.  With exclude NULL or -1 everywhere every output
+ * (ids, states, n_kept, cut) is hpa_sample_filtered's bit for bit;
+ * hpa_sample_filtered is this call with NULL. */
+int hpa_sample_filtered_ex(const float* logits, int B, int V, const float* temperature, const int* top_k,
+                           const float* top_p, unsigned long long* state, int* next, int* tokens, int* pos,
+                           const int* active, int* n_kept, float* cut, const int* exclude);
+/* The filter alone, for R rows at once, and the mass it gives one id per row:
+ * no coin, no state, no draw.  Row r (logits [R][V], rows 4-byte aligned) reads
+ * the settings of sequence seq[r] (seq NULL: of sequence r) from the arrays
+ * hpa_sample_filtered reads, sanitised the same way, and runs the same passes
+ * (one workgroup per row).  Outputs, [R] each:
+ *   n_kept, cut  (nullable) hpa_sample_filtered's for that row and settings, bit for bit
+ *   w_total      the kept set's fixed-point mass, the total the draw divides by
+ *   w_target     the fixed-point mass of target[r] in the draw: 0 when it is
+ *                outside the kept set (a tie at the cut that is not kept, an id
+ *                below the cut, an id outside [0, V))
+ * so p(target) = w_target / w_total, and a coin u = j / 2^24 lies below it iff
+ * w_target * 2^24 > w_total * j.  A temperature-0 row reports (w_target,
+ * w_total) = (1, 1) when target[r] is the lowest-index argmax and (0, 1)
+ * otherwise.  Integer sums: a launch repeats bit for bit. */
+int hpa_sample_filtered_prob(const float* logits, int R, int V, const int* seq, const float* temperature,
+                             const int* top_k, const float* top_p, const int* target, int* n_kept, float* cut,
+                             unsigned long long* w_target, unsigned long long* w_total);
+/* The accept / reject walk of speculative sampling with point-mass drafts, one
+ * thread per sequence.  Sequence b has len[b] rows (row 0 its pending id, then
+ * len[b] - 1 drafts drafts[draft0[b] ..]); w_target / w_total [draft0[b] + i]
+ * are hpa_sample_filtered_prob's masses of draft i under the row before it.
+ * For i = 0, 1, ..: one coin j = xorshift_u32(state[b]) >> 8; draft i is
+ * accepted iff w_target * 2^24 > w_total * j (128-bit integers); the walk stops
+ * at the first rejection.  a = the number accepted:
+ *   n_accepted[b] = a; cont_row[b] = row0[b] + a; pos[b] = start[b] + a;
+ *   exclude[b] = the rejected draft, -1 when every draft was accepted.
+ * state[b] has then advanced once per examined draft (the pick that follows
+ * advances it once more).  len[b] == 0: n_accepted = cont_row = exclude = -1,
+ * state and pos untouched. */
+int hpa_spec_accept(const unsigned long long* w_target, const unsigned long long* w_total, const int* drafts,
+                    const int* draft0, const int* start, const int* row0, const int* len, int B,
+                    unsigned long long* state, int* n_accepted, int* cont_row, int* exclude, int* pos);
 /* ---------------- logit processors (hpa_process.hip) ----------------
  * Repetition, presence and frequency penalties and a sparse logit bias, per
  * row, from the raw logits [B][V] and a dense count table counts [B][V]

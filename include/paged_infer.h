@@ -234,7 +234,7 @@ int  gpt2_decode_set_score_chunk(GPT2* model, int rows);
  * Eviction and shared pages as in gpt2_decode_prefill_ragged.  Eager and
  * host-synchronous like the prefill; a captured decode graph stays valid.
  * Refused (message, nonzero, nothing changed): a sampling mode other than 0
- * (rejection sampling is not implemented), n_draft out of range, a draft id
+ * (gpt2_decode_verify_sampled is the pass for mode 2), n_draft out of range, a draft id
  * outside [0, vocab_size), pos[b] + n_draft[b] + 1 > max_ctx, no engine.
  * The pending id must be valid: for a fresh slot or a fork of a shorter
  * prefix it is not, and that is the caller's responsibility, as with
@@ -251,6 +251,44 @@ int  gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int*
 int  gpt2_decode_verify_plan(int max_rows, int kv_dtype, int page_size, int head_size, int request);
 /* the request gpt2_decode_verify passes to the plan (default 0) */
 int  gpt2_decode_set_verify_attention(GPT2* model, int request);
+/* Speculative sampling: gpt2_decode_verify under sampling mode 2 (per-sequence
+ * temperature / top-k / top-p).  Arguments, row layout, page growth, eviction,
+ * trace arming, out_tokens layout and position bookkeeping are
+ * gpt2_decode_verify's.  Drafts are point-mass proposals (exact for a
+ * deterministic drafter: gpt2_ngram_draft, a greedy draft model; a sampled
+ * draft model's own distribution q is not taken).  With p_i the distribution
+ * mode 2 draws from at row i (hpa_sample_filtered's kept set and masses under
+ * b's settings) and d_{i+1} the draft after it, rows are examined in order:
+ *   - one coin u = j / 2^24 from b's stream; d_{i+1} is accepted iff
+ *     u < p_i(d_{i+1}), the integer test w_target * 2^24 > w_total * j
+ *     (a draft outside the kept set is always rejected, a draft that is the
+ *     whole kept set always accepted);
+ *   - at the first rejection, at row a, b's own token is drawn from p_a with
+ *     d_{a+1} removed and the rest renormalised (hpa_sample_filtered_ex), with
+ *     one more coin;
+ *   - with every draft accepted the own token is a plain mode-2 draw from the
+ *     last row.
+ * The emitted tokens are distributed exactly as token-by-token mode-2 sampling.
+ * A temperature-0 sequence is greedy (accepts iff the draft is the argmax); its
+ * coins are still drawn.  b's sampler state advances examined + 1 times,
+ * examined = the drafted rows up to and including the first rejection; an
+ * untouched sequence advances nothing.
+ * The pass: hpa_verify_rows, the layers with gpt2_decode_verify_plan's
+ * attention kernel, then the drafted rows through the dense route in chunks of
+ * gpt2_decode_set_score_chunk rows (default 256): one LOGITS GEMM into
+ * gpt2_decode_score_top's [chunk][V] workspace and one
+ * hpa_sample_filtered_prob with the drafts as targets; hpa_spec_accept; then
+ * the verify pass's tail (gather, logits GEMM, pick, log-probabilities as set).
+ *   draft_probs (nullable, stride HPA_VERIFY_MAX_ROWS): entry i < n_draft[b] =
+ *     (float)((double)w_target / w_total) of drafted row i, for every drafted
+ *     row, examined or not.
+ * Refused (message, nonzero, nothing changed, sampler states included): a
+ * sampling mode other than 2 (mode 0: gpt2_decode_verify; mode 1's order-exact
+ * float sampler has no integer masses), logit processors on, and everything
+ * gpt2_decode_verify refuses.  Buffers are allocated on first use and freed
+ * with the engine. */
+int  gpt2_decode_verify_sampled(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
+                                float* draft_probs);
 /* n-gram (prompt-lookup) drafter, host only (no device, allocation or I/O):
  * for g from max_ngram down to min_ngram, the most recent earlier occurrence
  * of the last g tokens of history[0..n) that has at least one token after it;

@@ -23,6 +23,15 @@
 // any order: two launches on the same inputs return the same ids, and the
 // cdf test  running / total > u  is the integer test  running * 2^24 > total * j
 // (u = j / 2^24).  The quantisation is below 2^-41 of the total per term.
+//
+// Speculative sampling (gpt2_decode_verify_sampled) is built from the same
+// passes, factored into device functions (sf_filter, sf_parts, sf_total,
+// sf_id_mass): hpa_sample_filtered_prob runs the filter for many rows and
+// reports the kept total and one id's mass, without coin or draw;
+// hpa_sample_filtered_ex is the sampler with one id taken out of the kept set
+// before the draw (hpa_sample_filtered: the instantiation without it);
+// hpa_spec_accept walks a sequence's drafted rows, one coin each, and accepts
+// while  w_target * 2^24 > w_total * j.
 #include <limits.h>
 #include <math.h>
 
@@ -40,6 +49,7 @@ struct SfShared {
     float red_max[kSfWaves], red_min[kSfWaves];
     int red_arg[kSfWaves];
     unsigned seg_ties[kSfSegs];
+    unsigned seg_tlt[kSfSegs];  // ties below the singled-out id (sf_parts<true>)
     u64 seg_mass[kSfSegs];
     unsigned digit, bin_count, c_above;
     u64 m_above, target;
@@ -257,32 +267,30 @@ __device__ __forceinline__ unsigned sf_descend(SfShared& sh, const SfRow& r, boo
     return prefix;
 }
 
-__global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
-    const float* __restrict__ logits, int V, const float* __restrict__ temperature, const int* __restrict__ top_k,
-    const float* __restrict__ top_p, unsigned long long* __restrict__ state, int* __restrict__ next,
-    int* __restrict__ tokens, int* __restrict__ pos, const int* __restrict__ active, int* __restrict__ n_kept,
-    float* __restrict__ cut_out, int shift) {
-    __shared__ SfShared sh;
-    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
-    if (active && active[b] <= 0) return;  // row left as it is (its RNG state too)
-    SfRow r;
-    r.lg = logits + (size_t)b * V;
+__device__ __forceinline__ void sf_row_init(SfRow& r, const float* lg, int V, int shift) {
+    r.lg = lg;
     r.V = V;
     r.head = min(V, (int)((4u - (unsigned)(((size_t)r.lg >> 2) & 3u)) & 3u));
     r.nq = (V - r.head) >> 2;
     r.tail0 = r.head + 4 * r.nq;
     r.scale = (float)(1ull << shift);
+}
 
-    // per-row parameters, sanitised so that nothing below can leave the row
-    float T = temperature[b];
+// per-row parameters, sanitised so that nothing below can leave the row
+__device__ __forceinline__ void sf_settings(float& T, int& k, float& P) {
     if (!(T >= 0.f) || isinf(T)) T = 1.f;
-    int k = top_k[b];
     if (k < 0) k = 0;
-    float P = top_p[b];
     if (!(P > 0.f && P <= 1.f)) P = 1.f;
-    unsigned long long st = state[b];
-    const u64 coin = hpa::xorshift_u32(st) >> 8;  // u = coin / 2^24
+}
 
+// The filter of one row, every thread of the workgroup: pass 1 and the radix
+// descents.  Sets r.mx and r.c; am: the lowest-index argmax.  Returns false
+// for a greedy row (T == 0: nothing after pass 1); else the cut: its value,
+// the ties kept at it and the kept count n.  Resets sh.pick and sh.cut_bits.
+__device__ __forceinline__ bool sf_filter(SfShared& sh, SfRow& r, float T, int k, float P, int& am_out, float& cutv,
+                                          unsigned& ties_kept, unsigned& n) {
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int V = r.V;
     // pass 1: max (lowest index on ties) and min
     float mx = -INFINITY, mn = INFINITY;
     int am = INT_MAX;
@@ -328,18 +336,8 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
     if (am < 0 || am >= V) am = 0;  // a row of NaNs
     r.mx = mx;
     r.c = T > 0.f ? fminf(1.44269504f / T, 3.0e38f) : 0.f;  // finite: 0 * c stays 0 for the maximum
-
-    if (T == 0.f) {  // greedy row: the coin is drawn and dropped
-        if (t == 0) {
-            state[b] = st;
-            next[b] = am;
-            if (tokens) tokens[b] = am;
-            if (pos) pos[b] += 1;
-            if (n_kept) n_kept[b] = 1;
-            if (cut_out) cut_out[b] = r.lg[am];
-        }
-        return;
-    }
+    am_out = am;
+    if (T == 0.f) return false;
 
     // the cut: (cut key, n kept, ties kept at the cut)
     const bool haveK = k > 0 && k < V, haveP = P < 1.f;
@@ -349,8 +347,6 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
         Kk = sf_descend<false>(sh, r, false, 0u, 0u, (unsigned)k, 1.f, c_gt, m_gt, bin, target);
         tieK = (unsigned)k - c_gt;
     }
-    float cutv;
-    unsigned ties_kept, n;
     if (haveP) {
         const unsigned Kp = sf_descend<true>(sh, r, haveK, Kk, tieK, 0u, P, c_gt, m_gt, bin, target);
         cutv = sf_unkey(Kp);
@@ -370,68 +366,156 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
         ties_kept = (unsigned)V;
         n = (unsigned)V;
     }
-    const u64 wcut = r.w(cutv);
+    return true;
+}
 
-    // draw, stage 1: ties and mass above the cut of every part, in index order:
-    // part 0 the head scalars, part 1 + w the float4s of wave w, last the tail
+// Ties and mass above the cut of every part of the row, in index order: part 0
+// the head scalars, part 1 + w the float4s of wave w, last the tail.  EX: also
+// the ties at an index below e (the tie rank of one singled-out id).  The
+// caller synchronises before it reads sh.seg_*.
+template <bool EX>
+__device__ __forceinline__ void sf_parts(SfShared& sh, const SfRow& r, float cutv, int e) {
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int Q = (r.nq + kSfWaves - 1) / kSfWaves;
     const int qlo = min(r.nq, w * Q), qhi = min(r.nq, qlo + Q);
-    {
-        unsigned ties = 0;
-        u64 mass = 0;
-        const float4* q4 = r.q4();
-        for (int q0 = qlo; q0 < qhi; q0 += 64 * kSfLoads) {
-            float4 v4[kSfLoads];
-            sf_load(q4, q0 + lane, 64, qhi, v4);
+    unsigned ties = 0, tlt = 0;
+    u64 mass = 0;
+    const float4* q4 = r.q4();
+    for (int q0 = qlo; q0 < qhi; q0 += 64 * kSfLoads) {
+        float4 v4[kSfLoads];
+        sf_load(q4, q0 + lane, 64, qhi, v4);
 #pragma unroll
-            for (int u = 0; u < kSfLoads; ++u) {
-                if (q0 + lane + 64 * u < qhi) {
-                    const float4 v = v4[u];
-                    const float x[4] = {v.x + 0.f, v.y + 0.f, v.z + 0.f, v.w + 0.f};
+        for (int u = 0; u < kSfLoads; ++u) {
+            if (q0 + lane + 64 * u < qhi) {
+                const float4 v = v4[u];
+                const float x[4] = {v.x + 0.f, v.y + 0.f, v.z + 0.f, v.w + 0.f};
 #pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        if (x[c] > cutv) mass += r.w(x[c]);
-                        ties += x[c] == cutv;
-                    }
+                for (int c = 0; c < 4; ++c) {
+                    if (x[c] > cutv) mass += r.w(x[c]);
+                    ties += x[c] == cutv;
+                    if (EX) tlt += x[c] == cutv && r.head + 4 * (q0 + lane + 64 * u) + c < e;
                 }
-            }
-        }
-        ties = wave_sum_u32(ties);
-        mass = wave_sum_u64(mass);
-        if (lane == 0) {
-            sh.seg_ties[1 + w] = ties;
-            sh.seg_mass[1 + w] = mass;
-        }
-        if (t == 0) {
-            for (int s = 0; s < 2; ++s) {
-                const int lo = s ? r.tail0 : 0, hi = s ? V : r.head;
-                unsigned tc = 0;
-                u64 mc = 0;
-                for (int i = lo; i < hi; ++i) {
-                    const float x = r.lg[i] + 0.f;
-                    if (x > cutv) mc += r.w(x);
-                    tc += x == cutv;
-                }
-                sh.seg_ties[s ? kSfSegs - 1 : 0] = tc;
-                sh.seg_mass[s ? kSfSegs - 1 : 0] = mc;
             }
         }
     }
+    ties = wave_sum_u32(ties);
+    mass = wave_sum_u64(mass);
+    if (EX) tlt = wave_sum_u32(tlt);
+    if (lane == 0) {
+        sh.seg_ties[1 + w] = ties;
+        sh.seg_mass[1 + w] = mass;
+        if (EX) sh.seg_tlt[1 + w] = tlt;
+    }
+    if (t == 0) {
+        for (int s = 0; s < 2; ++s) {
+            const int lo = s ? r.tail0 : 0, hi = s ? r.V : r.head;
+            unsigned tc = 0, tl = 0;
+            u64 mc = 0;
+            for (int i = lo; i < hi; ++i) {
+                const float x = r.lg[i] + 0.f;
+                if (x > cutv) mc += r.w(x);
+                tc += x == cutv;
+                if (EX) tl += x == cutv && i < e;
+            }
+            sh.seg_ties[s ? kSfSegs - 1 : 0] = tc;
+            sh.seg_mass[s ? kSfSegs - 1 : 0] = mc;
+            if (EX) sh.seg_tlt[s ? kSfSegs - 1 : 0] = tl;
+        }
+    }
+}
+
+// the kept total S and the number jj of ties kept, from the parts (every thread)
+__device__ __forceinline__ u64 sf_total(const SfShared& sh, unsigned ties_kept, u64 wcut, unsigned& jj) {
+    unsigned total_ties = 0;
+    for (int s = 0; s < kSfSegs; ++s) total_ties += sh.seg_ties[s];
+    jj = min(ties_kept, total_ties);
+    u64 S = 0;
+    unsigned tb = 0;
+    for (int s = 0; s < kSfSegs; ++s) {
+        const unsigned ts = sh.seg_ties[s];
+        const unsigned kt = tb >= jj ? 0u : min(ts, jj - tb);
+        S += sh.seg_mass[s] + (u64)kt * wcut;
+        tb += ts;
+    }
+    return S;
+}
+
+// the mass id e (in [0, V)) has in the draw, after sf_parts<true>(.., e): above
+// the cut its own, at the cut wcut if its tie rank is kept, else 0
+__device__ __forceinline__ u64 sf_id_mass(const SfShared& sh, const SfRow& r, float cutv, u64 wcut, unsigned jj, int e) {
+    unsigned tlt = 0;
+    for (int s = 0; s < kSfSegs; ++s) tlt += sh.seg_tlt[s];
+    const float xe = r.lg[e] + 0.f;
+    return xe > cutv ? r.w(xe) : (xe == cutv && tlt < jj) ? wcut : 0;
+}
+
+// the part that holds index e
+__device__ __forceinline__ int sf_seg_of(const SfRow& r, int e) {
+    if (e < r.head) return 0;
+    if (e >= r.tail0) return kSfSegs - 1;
+    const int Q = (r.nq + kSfWaves - 1) / kSfWaves;
+    return 1 + ((e - r.head) >> 2) / Q;
+}
+
+// EX: exclude[b] (nullable, -1: none) is taken out of the kept set before the draw
+template <bool EX>
+__global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
+    const float* __restrict__ logits, int V, const float* __restrict__ temperature, const int* __restrict__ top_k,
+    const float* __restrict__ top_p, unsigned long long* __restrict__ state, int* __restrict__ next,
+    int* __restrict__ tokens, int* __restrict__ pos, const int* __restrict__ active, int* __restrict__ n_kept,
+    float* __restrict__ cut_out, const int* __restrict__ exclude, int shift) {
+    __shared__ SfShared sh;
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
+    if (active && active[b] <= 0) return;  // row left as it is (its RNG state too)
+    SfRow r;
+    sf_row_init(r, logits + (size_t)b * V, V, shift);
+    float T = temperature[b];
+    int k = top_k[b];
+    float P = top_p[b];
+    sf_settings(T, k, P);
+    unsigned long long st = state[b];
+    const u64 coin = hpa::xorshift_u32(st) >> 8;  // u = coin / 2^24
+    int ex = -1;
+    if (EX) {
+        ex = exclude[b];
+        if (ex < 0 || ex >= V) ex = -1;
+    }
+
+    int am;
+    float cutv;
+    unsigned ties_kept, n;
+    if (!sf_filter(sh, r, T, k, P, am, cutv, ties_kept, n)) {  // greedy row: the coin is drawn and dropped
+        if (t == 0) {
+            state[b] = st;
+            next[b] = am;
+            if (tokens) tokens[b] = am;
+            if (pos) pos[b] += 1;
+            if (n_kept) n_kept[b] = 1;
+            if (cut_out) cut_out[b] = r.lg[am];
+        }
+        return;
+    }
+    const u64 wcut = r.w(cutv);
+
+    // draw, stage 1: the parts
+    const int Q = (r.nq + kSfWaves - 1) / kSfWaves;
+    const int qlo = min(r.nq, w * Q), qhi = min(r.nq, qlo + Q);
+    sf_parts<EX>(sh, r, cutv, ex);
     __syncthreads();
     // every thread: the kept total, the coin's threshold, and which part holds
     // the crossing and the last kept tie
-    unsigned total_ties = 0;
-    for (int s = 0; s < kSfSegs; ++s) total_ties += sh.seg_ties[s];
-    const unsigned jj = min(ties_kept, total_ties);
-    u64 S = 0;
-    {
-        unsigned tb = 0;
-        for (int s = 0; s < kSfSegs; ++s) {
-            const unsigned ts = sh.seg_ties[s];
-            const unsigned kt = tb >= jj ? 0u : min(ts, jj - tb);
-            S += sh.seg_mass[s] + (u64)kt * wcut;
-            tb += ts;
-        }
+    unsigned jj;
+    u64 S = sf_total(sh, ties_kept, wcut, jj);
+    // the excluded id's mass leaves its part and the total; an exclusion that
+    // would leave nothing (or that removes nothing) is dropped
+    u64 wex = 0;
+    int exseg = -1;
+    if (EX && ex >= 0) {
+        wex = sf_id_mass(sh, r, cutv, wcut, jj, ex);
+        if (wex >= S) wex = 0;
+        if (wex == 0) ex = -1;
+        else exseg = sf_seg_of(r, ex);
+        S -= wex;
     }
     // running / S > u  <=>  running > floor(S * coin / 2^24)
     const u64 thr = (__umul64hi(S, coin) << 40) | ((S * coin) >> 24);
@@ -445,7 +529,8 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
         for (int s = 0; s < kSfSegs; ++s) {
             const unsigned ts = sh.seg_ties[s];
             const unsigned kt = tb >= jj ? 0u : min(ts, jj - tb);
-            const u64 ms = sh.seg_mass[s] + (u64)kt * wcut;
+            u64 ms = sh.seg_mass[s] + (u64)kt * wcut;
+            if (EX && s == exseg) ms -= wex;
             if (cross_seg < 0 && mb + ms > thr) cross_seg = s;
             if (jj > 0 && tb <= jj - 1 && jj - 1 < tb + ts) tie_seg = s;
             if (s == 1 + w) {
@@ -499,6 +584,7 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
                     if (want_bits && rank == jj - 1) sh.cut_bits = raw[c];
                     ++rank;
                 }
+                if (EX && r.head + 4 * q + c == ex) mw[c] = 0;
                 ml += mw[c];
             }
             u64 mi = ml;  // inclusive scan of the kept mass
@@ -530,6 +616,7 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
                 const unsigned ts = sh.seg_ties[q];
                 const unsigned kt = tb >= jj ? 0u : min(ts, jj - tb);
                 mb += sh.seg_mass[q] + (u64)kt * wcut;
+                if (EX && q == exseg) mb -= wex;
                 tb += ts;
             }
             const int lo = s ? r.tail0 : 0, hi = s ? V : r.head;
@@ -542,6 +629,7 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
                     if (want_bits && tb == jj - 1) sh.cut_bits = __float_as_uint(xr);
                     ++tb;
                 }
+                if (EX && i == ex) mw = 0;
                 if (mb <= thr && mb + mw > thr) sh.pick = i;
                 mb += mw;
             }
@@ -561,18 +649,208 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
         if (cut_out) cut_out[b] = want_bits ? __uint_as_float(sh.cut_bits) : cutv;
     }
 }
+
+// the raw bits of the last kept tie (rank jj - 1 in index order) into
+// sh.cut_bits: the stage-2 tie scan without the draw (the caller synchronises)
+__device__ __forceinline__ void sf_cut_bits(SfShared& sh, const SfRow& r, float cutv, unsigned jj) {
+    if (jj == 0) return;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    int tie_seg = -1;
+    unsigned seg_tb = 0;
+    {
+        unsigned tb = 0;
+        for (int s = 0; s < kSfSegs; ++s) {
+            const unsigned ts = sh.seg_ties[s];
+            if (tb <= jj - 1 && jj - 1 < tb + ts) {
+                tie_seg = s;
+                seg_tb = tb;
+            }
+            tb += ts;
+        }
+    }
+    if (tie_seg == 1 + w) {
+        const int Q = (r.nq + kSfWaves - 1) / kSfWaves;
+        const int qlo = min(r.nq, w * Q), qhi = min(r.nq, qlo + Q);
+        const float4* q4 = r.q4();
+        unsigned tb = seg_tb;
+        for (int q0 = qlo; q0 < qhi; q0 += 64) {  // wave-uniform, in index order
+            const int q = q0 + lane;
+            const bool ok = q < qhi;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ok) v = q4[q];
+            const unsigned raw[4] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z),
+                                     __float_as_uint(v.w)};
+            const float x[4] = {v.x + 0.f, v.y + 0.f, v.z + 0.f, v.w + 0.f};
+            unsigned tc = 0;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) tc += ok && x[c] == cutv;
+            unsigned ti = tc;  // inclusive scan of the tie counts
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const unsigned u = __shfl_up(ti, o, 64);
+                if (lane >= o) ti += u;
+            }
+            unsigned rank = tb + ti - tc;
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                if (ok && x[c] == cutv) {
+                    if (rank == jj - 1) sh.cut_bits = raw[c];
+                    ++rank;
+                }
+            }
+            tb += __shfl(ti, 63, 64);
+        }
+    }
+    if (t == 0 && (tie_seg == 0 || tie_seg == kSfSegs - 1)) {
+        const int lo = tie_seg ? r.tail0 : 0, hi = tie_seg ? r.V : r.head;
+        unsigned tb = seg_tb;
+        for (int i = lo; i < hi; ++i) {
+            const float xr = r.lg[i];
+            if (xr + 0.f == cutv) {
+                if (tb == jj - 1) sh.cut_bits = __float_as_uint(xr);
+                ++tb;
+            }
+        }
+    }
+}
+
+// The filter of R rows and the mass of one id per row: sample_filtered_kernel
+// up to the kept total, without coin, state or draw.
+__global__ __launch_bounds__(kSfThreads) void sample_filtered_prob_kernel(
+    const float* __restrict__ logits, int V, const int* __restrict__ seq, const float* __restrict__ temperature,
+    const int* __restrict__ top_k, const float* __restrict__ top_p, const int* __restrict__ target,
+    int* __restrict__ n_kept, float* __restrict__ cut_out, unsigned long long* __restrict__ w_target,
+    unsigned long long* __restrict__ w_total, int shift) {
+    __shared__ SfShared sh;
+    const int row = blockIdx.x, t = threadIdx.x;
+    const int b = seq ? seq[row] : row;
+    SfRow r;
+    sf_row_init(r, logits + (size_t)row * V, V, shift);
+    float T = temperature[b];
+    int k = top_k[b];
+    float P = top_p[b];
+    sf_settings(T, k, P);
+    int d = target[row];
+    if (d < 0 || d >= V) d = -1;
+
+    int am;
+    float cutv;
+    unsigned ties_kept, n;
+    if (!sf_filter(sh, r, T, k, P, am, cutv, ties_kept, n)) {  // greedy row: a point mass at the argmax
+        if (t == 0) {
+            if (n_kept) n_kept[row] = 1;
+            if (cut_out) cut_out[row] = r.lg[am];
+            w_target[row] = d == am ? 1ull : 0ull;
+            w_total[row] = 1ull;
+        }
+        return;
+    }
+    const u64 wcut = r.w(cutv);
+    sf_parts<true>(sh, r, cutv, d);
+    __syncthreads();
+    unsigned jj;
+    const u64 S = sf_total(sh, ties_kept, wcut, jj);
+    const bool want_bits = cut_out && cutv == 0.f;  // the only value with two encodings
+    if (want_bits) {
+        sf_cut_bits(sh, r, cutv, jj);
+        __syncthreads();
+    }
+    if (t == 0) {
+        if (n_kept) n_kept[row] = (int)n;
+        if (cut_out) cut_out[row] = want_bits ? __uint_as_float(sh.cut_bits) : cutv;
+        w_target[row] = d >= 0 ? sf_id_mass(sh, r, cutv, wcut, jj, d) : 0ull;
+        w_total[row] = S;
+    }
+}
+
+// The accept walk of speculative sampling, one thread per sequence (plain
+// integer arithmetic: the products are compared as 128-bit numbers).
+__global__ __launch_bounds__(64) void spec_accept_kernel(
+    const unsigned long long* __restrict__ w_target, const unsigned long long* __restrict__ w_total,
+    const int* __restrict__ drafts, const int* __restrict__ draft0, const int* __restrict__ start,
+    const int* __restrict__ row0, const int* __restrict__ len, int B, unsigned long long* __restrict__ state,
+    int* __restrict__ n_accepted, int* __restrict__ cont_row, int* __restrict__ exclude, int* __restrict__ pos) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    const int n = len[b];
+    if (n <= 0) {  // untouched: state and position left as they are
+        n_accepted[b] = -1;
+        cont_row[b] = -1;
+        exclude[b] = -1;
+        return;
+    }
+    const int d0 = draft0[b];
+    unsigned long long st = state[b];
+    int a = 0, rejected = -1;
+    while (a + 1 < n) {
+        const u64 j = hpa::xorshift_u32(st) >> 8;  // u = j / 2^24
+        const u64 wt = w_target[d0 + a], ws = w_total[d0 + a];
+        // wt * 2^24 > ws * j
+        const u64 lhi = wt >> 40, llo = wt << 24;
+        const u64 rhi = __umul64hi(ws, j), rlo = ws * j;
+        if (!(lhi > rhi || (lhi == rhi && llo > rlo))) {
+            rejected = drafts[d0 + a];
+            break;
+        }
+        ++a;
+    }
+    state[b] = st;
+    n_accepted[b] = a;
+    cont_row[b] = row0[b] + a;
+    exclude[b] = rejected;
+    pos[b] = start[b] + a;
+}
+
+// V masses of at most 2^shift sum below 2^62
+int sf_shift(int V) {
+    int lg = 0;  // ceil(log2 V)
+    while ((1ll << lg) < (long long)V) ++lg;
+    return 62 - lg < 44 ? 62 - lg : 44;
+}
 }  // namespace
+
+int hpa_sample_filtered_ex(const float* logits, int B, int V, const float* temperature, const int* top_k,
+                           const float* top_p, unsigned long long* state, int* next, int* tokens, int* pos,
+                           const int* active, int* n_kept, float* cut, const int* exclude) {
+    HPA_REQUIRE(logits && temperature && top_k && top_p && state && next && B > 0 && V > 0,
+                "sample_filtered: bad arguments");
+    const int shift = sf_shift(V);
+    if (exclude)
+        sample_filtered_kernel<true><<<B, kSfThreads, 0, hpa_stream()>>>(
+            logits, V, temperature, top_k, top_p, state, next, tokens, pos, active, n_kept, cut, exclude, shift);
+    else
+        sample_filtered_kernel<false><<<B, kSfThreads, 0, hpa_stream()>>>(
+            logits, V, temperature, top_k, top_p, state, next, tokens, pos, active, n_kept, cut, nullptr, shift);
+    HPA_LAUNCH_CHECK();
+    return 0;
+}
 
 int hpa_sample_filtered(const float* logits, int B, int V, const float* temperature, const int* top_k,
                         const float* top_p, unsigned long long* state, int* next, int* tokens, int* pos,
                         const int* active, int* n_kept, float* cut) {
-    HPA_REQUIRE(logits && temperature && top_k && top_p && state && next && B > 0 && V > 0,
-                "sample_filtered: bad arguments");
-    int lg = 0;  // ceil(log2 V)
-    while ((1ll << lg) < (long long)V) ++lg;
-    const int shift = 62 - lg < 44 ? 62 - lg : 44;  // V masses of at most 2^shift sum below 2^62
-    sample_filtered_kernel<<<B, kSfThreads, 0, hpa_stream()>>>(logits, V, temperature, top_k, top_p, state, next,
-                                                               tokens, pos, active, n_kept, cut, shift);
+    return hpa_sample_filtered_ex(logits, B, V, temperature, top_k, top_p, state, next, tokens, pos, active, n_kept,
+                                  cut, NULL);
+}
+
+int hpa_sample_filtered_prob(const float* logits, int R, int V, const int* seq, const float* temperature,
+                             const int* top_k, const float* top_p, const int* target, int* n_kept, float* cut,
+                             unsigned long long* w_target, unsigned long long* w_total) {
+    HPA_REQUIRE(logits && temperature && top_k && top_p && target && w_target && w_total && R > 0 && V > 0,
+                "sample_filtered_prob: bad arguments");
+    sample_filtered_prob_kernel<<<R, kSfThreads, 0, hpa_stream()>>>(logits, V, seq, temperature, top_k, top_p, target,
+                                                                    n_kept, cut, w_target, w_total, sf_shift(V));
+    HPA_LAUNCH_CHECK();
+    return 0;
+}
+
+int hpa_spec_accept(const unsigned long long* w_target, const unsigned long long* w_total, const int* drafts,
+                    const int* draft0, const int* start, const int* row0, const int* len, int B,
+                    unsigned long long* state, int* n_accepted, int* cont_row, int* exclude, int* pos) {
+    HPA_REQUIRE(w_target && w_total && drafts && draft0 && start && row0 && len && state && n_accepted && cont_row &&
+                    exclude && pos && B > 0,
+                "spec accept: bad arguments");
+    spec_accept_kernel<<<(unsigned)((B + 63) / 64), 64, 0, hpa_stream()>>>(
+        w_target, w_total, drafts, draft0, start, row0, len, B, state, n_accepted, cont_row, exclude, pos);
     HPA_LAUNCH_CHECK();
     return 0;
 }

@@ -750,6 +750,13 @@ struct GPT2Decode {
     int* vf_int;
     float* vf_lp;
     int* h_vf;
+    /* speculative sampling (gpt2_decode_verify_sampled), allocated on first use,
+     * indexed by drafted row (draft0[b] + i): sp_w = w_target, w_total
+     * [2][B * (MR - 1)]; sp_i = the rows' sequences [B * (MR - 1)], then exclude
+     * [B]; h_sp_w the host copy of sp_w */
+    unsigned long long* sp_w;
+    int* sp_i;
+    unsigned long long* h_sp_w;
     /* logit processors (gpt2_decode_set_processors).  The settings' host
      * mirrors exist from gpt2_decode_init on (they may be set while off); the
      * device tables are allocated on first enable: the fed tokens pr_hist
@@ -846,6 +853,9 @@ static void dec_verify_free(GPT2Decode* d) {
     hpa_free(d->vf_int); hpa_free(d->vf_lp);
     free(d->h_vf);
     d->vf_int = NULL; d->vf_lp = NULL; d->h_vf = NULL;
+    hpa_free(d->sp_w); hpa_free(d->sp_i);
+    free(d->h_sp_w);
+    d->sp_w = NULL; d->sp_i = NULL; d->h_sp_w = NULL;
 }
 
 static void dec_shard_free(GPT2Decode* d) {
@@ -1770,7 +1780,7 @@ static int dec_gemm(GPT2* model, int l, int which) {
 
 /* greedy or sampled next token; active (nullable): rows with active[b] <= 0
  * are left untouched */
-static int dec_pick_ids(GPT2* model, const int* active) {
+static int dec_pick_ids(GPT2* model, const int* active, const int* exclude) {
     GPT2Decode* d = model->decode;
     const int V = model->config.vocab_size;
     const float* lg = d->d_logits;
@@ -1784,8 +1794,8 @@ static int dec_pick_ids(GPT2* model, const int* active) {
         lg = d->pr_logits;
     }
     if (d->sample == 2)
-        return hpa_sample_filtered(lg, d->B, V, d->d_samp_t, d->d_samp_k, d->d_samp_p, d->d_rng, d->d_next,
-                                   d->d_tokens, d->d_pos, active, NULL, NULL);
+        return hpa_sample_filtered_ex(lg, d->B, V, d->d_samp_t, d->d_samp_k, d->d_samp_p, d->d_rng, d->d_next,
+                                      d->d_tokens, d->d_pos, active, NULL, NULL, exclude);
     if (d->sample)
         return hpa_sample_final(lg, d->B, V, d->d_rng, d->d_next, d->d_tokens, d->d_pos, active);
     HpaFusedGemm g;
@@ -1799,9 +1809,9 @@ static int dec_pick_ids(GPT2* model, const int* active) {
  * log-probabilities (the pick has advanced pos and written d_next; the
  * log-probability kernel reads d_logits and d_next only); with
  * gpt2_decode_set_top_logprobs on, the raw rows' k best columns */
-static int dec_pick(GPT2* model, const int* active) {
+static int dec_pick_ex(GPT2* model, const int* active, const int* exclude) {
     GPT2Decode* d = model->decode;
-    int rc = dec_pick_ids(model, active);
+    int rc = dec_pick_ids(model, active, exclude);
     if (d->logprobs && !rc)
         rc = hpa_logprob_rows(d->d_logits, d->B, model->config.vocab_size, d->d_next, active, d->d_lp);
     if (d->top_k && !rc)
@@ -1809,6 +1819,8 @@ static int dec_pick(GPT2* model, const int* active) {
                                  d->d_top_lps, NULL, NULL, d->d_top_ws, d->top_ws_bytes, 0);
     return rc;
 }
+
+static int dec_pick(GPT2* model, const int* active) { return dec_pick_ex(model, active, NULL); }
 
 /* one decode-attention launch: the (sequence, head, context range) grid,
  * frag output */
@@ -2889,11 +2901,70 @@ int gpt2_decode_set_verify_attention(GPT2* model, int request) {
     return 0;
 }
 
+/* the drafted rows' masses under mode 2 (gpt2_decode_verify_sampled): the dense
+ * route of dec_score_top_rows over the ND drafted rows only, in chunks: gather,
+ * one LOGITS GEMM into the [chunk][V] workspace, one hpa_sample_filtered_prob
+ * with the drafts as targets.  Drafted row draft0[b] + i is packed row
+ * row0[b] + i; hrow0 / hlen: the host row tables */
+static int dec_spec_rows(GPT2* model, int R, int ND, const int* hrow0, const int* hlen, const int* v_drafts) {
+    GPT2Decode* d = model->decode;
+    const GPT2Config c = model->config;
+    const int B = d->B, C = c.channels, V = c.vocab_size;
+    const int Rp = (R + 15) / 16 * 16, NDp = (ND + 15) / 16 * 16;
+    int chunk = d->sc_chunk ? d->sc_chunk : DEC_SCORE_TOP_CHUNK;
+    if (chunk > NDp) chunk = NDp;
+    if (dec_score_reserve(model, chunk) || dec_score_top_reserve(model, chunk)) return 1;
+    int* hrows = (int*)malloc(2 * (size_t)ND * sizeof(int));
+    if (!hrows) return 1;
+    int* hseq = hrows + ND;
+    int nd = 0;
+    for (int b = 0; b < B; b++)
+        for (int i = 0; i + 1 < hlen[b]; i++, nd++) {
+            hrows[nd] = hrow0[b] + i;
+            hseq[nd] = b;
+        }
+    int rc = hpa_memcpy(d->sp_i, hseq, (size_t)ND * sizeof(int));
+    unsigned long long *w_target = d->sp_w, *w_total = d->sp_w + (size_t)B * (HPA_VERIFY_MAX_ROWS - 1);
+    for (int r0 = 0; r0 < ND && !rc; r0 += chunk) {
+        const int n = ND - r0 < chunk ? ND - r0 : chunk, np = (n + 15) / 16 * 16;
+        rc |= hpa_memcpy(d->sc_rows, hrows + r0, n * sizeof(int));
+        rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->sc_rows, n, d->sc_x, d->sc_st, np, C);
+        HpaFusedGemm g;
+        memset(&g, 0, sizeof(g));
+        g.M = n;
+        g.w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
+        g.epilogue = HPA_FEPI_LOGITS;
+        g.x = d->sc_x;
+        g.K = C;
+        g.ln_stats = d->sc_st;
+        g.ln_ntiles = C / 16;
+        g.ln_w = model->params.lnfw;
+        g.ln_b = model->params.lnfb;
+        g.w = wpack_at(d, d->wpack_off[4]);
+        g.N = V;
+        g.out = d->st_logits;
+        g.part_out = d->sc_part; /* not read (dec_score_top_rows) */
+        rc |= hpa_gemm_fused(&g);
+        if (!rc)
+            rc |= hpa_sample_filtered_prob(d->st_logits, n, V, d->sp_i + r0, d->d_samp_t, d->d_samp_k, d->d_samp_p,
+                                           v_drafts + r0, NULL, NULL, w_target + r0, w_total + r0);
+    }
+    free(hrows);
+    return rc;
+}
+
+/* sampled: gpt2_decode_verify_sampled (draft_out: the drafts' probabilities);
+ * else gpt2_decode_verify (draft_out: their raw log-probabilities) */
 static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
-                            float* draft_logprobs) {
+                            float* draft_logprobs, int sampled) {
     GPT2Decode* d = model->decode;
     if (!n_draft || !n_accepted || !out_tokens) return 1;
-    if (d->sample) {
+    if (sampled && d->sample != 2) {
+        fprintf(stderr, "[paged_infer] verify_sampled: sampling mode 2 only (mode %d is on%s)\n", d->sample,
+                d->sample ? ": its float sampler has no integer masses" : ": gpt2_decode_verify is the greedy pass");
+        return 1;
+    }
+    if (!sampled && d->sample) {
         fprintf(stderr, "[paged_infer] verify: greedy decoding only (sampling mode %d is on)\n", d->sample);
         return 1;
     }
@@ -2937,6 +3008,13 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, 
         d->h_vf = (int*)malloc((n_int + 4 * (size_t)B) * sizeof(int));
         if (!d->vf_int || !d->vf_lp || !d->h_vf) { dec_verify_free(d); return 1; }
     }
+    if (sampled && !d->sp_w) {
+        d->sp_w = (unsigned long long*)hpa_malloc(2 * (size_t)B * (MR - 1) * sizeof(unsigned long long));
+        d->sp_i = (int*)hpa_malloc(((size_t)B * (MR - 1) + B) * sizeof(int));
+        d->h_sp_w = (unsigned long long*)malloc(2 * (size_t)B * (MR - 1) * sizeof(unsigned long long));
+        if (!d->sp_w || !d->sp_i || !d->h_sp_w) { dec_verify_free(d); return 1; }
+    }
+    int* sp_excl = sampled ? d->sp_i + (size_t)B * (MR - 1) : NULL;
     int *v_drafts = d->vf_int, *v_d0 = v_drafts + (size_t)B * (MR - 1), *v_acc = v_d0 + B, *v_tgt = v_acc + B,
         *v_top = v_tgt + (size_t)B * MR;
     int *hst = d->h_vf, *hr0 = hst + B, *hln = hr0 + B, *hd0 = hln + B, *hacc = hd0 + B;
@@ -2965,17 +3043,25 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, 
     if (!rc)
         rc = dec_prefill_layers(model, R, T,
                                 gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request));
-    const DecScore sc = {NULL, NULL, NULL, v_tgt, d->vf_lp, v_top, 0, NULL, NULL};
-    if (!rc) rc = dec_score_rows(model, R, &sc);
     /* the accepted row of every live sequence -> the decode rows, logits, pick
      * (which advances pos by one from start + accepted) */
-    rc |= hpa_verify_accept(d->pf_tok, v_top, d->pf_start, d_row0, d_len, B, v_acc, d->pf_last, d->d_pos);
+    if (sampled) {
+        if (!rc && ND) rc = dec_spec_rows(model, R, ND, hr0, hln, v_drafts);
+        rc |= hpa_spec_accept(d->sp_w, d->sp_w + (size_t)B * (MR - 1), v_drafts, v_d0, d->pf_start, d_row0, d_len, B,
+                              d->d_rng, v_acc, d->pf_last, sp_excl, d->d_pos);
+    } else {
+        const DecScore sc = {NULL, NULL, NULL, v_tgt, d->vf_lp, v_top, 0, NULL, NULL};
+        if (!rc) rc = dec_score_rows(model, R, &sc);
+        rc |= hpa_verify_accept(d->pf_tok, v_top, d->pf_start, d_row0, d_len, B, v_acc, d->pf_last, d->d_pos);
+    }
     rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->pf_last, B, d->res, d->st1, d->Mp, C);
     rc |= dec_gemm(model, 0, G_LOGITS);
-    rc |= dec_pick(model, d_len);
+    rc |= dec_pick_ex(model, d_len, sp_excl);
     if (rc) return 1;
     if (hpa_memcpy(hacc, v_acc, B * sizeof(int)) || hpa_memcpy(d->h_next, d->d_next, B * sizeof(int)) ||
-        (draft_logprobs && hpa_memcpy(hlp, d->vf_lp, (size_t)R * sizeof(float))))
+        (!sampled && draft_logprobs && hpa_memcpy(hlp, d->vf_lp, (size_t)R * sizeof(float))) ||
+        (sampled && draft_logprobs && ND &&
+         hpa_memcpy(d->h_sp_w, d->sp_w, 2 * (size_t)B * (MR - 1) * sizeof(unsigned long long))))
         return 1;
     for (int b = 0; b < B; b++) {
         n_accepted[b] = hacc[b];
@@ -2984,7 +3070,10 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, 
         if (a < 0 || a > n_draft[b]) return 1;
         for (int i = 0; i < a; i++) out_tokens[b * MR + i] = drafts[hd0[b] + i];
         out_tokens[b * MR + a] = d->h_next[b];
-        for (int i = 0; draft_logprobs && i < n_draft[b]; i++) draft_logprobs[b * MR + i] = hlp[hr0[b] + i];
+        for (int i = 0; draft_logprobs && i < n_draft[b]; i++)
+            draft_logprobs[b * MR + i] =
+                sampled ? (float)((double)d->h_sp_w[hd0[b] + i] / (double)d->h_sp_w[(size_t)B * (MR - 1) + hd0[b] + i])
+                        : hlp[hr0[b] + i];
         d->h_pos[b] += a + 1;
     }
     return hpa_synchronize();
@@ -2994,7 +3083,14 @@ int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* 
                        float* draft_logprobs) {
     GPT2Decode* d = model->decode;
     if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    return dec_trace_disarm(d, dec_verify_armed(model, drafts, n_draft, n_accepted, out_tokens, draft_logprobs));
+    return dec_trace_disarm(d, dec_verify_armed(model, drafts, n_draft, n_accepted, out_tokens, draft_logprobs, 0));
+}
+
+int gpt2_decode_verify_sampled(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
+                               float* draft_probs) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    return dec_trace_disarm(d, dec_verify_armed(model, drafts, n_draft, n_accepted, out_tokens, draft_probs, 1));
 }
 
 int gpt2_decode_release(GPT2* model, int seq) {

@@ -319,6 +319,7 @@ def lib():
     _sig(L, "hpa_verify_rows", i, [_I, _I, _I, _I, _I, _I, i, _I, _I, _I, _I])
     _sig(L, "hpa_verify_accept", i, [_I, _I, _I, _I, _I, i, _I, _I, _I])
     _sig(L, "gpt2_decode_verify", i, [v, _I, _I, _I, _I, _F])
+    _sig(L, "gpt2_decode_verify_sampled", i, [v, _I, _I, _I, _I, _F])
     _sig(L, "gpt2_decode_verify_plan", i, [i, i, i, i, i])
     _sig(L, "gpt2_decode_set_verify_attention", i, [v, i])
     _sig(L, "gpt2_ngram_draft", i, [_I, i, i, i, i, _I])
@@ -387,6 +388,9 @@ def lib():
     _sig(L, "hpa_sample_final", i, [v, i, i, v, v, v, v, v])
     _sig(L, "hpa_sample_final_serial", i, [v, i, i, v, v, v, v, v])
     _sig(L, "hpa_sample_filtered", i, [v, i, i, v, v, v, v, v, v, v, v, v, v])
+    _sig(L, "hpa_sample_filtered_ex", i, [v, i, i, v, v, v, v, v, v, v, v, v, v, v])
+    _sig(L, "hpa_sample_filtered_prob", i, [v, i, i, v, v, v, v, v, v, v, v, v])
+    _sig(L, "hpa_spec_accept", i, [v, v, v, v, v, v, v, i, v, v, v, v, v])
     _sig(L, "hpa_paged_attention_decode_frag", i, [v, P, i, v, i, v, v, i])
     _sig(L, "gpt2_decode_set_positions", i, [v, _I])
     _sig(L, "gpt2_decode_logits", v, [v])
@@ -1081,6 +1085,27 @@ class Model:
         return ([int(acc[b]) if live[b] else None for b in range(self.B)],
                 [toks[b, :acc[b] + 1].tolist() if live[b] else None for b in range(self.B)],
                 [lp[b, :nd[b]].copy() if live[b] and want_logprobs else None for b in range(self.B)])
+
+    def verify_sampled(self, drafts, want_probs=False):
+        """gpt2_decode_verify_sampled: one speculative pass under sampling
+        mode 2 (per-sequence temperature / top-k / top-p), drafts as point-mass
+        proposals.  Arguments and the first two results as verify(); the third,
+        probs[b] (None unless want_probs), = the mass mode 2 gives every
+        drafted id at its row, examined or not."""
+        assert len(drafts) == self.B
+        nd = np.array([-1 if t is None else len(t) for t in drafts], np.int32)
+        parts = [np.asarray(t, np.int32).reshape(-1) for t in drafts if t is not None and len(t)]
+        flat = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros(1, np.int32), np.int32)
+        acc = np.zeros(self.B, np.int32)
+        toks = np.zeros((self.B, VERIFY_MAX_ROWS), np.int32)
+        pr = np.zeros((self.B, VERIFY_MAX_ROWS), np.float32)
+        check(lib().gpt2_decode_verify_sampled(self.h, flat.ctypes.data_as(_I), nd.ctypes.data_as(_I),
+                                               acc.ctypes.data_as(_I), toks.ctypes.data_as(_I),
+                                               pr.ctypes.data_as(_F) if want_probs else None), "verify_sampled")
+        live = [int(n) >= 0 for n in nd]
+        return ([int(acc[b]) if live[b] else None for b in range(self.B)],
+                [toks[b, :acc[b] + 1].tolist() if live[b] else None for b in range(self.B)],
+                [pr[b, :nd[b]].copy() if live[b] and want_probs else None for b in range(self.B)])
 
     def set_verify_attention(self, request=0):
         """the attention kernel of verify(): 0 auto, 1 the prefill kernel, 2 the
