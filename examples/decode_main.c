@@ -20,6 +20,7 @@
  *                 [--temperature X] [--top-k N] [--top-p X] [--perplexity] [--logprobs]
  *                 [--speculate K] [--speculate-sampled K] [--repetition-penalty R] [--presence-penalty X]
  *                 [--frequency-penalty X] [--ban ID]... [--top-logprobs K]
+ *                 [--speculate-tree N] [--tree-depth D] [--tree-branches W]
  *     -g greedy (default: sampling as the reference), -o writes the B x
  *     (prompt + new) token ids as int32, -q prints only the summary line.
  *     --temperature / --top-k / --top-p: any of them selects filtered
@@ -42,6 +43,15 @@
  *     accepted drafts and one token of the model's own.  The ids are those of
  *     plain greedy decoding; one more line reports passes, tokens and the mean
  *     number of accepted drafts per sequence and pass.  Not with --logprobs.
+ *     --speculate-tree N (1..7 nodes, with -g only; --tree-depth D, default 4;
+ *     --tree-branches W, default 3): the same loop over draft TREES.  Every
+ *     pass merges the continuations of up to W earlier occurrences of the
+ *     suffix into a tree of at most N drafts, D deep (gpt2_ngram_draft_tree),
+ *     and gpt2_decode_verify_tree verifies every branch in one pass.  The ids
+ *     are those of plain greedy decoding; the closing line also reports how
+ *     many (sequence, pass) pairs continued from a node that was not on the
+ *     tree's first branch (what a chain draft would have lost).  Exclusive with
+ *     --speculate, --speculate-sampled, sampling and processor flags.
  *     --repetition-penalty R (> 0, 1 = off; the HF rule), --presence-penalty X,
  *     --frequency-penalty X (0 = off; the OpenAI rule) and --ban ID (repeatable,
  *     up to HPA_LOGIT_BIAS_MAX ids that are never produced): any of them turns
@@ -103,6 +113,7 @@ int main(int argc, char** argv) {
     const char *ckpt = NULL, *tok_path = NULL, *tokens_path = NULL, *ids_out = NULL;
     int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
     int perplexity = 0, logprobs = 0, speculate = 0, spec_sampled = 0, top_lp = 0;
+    int spec_tree = 0, spec_chain = 0, tree_depth = 4, tree_branches = 3;
     float temperature = 1.0f, top_p = 1.0f;
     int processors = 0, n_ban = 0, ban[HPA_LOGIT_BIAS_MAX];
     float repetition = 1.0f, presence = 0.0f, frequency = 0.0f, ban_value[HPA_LOGIT_BIAS_MAX];
@@ -124,8 +135,11 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--temperature")) { temperature = (float)atof(v); filtered = 1; }
         else if (!strcmp(a, "--top-k")) { top_k = atoi(v); filtered = 1; }
         else if (!strcmp(a, "--top-p")) { top_p = (float)atof(v); filtered = 1; }
-        else if (!strcmp(a, "--speculate")) speculate = atoi(v);
-        else if (!strcmp(a, "--speculate-sampled")) { speculate = atoi(v); spec_sampled = filtered = 1; }
+        else if (!strcmp(a, "--speculate")) { speculate = atoi(v); spec_chain = 1; }
+        else if (!strcmp(a, "--speculate-sampled")) { speculate = atoi(v); spec_chain = spec_sampled = filtered = 1; }
+        else if (!strcmp(a, "--speculate-tree")) { speculate = atoi(v); spec_tree = 1; }
+        else if (!strcmp(a, "--tree-depth")) tree_depth = atoi(v);
+        else if (!strcmp(a, "--tree-branches")) tree_branches = atoi(v);
         else if (!strcmp(a, "--top-logprobs")) {
             top_lp = atoi(v);
             if (top_lp < 1 || top_lp > HPA_TOP_LOGPROBS_MAX) {
@@ -144,6 +158,12 @@ int main(int argc, char** argv) {
         }
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         i++;
+    }
+    if (spec_tree && (spec_chain || speculate < 1 || speculate > HPA_VERIFY_MAX_ROWS - 1 || tree_depth < 1 ||
+                      tree_branches < 1)) {
+        fprintf(stderr, "--speculate-tree takes 1..%d nodes (--tree-depth and --tree-branches >= 1) and does not go "
+                        "with --speculate or --speculate-sampled\n", HPA_VERIFY_MAX_ROWS - 1);
+        return 2;
     }
     if (speculate) {
         if (speculate < 1 || speculate > HPA_VERIFY_MAX_ROWS - 1) {
@@ -279,7 +299,7 @@ int main(int argc, char** argv) {
         if (new_tokens > 0) gen[(size_t)b * total + prompt_len] = next[b];
     }
     if (!quiet) printf("\ngenerating:\n---\n");
-    long spec_passes = 0, spec_live = 0, spec_accepted = 0, spec_tokens = 0;
+    long spec_passes = 0, spec_live = 0, spec_accepted = 0, spec_tokens = 0, spec_off_first = 0;
     if (speculate && new_tokens > 0) {
         /* count[b] tokens of sequence b are out (the prefill's pick is the first and is b's pending id) */
         int* count = (int*)malloc(B * sizeof(int));
@@ -287,7 +307,10 @@ int main(int argc, char** argv) {
         int* n_acc = (int*)malloc(B * sizeof(int));
         int* drafts = (int*)malloc((size_t)B * HPA_VERIFY_MAX_ROWS * sizeof(int));
         int* out = (int*)malloc((size_t)B * HPA_VERIFY_MAX_ROWS * sizeof(int));
-        if (!count || !n_draft || !n_acc || !drafts || !out) return 1;
+        int* parents = (int*)malloc((size_t)B * HPA_VERIFY_MAX_ROWS * sizeof(int));
+        int* nodes = (int*)malloc((size_t)B * HPA_VERIFY_MAX_ROWS * sizeof(int));
+        int* d0 = (int*)malloc(B * sizeof(int));
+        if (!count || !n_draft || !n_acc || !drafts || !out || !parents || !nodes || !d0) return 1;
         for (int b = 0; b < B; b++) count[b] = 1;
         if (!quiet) print_token(&tk, next[0]);
         for (;;) {
@@ -297,19 +320,35 @@ int main(int argc, char** argv) {
                 n_draft[b] = -1;
                 if (left <= 0) continue;
                 const int k = speculate < left - 1 ? speculate : left - 1;
-                n_draft[b] = gpt2_ngram_draft(gen + (size_t)b * total, prompt_len + count[b], 3, 1, k, drafts + nd);
+                d0[b] = nd;
+                if (!spec_tree)
+                    n_draft[b] = gpt2_ngram_draft(gen + (size_t)b * total, prompt_len + count[b], 3, 1, k, drafts + nd);
+                else /* a path of depth d emits d + 1 tokens: no deeper than left - 1 */
+                    n_draft[b] = k < 1 ? 0
+                                       : gpt2_ngram_draft_tree(gen + (size_t)b * total, prompt_len + count[b], 3, 1, k,
+                                                               tree_depth < k ? tree_depth : k, tree_branches,
+                                                               drafts + nd, parents + nd);
                 nd += n_draft[b];
                 live++;
             }
             if (!live) break;
-            if (spec_sampled ? gpt2_decode_verify_sampled(&model, drafts, n_draft, n_acc, out, NULL)
-                             : gpt2_decode_verify(&model, drafts, n_draft, n_acc, out, NULL))
+            if (spec_tree      ? gpt2_decode_verify_tree(&model, drafts, parents, n_draft, n_acc, out, nodes)
+                : spec_sampled ? gpt2_decode_verify_sampled(&model, drafts, n_draft, n_acc, out, NULL)
+                               : gpt2_decode_verify(&model, drafts, n_draft, n_acc, out, NULL))
                 return 1;
             spec_passes++;
             spec_live += live;
             for (int b = 0; b < B; b++) {
                 if (n_draft[b] < 0) continue;
                 spec_accepted += n_acc[b];
+                if (spec_tree && n_acc[b] > 0) {
+                    /* is the node decoding continues from on the first-child chain from the root? */
+                    const int last = nodes[b * HPA_VERIFY_MAX_ROWS + n_acc[b] - 1];
+                    int cur = 0, on_first = 0;
+                    for (int j = 0; j < n_draft[b] && !on_first; j++)
+                        if (parents[d0[b] + j] == cur) { cur = j + 1; on_first = cur == last; }
+                    spec_off_first += !on_first;
+                }
                 for (int i = 0; i <= n_acc[b]; i++) {
                     const int id = out[b * HPA_VERIFY_MAX_ROWS + i];
                     gen[(size_t)b * total + prompt_len + count[b]++] = id;
@@ -318,7 +357,7 @@ int main(int argc, char** argv) {
                 spec_tokens += n_acc[b] + 1;
             }
         }
-        free(count); free(n_draft); free(n_acc); free(drafts); free(out);
+        free(count); free(n_draft); free(n_acc); free(drafts); free(out); free(parents); free(nodes); free(d0);
     }
     for (int t = 1; t < new_tokens && !speculate; t++) {
         if (!quiet) print_token(&tk, next[0]);
@@ -341,6 +380,9 @@ int main(int argc, char** argv) {
     if (speculate)
         printf("speculation: %ld passes, %ld tokens emitted, mean accepted %.2f drafts per sequence and pass\n",
                spec_passes, spec_tokens, spec_live ? (double)spec_accepted / spec_live : 0.0);
+    if (spec_tree)
+        printf("tree speculation: %ld of %ld (sequence, pass) pairs continued from a node off the first branch\n",
+               spec_off_first, spec_live);
     if (ids_out) {
         FILE* f = fopen(ids_out, "wb");
         if (!f || fwrite(gen, sizeof(int), (size_t)B * total, f) != (size_t)B * total) return 1;

@@ -829,6 +829,63 @@ int hpa_verify_rows(const int* next, const int* drafts, const int* draft0, const
 int hpa_verify_accept(const int* tok, const int* top_id, const int* start, const int* row0, const int* len, int B,
                       int* n_accepted, int* cont_row, int* pos);
 
+/* ---------------- tree speculation (hpa_verify.hip) ----------------
+ * The len[b] <= HPA_VERIFY_MAX_ROWS rows of sequence b are the nodes of a token
+ * tree, not a chain: node 0 is the pending id, node j + 1 is draft j (packed
+ * like `drafts`) and hangs from node parents[draft0[b] + j] in [0, j] -- a
+ * smaller index than its own, so node order is topological.  Node i's K/V is
+ * appended to slot start[b] + i whatever its depth.
+ *
+ * hpa_paged_attention_verify_tree: hpa_paged_attention_verify's contract with
+ * one change: the row of node r of sequence b sees keys 0 .. start[b] - 1 plus
+ * key start[b] + i for every bit i of anc[row0[b] + r] (device, one byte per
+ * packed row; bit r itself must be set and no bit above it, as
+ * hpa_verify_tree_rows writes them).  The same kernel with a compile-time mask
+ * test: same tile loop, same dealing of tiles over waves, same fold, so with
+ * chain masks (bits 0 .. r) the output bits are hpa_paged_attention_verify's.
+ * Each wave reads its sequence's masks once into scalar registers.  A hidden
+ * node's K/V is still streamed and its V row multiplied by a weight of
+ * exactly 0: hidden slots must hold finite values (the pass's own appends do).
+ * Limits as the verify kernel's: fp32 pool, head size 64, page size 8 / 16 /
+ * 32 / 64, 1 <= T <= HPA_VERIFY_MAX_ROWS, no context splits; anything else
+ * returns nonzero and launches nothing. */
+int hpa_paged_attention_verify_tree(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
+                                    int bt_stride, const int* start, const int* row0, const int* len,
+                                    const unsigned char* anc, int B, int T, float* out_frag);
+/* row tables of a tree pass (device arrays), the sibling of hpa_verify_rows:
+ * per packed row row0[b] + i of node i: tok (next[b] for node 0, else draft
+ * i - 1), seq = b, pos = start[b] + depth(i) (what hpa_embed_frag reads for
+ * wpe), slot = start[b] + i (the QKV GEMM's append position) and anc (bit k:
+ * node k is node i or one of its ancestors).  A parent outside [0, j] is
+ * clamped into it (the engine refuses it before launching anything). */
+int hpa_verify_tree_rows(const int* next, const int* drafts, const int* parents, const int* draft0, const int* start,
+                         const int* row0, const int* len, int B, int* tok, int* pos, int* seq, int* slot,
+                         unsigned char* anc);
+/* the accept walk, one thread per sequence: cur = 0; while some child c of cur
+ * (lowest index first) has tok[row0[b] + c] == top_id[row0[b] + cur]: cur = c.
+ * n_accepted[b] = a = depth(cur); path[b * HPA_VERIFY_MAX_ROWS + i], i < a:
+ * the node indices walked (strictly increasing); cont_row[b] = row0[b] + cur;
+ * pos[b] = start[b] + a.  len[b] == 0: n_accepted[b] = cont_row[b] = -1, pos[b]
+ * and path untouched.  Siblings with equal tokens: the lower index wins (the
+ * engine refuses such trees). */
+int hpa_verify_tree_accept(const int* tok, const int* top_id, const int* parents, const int* draft0, const int* start,
+                           const int* row0, const int* len, int B, int* n_accepted, int* path, int* cont_row,
+                           int* pos);
+/* K/V compaction after a tree pass: for every sequence b with a =
+ * n_accepted[b] > 0 and every k = 1 .. a with p = path[b * HPA_VERIFY_MAX_ROWS +
+ * k - 1] != k, the K and V of slot start[b] + p go to slot start[b] + k, in
+ * every layer and head; pages are resolved through the block table (source and
+ * destination may lie in different pages).  ONE asynchronous launch on the
+ * current stream; start / path / n_accepted / block_table are device arrays.
+ * In place: each thread owns a fixed (layer, K|V, head, 4 dims) lane and walks
+ * k upwards; path strictly increases with path[k-1] >= k, so a destination is
+ * never a source still to be read.  Entries that break that, and n_accepted
+ * <= 0, move nothing.  The slots from start[b] on must be private to b (the
+ * engine's appends went there after its copy-on-write).  fp32 pools, head size
+ * 64; anything else returns nonzero and launches nothing. */
+int hpa_pool_compact_path(const HpaKVPool* pool, const int* block_table, int bt_stride, const int* start,
+                          const int* path, const int* n_accepted, int B);
+
 /* rows[i] of a frag-layout [src_Mp][C] matrix and of its LN statistics
  * ([C/16][src_Mp][2]) -> row i of dst / dst_stats (n rows; prefill -> logits);
  * rows[i] < 0 leaves row i of dst as it is */

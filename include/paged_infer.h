@@ -295,6 +295,64 @@ int  gpt2_decode_verify_sampled(GPT2* model, const int* drafts, const int* n_dra
  * up to k of the tokens that followed it are copied to draft.  Returns how
  * many (0: no match, k <= 0, n too short). */
 int  gpt2_ngram_draft(const int* history, int n, int max_ngram, int min_ngram, int k, int* draft);
+/* Tree speculation: gpt2_decode_verify over a draft TREE per sequence, greedy.
+ * The n_draft[b] + 1 <= HPA_VERIFY_MAX_ROWS rows of sequence b are tree nodes:
+ * node 0 is b's pending id, draft j (0-based, packed like `drafts`) is node
+ * j + 1 and hangs from node parents[j] in [0, j] (`parents` is packed like
+ * `drafts`; a parent is always a smaller node index than its child).  A chain
+ * is parents[j] = j.  One pass verifies every branch and continues from the
+ * deepest node the model agrees with; each sequence's cached K/V is read once,
+ * exactly as in gpt2_decode_verify.
+ * n_draft (-1 untouched, 0 a plain step), out_tokens (stride
+ * HPA_VERIFY_MAX_ROWS: the a accepted tokens, then the model's own), page
+ * growth, eviction, shared pages, trace arming (rows in node order) and the
+ * tail (gather from the continuing row, logits GEMM, pick, log-probabilities /
+ * top log-probabilities as set) are gpt2_decode_verify's.
+ * The pass: hpa_verify_tree_rows (node i of b: wpe position pos[b] + depth(i),
+ * K/V appended to slot pos[b] + i, ancestor mask); the layers with
+ * hpa_paged_attention_verify_tree (a node sees the cached context and its own
+ * ancestors, never a sibling branch); every row's greedy id from the SCORE GEMM
+ * with targets -1; hpa_verify_tree_accept: cur = node 0, and while some child c
+ * of cur (lowest index first) carries the greedy id of cur, cur = c; then
+ * hpa_pool_compact_path moves the K/V of the accepted path's nodes into the
+ * consecutive slots pos[b] + 1 .. pos[b] + a in every layer (one launch); then
+ * the tail from cur's row.
+ *   n_accepted[b] = a = depth(cur) (-1: untouched)
+ *   out_tokens[b * HPA_VERIFY_MAX_ROWS + i], i <= a: the accepted drafts along
+ *     the path, then the model's own next token (b's new pending id)
+ *   accepted_nodes (nullable, same stride): entry i < a = the node index
+ *     (1-based among the drafts: draft j is node j + 1) of the i-th accepted draft
+ * Afterwards pos[b] += a + 1 and the engine is in the state a + 1 greedy steps
+ * would leave, K/V slots included.  The slots past the new position hold
+ * rejected nodes' rows, which nothing reads.
+ * Limits: greedy only (no sampled tree verification); fp32 KV pools (the
+ * bf16 / fp8 pools' prefill kernel has no tree mask); at most
+ * HPA_VERIFY_MAX_ROWS nodes; no drafted-token log-probability output (a node
+ * with several children has several targets and the SCORE epilogue takes one
+ * per row).
+ * Refused (message, nonzero, nothing changed -- positions, pages, pending ids):
+ * everything gpt2_decode_verify refuses (a sampling mode other than 0, logit
+ * processors on, n_draft or a draft id out of range, overflow of max_ctx, no
+ * engine), a parent outside [0, j], two siblings (same parent) with the same
+ * token, and an engine for which gpt2_decode_verify_plan(rows, kv_dtype,
+ * page_size, head_size, 0) != 1. */
+int  gpt2_decode_verify_tree(GPT2* model, const int* drafts, const int* parents, const int* n_draft,
+                             int* n_accepted, int* out_tokens, int* accepted_nodes);
+/* n-gram tree drafter, host only (no device, allocation or I/O).  For g from
+ * max_ngram down to min_ngram, the earlier occurrences of the last g tokens of
+ * history[0..n) that have at least one token after them are scanned, most
+ * recent first; each one's continuation (up to `depth` tokens) is inserted
+ * into a trie rooted at node 0 (the pending token): existing prefixes are
+ * shared, new nodes appended, so parents precede children.  Stops once
+ * max_nodes (1..HPA_VERIFY_MAX_ROWS - 1) drafts exist -- an insertion is cut
+ * there -- or once max_branches continuations have each added at least one
+ * node.  draft[j] / parents[j] (room for max_nodes each): draft j's token and
+ * parent node, in gpt2_decode_verify_tree's layout.  Returns the number of
+ * drafts (0: no match, or max_nodes, depth or max_branches < 1, n too short).
+ * The first inserted continuation is gpt2_ngram_draft's with k = depth, so for
+ * depth <= max_nodes the tree's first-child chain is that draft. */
+int  gpt2_ngram_draft_tree(const int* history, int n, int max_ngram, int min_ngram, int max_nodes, int depth,
+                           int max_branches, int* draft, int* parents);
 /* enable != 0: every pick (decode step, prefill, ragged prefill, score) is
  * followed by one hpa_logprob_rows launch: the log-probability of the chosen
  * id under the raw model distribution (temperature 1, no filter, in every

@@ -757,6 +757,16 @@ struct GPT2Decode {
     unsigned long long* sp_w;
     int* sp_i;
     unsigned long long* h_sp_w;
+    /* tree speculation (gpt2_decode_verify_tree), allocated on first use: vt_int =
+     * drafts [B * 7], parents [B * 7] (one upload), accepted [B], the accepted
+     * path [B * HPA_VERIFY_MAX_ROWS] (one download), the rows' K/V slots [B *
+     * HPA_VERIFY_MAX_ROWS]; vt_anc the rows' ancestor masks; h_vt the host
+     * staging of the upload, then of the download.  pf_slot: the rows' append slots while a tree pass runs its layers
+     * (prefill_gemm: the QKV GEMM's positions), NULL otherwise */
+    int* vt_int;
+    unsigned char* vt_anc;
+    int* h_vt;
+    const int* pf_slot;
     /* logit processors (gpt2_decode_set_processors).  The settings' host
      * mirrors exist from gpt2_decode_init on (they may be set while off); the
      * device tables are allocated on first enable: the fed tokens pr_hist
@@ -856,6 +866,9 @@ static void dec_verify_free(GPT2Decode* d) {
     hpa_free(d->sp_w); hpa_free(d->sp_i);
     free(d->h_sp_w);
     d->sp_w = NULL; d->sp_i = NULL; d->h_sp_w = NULL;
+    hpa_free(d->vt_int); hpa_free(d->vt_anc);
+    free(d->h_vt);
+    d->vt_int = NULL; d->vt_anc = NULL; d->h_vt = NULL;
 }
 
 static void dec_shard_free(GPT2Decode* d) {
@@ -2458,6 +2471,7 @@ static int prefill_gemm(GPT2* model, int l, int which, int R) {
             g.epilogue = HPA_FEPI_QKV; g.x = d->pf_res; g.K = C; g.ln_stats = d->pf_st1;
             g.ln_ntiles = l == 0 ? 1 : ct; g.ln_w = o.ln1_w; g.ln_b = o.ln1_b;
             g.w = o.w_qkv; g.N = 3 * C; g.bias = o.b_qkv; g.out = d->pf_q;
+            if (d->pf_slot) g.pos = d->pf_slot; /* a tree pass appends node i at start + i, whatever its depth */
             if (d->d_fold) { g.ln_fold_c1 = o.qkv_c1; g.bias = o.qkv_c2; }
             break;
         case G_ATTPROJ:
@@ -2699,8 +2713,9 @@ static int dec_trace_fits(GPT2* model, long R) {
 
 /* the R packed rows of the uploaded row tables (pf_tok, pf_pos, pf_seq;
  * pf_start: start, row0, len) through the embedding and every layer; T =
- * max(len).  verify_attn: the few-row kernel (gpt2_decode_verify_plan) in
- * place of the MFMA prefill kernel */
+ * max(len).  verify_attn: 1 the few-row kernel (gpt2_decode_verify_plan) in
+ * place of the MFMA prefill kernel; 2 its tree form over the masks of vt_anc
+ * (gpt2_decode_verify_tree) */
 static int dec_prefill_layers(GPT2* model, int R, int T, int verify_attn) {
     GPT2Decode* d = model->decode;
     const int B = d->B, C = model->config.channels, L = model->config.num_layers;
@@ -2723,10 +2738,13 @@ static int dec_prefill_layers(GPT2* model, int R, int T, int verify_attn) {
     PF_TRACE(0);
     for (int l = 0; l < L && !rc; l++) {
         rc |= prefill_gemm(model, l, G_QKV, R);
-        rc |= verify_attn ? hpa_paged_attention_verify(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
-                                                       d_len, B, T, d->pf_att)
-                          : hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start,
-                                                               d_row0, d_len, B, T, d->pf_att);
+        rc |= verify_attn == 2
+                  ? hpa_paged_attention_verify_tree(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
+                                                    d_len, d->vt_anc, B, T, d->pf_att)
+              : verify_attn ? hpa_paged_attention_verify(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
+                                                         d_len, B, T, d->pf_att)
+                            : hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start,
+                                                                 d_row0, d_len, B, T, d->pf_att);
         rc |= prefill_gemm(model, l, G_ATTPROJ, R);
         rc |= prefill_gemm(model, l, G_FC, R);
         rc |= prefill_gemm(model, l, G_FCPROJ, R);
@@ -2954,11 +2972,16 @@ static int dec_spec_rows(GPT2* model, int R, int ND, const int* hrow0, const int
 }
 
 /* sampled: gpt2_decode_verify_sampled (draft_out: the drafts' probabilities);
- * else gpt2_decode_verify (draft_out: their raw log-probabilities) */
-static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
-                            float* draft_logprobs, int sampled) {
+ * else gpt2_decode_verify (draft_out: their raw log-probabilities).
+ * parents != NULL (greedy only): gpt2_decode_verify_tree -- the rows are tree
+ * nodes: depth positions, slot appends and ancestor masks in the layers, no
+ * SCORE targets, the accept walk, then the accepted path's K/V compacted into
+ * consecutive slots ahead of the tail; accepted_nodes (nullable): the path */
+static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, const int* n_draft, int* n_accepted,
+                            int* out_tokens, float* draft_logprobs, int sampled, int* accepted_nodes) {
     GPT2Decode* d = model->decode;
     if (!n_draft || !n_accepted || !out_tokens) return 1;
+    const int tree = parents != NULL;
     if (sampled && d->sample != 2) {
         fprintf(stderr, "[paged_infer] verify_sampled: sampling mode 2 only (mode %d is on%s)\n", d->sample,
                 d->sample ? ": its float sampler has no integer masses" : ": gpt2_decode_verify is the greedy pass");
@@ -2995,9 +3018,31 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, 
             fprintf(stderr, "[paged_infer] verify: draft %d (%d) is outside [0, %d)\n", i, drafts[i], c.vocab_size);
             return 1;
         }
+    if (tree) { /* draft j of a sequence is node j + 1: its parent a node in [0, j], no sibling with its token */
+        for (int b = 0, nd = 0; b < B; nd += n_draft[b] > 0 ? n_draft[b] : 0, b++)
+            for (int j = 0; j < n_draft[b]; j++) {
+                const int pj = parents[nd + j];
+                if (pj < 0 || pj > j) {
+                    fprintf(stderr, "[paged_infer] verify_tree: parent %d of draft %d of sequence %d is outside [0, %d]\n",
+                            pj, j, b, j);
+                    return 1;
+                }
+                for (int i = 0; i < j; i++)
+                    if (parents[nd + i] == pj && drafts[nd + i] == drafts[nd + j]) {
+                        fprintf(stderr, "[paged_infer] verify_tree: drafts %d and %d of sequence %d are siblings with the "
+                                        "same token\n", i, j, b);
+                        return 1;
+                    }
+            }
+    }
     if (R == 0) {
         for (int b = 0; b < B; b++) n_accepted[b] = -1;
         return 0;
+    }
+    if (tree && gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, 0) != 1) {
+        fprintf(stderr, "[paged_infer] verify_tree: fp32 KV pool, head size 64, page size 8 / 16 / 32 / 64 only (the "
+                        "prefill kernel of the other pools has no tree mask)\n");
+        return 1;
     }
     if (dec_trace_fits(model, R)) return 1;
     /* tables: drafts [B * (MR - 1)], draft0 [B], accepted [B], targets [B * MR], greedy ids [B * MR] */
@@ -3014,11 +3059,28 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, 
         d->h_sp_w = (unsigned long long*)malloc(2 * (size_t)B * (MR - 1) * sizeof(unsigned long long));
         if (!d->sp_w || !d->sp_i || !d->h_sp_w) { dec_verify_free(d); return 1; }
     }
+    if (tree && !d->vt_int) {
+        d->vt_int = (int*)hpa_malloc((2 * (size_t)B * (MR - 1) + B + 2 * (size_t)B * MR) * sizeof(int));
+        d->vt_anc = (unsigned char*)hpa_malloc((size_t)B * MR);
+        d->h_vt = (int*)malloc((2 * (size_t)B * (MR - 1) + B + (size_t)B * MR) * sizeof(int));
+        if (!d->vt_int || !d->vt_anc || !d->h_vt) { dec_verify_free(d); return 1; }
+    }
     int* sp_excl = sampled ? d->sp_i + (size_t)B * (MR - 1) : NULL;
     int *v_drafts = d->vf_int, *v_d0 = v_drafts + (size_t)B * (MR - 1), *v_acc = v_d0 + B, *v_tgt = v_acc + B,
         *v_top = v_tgt + (size_t)B * MR;
     int *hst = d->h_vf, *hr0 = hst + B, *hln = hr0 + B, *hd0 = hln + B, *hacc = hd0 + B;
     float* hlp = (float*)(hacc + B); /* [B * MR]: fits the n_int tail */
+    /* a tree pass keeps drafts beside parents and the accepted counts beside the path: one copy each way */
+    int *t_par = NULL, *t_path = NULL, *t_slot = NULL, *h_tpath = NULL;
+    if (tree) {
+        v_drafts = d->vt_int;
+        t_par = v_drafts + (size_t)B * (MR - 1);
+        v_acc = t_par + (size_t)B * (MR - 1);
+        t_path = v_acc + B;
+        t_slot = t_path + (size_t)B * MR;
+        hacc = d->h_vt + 2 * (size_t)B * (MR - 1);
+        h_tpath = hacc + B;
+    }
     for (int b = 0; b < B; b++) hln[b] = n_draft[b] + 1;
     for (int b = 0; b < B; b++)
         if (hln[b] > 0 && dec_grow(d, b, hln[b], hln, NULL)) return 1;
@@ -3033,16 +3095,31 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, 
         if (n_draft[b] > 0) nd += n_draft[b];
     }
     if (hpa_memcpy(d->pf_start, hst, 3 * (size_t)B * sizeof(int)) || hpa_memcpy(v_d0, hd0, B * sizeof(int)) ||
-        (ND && hpa_memcpy(v_drafts, drafts, (size_t)ND * sizeof(int))))
+        (ND && !tree && hpa_memcpy(v_drafts, drafts, (size_t)ND * sizeof(int))))
         return 1;
+    if (tree && ND) { /* drafts [ND] and, from B * (MR - 1) on, parents [ND] */
+        memcpy(d->h_vt, drafts, (size_t)ND * sizeof(int));
+        memcpy(d->h_vt + (size_t)B * (MR - 1), parents, (size_t)ND * sizeof(int));
+        if (hpa_memcpy(v_drafts, d->h_vt, ((size_t)B * (MR - 1) + ND) * sizeof(int))) return 1;
+    }
     const int* d_row0 = d->pf_start + B;
     const int* d_len = d->pf_start + 2 * B;
     const int Rp = (R + 15) / 16 * 16;
-    int rc = hpa_verify_rows(d->d_next, v_drafts, v_d0, d->pf_start, d_row0, d_len, B, d->pf_tok, d->pf_pos, d->pf_seq,
+    int rc;
+    if (tree) { /* no row has a single target: the SCORE GEMM runs with -1 throughout */
+        rc = hpa_verify_tree_rows(d->d_next, v_drafts, t_par, v_d0, d->pf_start, d_row0, d_len, B, d->pf_tok, d->pf_pos,
+                                  d->pf_seq, t_slot, d->vt_anc) ||
+             hpa_memset_async(v_tgt, 0xFF, (size_t)R * sizeof(int));
+        d->pf_slot = t_slot;
+        if (!rc) rc = dec_prefill_layers(model, R, T, 2);
+        d->pf_slot = NULL;
+    } else {
+        rc = hpa_verify_rows(d->d_next, v_drafts, v_d0, d->pf_start, d_row0, d_len, B, d->pf_tok, d->pf_pos, d->pf_seq,
                              v_tgt);
-    if (!rc)
-        rc = dec_prefill_layers(model, R, T,
-                                gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request));
+        if (!rc)
+            rc = dec_prefill_layers(model, R, T,
+                                    gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request));
+    }
     /* the accepted row of every live sequence -> the decode rows, logits, pick
      * (which advances pos by one from start + accepted) */
     if (sampled) {
@@ -3052,13 +3129,20 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, 
     } else {
         const DecScore sc = {NULL, NULL, NULL, v_tgt, d->vf_lp, v_top, 0, NULL, NULL};
         if (!rc) rc = dec_score_rows(model, R, &sc);
-        rc |= hpa_verify_accept(d->pf_tok, v_top, d->pf_start, d_row0, d_len, B, v_acc, d->pf_last, d->d_pos);
+        if (tree) {
+            rc |= hpa_verify_tree_accept(d->pf_tok, v_top, t_par, v_d0, d->pf_start, d_row0, d_len, B, v_acc, t_path,
+                                         d->pf_last, d->d_pos);
+            rc |= hpa_pool_compact_path(&d->pool, d->d_bt, d->bt_stride, d->pf_start, t_path, v_acc, B);
+        } else {
+            rc |= hpa_verify_accept(d->pf_tok, v_top, d->pf_start, d_row0, d_len, B, v_acc, d->pf_last, d->d_pos);
+        }
     }
     rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->pf_last, B, d->res, d->st1, d->Mp, C);
     rc |= dec_gemm(model, 0, G_LOGITS);
     rc |= dec_pick_ex(model, d_len, sp_excl);
     if (rc) return 1;
-    if (hpa_memcpy(hacc, v_acc, B * sizeof(int)) || hpa_memcpy(d->h_next, d->d_next, B * sizeof(int)) ||
+    if (hpa_memcpy(hacc, v_acc, (tree ? B + (size_t)B * MR : (size_t)B) * sizeof(int)) ||
+        hpa_memcpy(d->h_next, d->d_next, B * sizeof(int)) ||
         (!sampled && draft_logprobs && hpa_memcpy(hlp, d->vf_lp, (size_t)R * sizeof(float))) ||
         (sampled && draft_logprobs && ND &&
          hpa_memcpy(d->h_sp_w, d->sp_w, 2 * (size_t)B * (MR - 1) * sizeof(unsigned long long))))
@@ -3068,7 +3152,12 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* n_draft, 
         if (hln[b] <= 0) continue;
         const int a = hacc[b];
         if (a < 0 || a > n_draft[b]) return 1;
-        for (int i = 0; i < a; i++) out_tokens[b * MR + i] = drafts[hd0[b] + i];
+        for (int i = 0; i < a; i++) {
+            const int node = tree ? h_tpath[b * MR + i] : i + 1; /* draft node - 1 */
+            if (node < 1 || node > n_draft[b]) return 1;
+            out_tokens[b * MR + i] = drafts[hd0[b] + node - 1];
+            if (accepted_nodes) accepted_nodes[b * MR + i] = node;
+        }
         out_tokens[b * MR + a] = d->h_next[b];
         for (int i = 0; draft_logprobs && i < n_draft[b]; i++)
             draft_logprobs[b * MR + i] =
@@ -3083,14 +3172,29 @@ int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* 
                        float* draft_logprobs) {
     GPT2Decode* d = model->decode;
     if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    return dec_trace_disarm(d, dec_verify_armed(model, drafts, n_draft, n_accepted, out_tokens, draft_logprobs, 0));
+    return dec_trace_disarm(d, dec_verify_armed(model, drafts, NULL, n_draft, n_accepted, out_tokens, draft_logprobs, 0,
+                                                NULL));
+}
+
+static const int no_parents[1] = {0}; /* a tree call without a single draft */
+
+int gpt2_decode_verify_tree(GPT2* model, const int* drafts, const int* parents, const int* n_draft, int* n_accepted,
+                            int* out_tokens, int* accepted_nodes) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    int any = 0;
+    for (int b = 0; n_draft && b < d->B; b++) any |= n_draft[b] > 0;
+    if (any && !parents) return dec_trace_disarm(d, 1);
+    return dec_trace_disarm(d, dec_verify_armed(model, drafts, parents ? parents : no_parents, n_draft, n_accepted,
+                                                out_tokens, NULL, 0, accepted_nodes));
 }
 
 int gpt2_decode_verify_sampled(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
                                float* draft_probs) {
     GPT2Decode* d = model ? model->decode : NULL;
     if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    return dec_trace_disarm(d, dec_verify_armed(model, drafts, n_draft, n_accepted, out_tokens, draft_probs, 1));
+    return dec_trace_disarm(d, dec_verify_armed(model, drafts, NULL, n_draft, n_accepted, out_tokens, draft_probs, 1,
+                                                NULL));
 }
 
 int gpt2_decode_release(GPT2* model, int seq) {

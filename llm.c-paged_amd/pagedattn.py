@@ -323,6 +323,13 @@ def lib():
     _sig(L, "gpt2_decode_verify_plan", i, [i, i, i, i, i])
     _sig(L, "gpt2_decode_set_verify_attention", i, [v, i])
     _sig(L, "gpt2_ngram_draft", i, [_I, i, i, i, i, _I])
+    _U8 = ctypes.POINTER(ctypes.c_ubyte)
+    _sig(L, "hpa_paged_attention_verify_tree", i, [_F, v, i, _I, i, _I, _I, _I, _U8, i, i, _F])
+    _sig(L, "hpa_verify_tree_rows", i, [_I, _I, _I, _I, _I, _I, _I, i, _I, _I, _I, _I, _U8])
+    _sig(L, "hpa_verify_tree_accept", i, [_I, _I, _I, _I, _I, _I, _I, i, _I, _I, _I, _I])
+    _sig(L, "hpa_pool_compact_path", i, [P, _I, i, _I, _I, _I, i])
+    _sig(L, "gpt2_decode_verify_tree", i, [v, _I, _I, _I, _I, _I, _I])
+    _sig(L, "gpt2_ngram_draft_tree", i, [_I, i, i, i, i, i, i, _I, _I])
     _sig(L, "gpt2_decode_step", i, [v, _I, _I])
     _sig(L, "gpt2_decode_step_async", i, [v, _I])
     _sig(L, "gpt2_decode_step_traced", i, [v, _I, _I, _F])
@@ -469,6 +476,21 @@ def ngram_draft(history, k, max_ngram=3, min_ngram=1):
     n = lib().gpt2_ngram_draft(h.ctypes.data_as(_I), int(h.size), int(max_ngram), int(min_ngram), int(k),
                                out.ctypes.data_as(_I))
     return out[:n].tolist()
+
+
+def ngram_draft_tree(history, max_nodes=7, depth=4, max_branches=3, max_ngram=3, min_ngram=1):
+    """gpt2_ngram_draft_tree (host only): the continuations of the earlier
+    occurrences of the longest matching suffixes of `history`, most recent
+    first, merged into a token tree of at most max_nodes drafts, `depth` deep,
+    from at most max_branches occurrences.  Returns (ids, parents) in
+    Model.verify_tree's layout: draft j is node j + 1, parents[j] its parent
+    node in [0, j] (0: the pending token); ([], []) without a match"""
+    h = np.ascontiguousarray(np.asarray(history, np.int32).reshape(-1))
+    ids = np.zeros(VERIFY_MAX_ROWS - 1, np.int32)
+    par = np.zeros(VERIFY_MAX_ROWS - 1, np.int32)
+    n = lib().gpt2_ngram_draft_tree(h.ctypes.data_as(_I), int(h.size), int(max_ngram), int(min_ngram), int(max_nodes),
+                                    int(depth), int(max_branches), ids.ctypes.data_as(_I), par.ctypes.data_as(_I))
+    return ids[:n].tolist(), par[:n].tolist()
 
 
 class DeviceBuffer:
@@ -1085,6 +1107,34 @@ class Model:
         return ([int(acc[b]) if live[b] else None for b in range(self.B)],
                 [toks[b, :acc[b] + 1].tolist() if live[b] else None for b in range(self.B)],
                 [lp[b, :nd[b]].copy() if live[b] and want_logprobs else None for b in range(self.B)])
+
+    def verify_tree(self, trees):
+        """gpt2_decode_verify_tree: one speculative greedy pass over a draft
+        tree per sequence.  trees[b]: None (sequence untouched) or (ids,
+        parents), up to VERIFY_MAX_ROWS - 1 drafted ids with parents[j] in
+        [0, j] the node draft j hangs from (node 0: the pending id; draft j is
+        node j + 1; ([], []) is a plain decode step).  Returns (n_accepted,
+        tokens, nodes), per-sequence lists with None for an untouched sequence:
+        tokens[b] = the accepted drafts along the path and then the model's own
+        next token; nodes[b] = the accepted drafts' node indices."""
+        assert len(trees) == self.B
+        nd = np.array([-1 if t is None else len(t[0]) for t in trees], np.int32)
+        assert all(t is None or len(t[0]) == len(t[1]) for t in trees)
+        live_parts = [t for t in trees if t is not None and len(t[0])]
+        cat = lambda k: np.ascontiguousarray(  # noqa: E731
+            np.concatenate([np.asarray(t[k], np.int32).reshape(-1) for t in live_parts]) if live_parts
+            else np.zeros(1, np.int32), np.int32)
+        flat, par = cat(0), cat(1)
+        acc = np.zeros(self.B, np.int32)
+        toks = np.zeros((self.B, VERIFY_MAX_ROWS), np.int32)
+        nodes = np.zeros((self.B, VERIFY_MAX_ROWS), np.int32)
+        check(lib().gpt2_decode_verify_tree(self.h, flat.ctypes.data_as(_I), par.ctypes.data_as(_I),
+                                            nd.ctypes.data_as(_I), acc.ctypes.data_as(_I), toks.ctypes.data_as(_I),
+                                            nodes.ctypes.data_as(_I)), "verify_tree")
+        live = [int(n) >= 0 for n in nd]
+        return ([int(acc[b]) if live[b] else None for b in range(self.B)],
+                [toks[b, :acc[b] + 1].tolist() if live[b] else None for b in range(self.B)],
+                [nodes[b, :acc[b]].tolist() if live[b] else None for b in range(self.B)])
 
     def verify_sampled(self, drafts, want_probs=False):
         """gpt2_decode_verify_sampled: one speculative pass under sampling
