@@ -420,6 +420,11 @@ int  gpt2_decode_release(GPT2* model, int seq);
 int  gpt2_decode_fork(GPT2* model, int src, int dst, int n_tokens);
 /* free pages of the engine's manager (-1 without an engine) */
 int  gpt2_decode_free_pages(GPT2* model);
+/* where the engine keeps the manager's pages: out[i] = the pool slot (the page
+ * index of hip_paged_attn.h's pool layout) of manager page i, for i < n.  The
+ * map is a fixed permutation chosen at gpt2_decode_init.  Returns the number
+ * of entries written (min(n, the manager's max_blocks)), -1 without an engine. */
+int  gpt2_decode_page_slots(GPT2* model, int* out, int n);
 /* the same, but enqueue only (no host sync; next ids stay on device) */
 int  gpt2_decode_step_async(GPT2* model, const int* tokens);
 /* one eager step that also copies the residual stream entering every layer

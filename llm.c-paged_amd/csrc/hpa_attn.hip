@@ -201,6 +201,10 @@ static int attn_dispatch(const float* q, const HpaKVPool* pool, int layer, const
     HPA_REQUIRE(((uintptr_t)q & 15) == 0 && ((uintptr_t)out & 15) == 0, "q/out must be 16-byte aligned");
     HPA_REQUIRE(S >= 1 && S <= HPA_ATTN_MAX_SPLITS && (S == 1 || ws), "decode attention: splits 1..16, workspace");
     const bool bf = pool->dtype == HPA_BF16, f8 = pool->dtype == HPA_FP8;
+#if HPA_ATTN_SWP  // the pipelined fp32 tile loop forms its V offsets as 32-bit buffer offsets from the layer's base
+    HPA_REQUIRE(bf || f8 || pool->layer_elems * pool->elem_bytes < 0x7fffffffull,
+                "decode attention (HPA_ATTN_SWP): a layer's pages must be < 2 GiB (32-bit offsets)");
+#endif
     float* w = (float*)ws;
     HPA_REQUIRE(waves == 0 || waves == 1 || waves == 2 || waves == 4 || waves == 8, "attention waves 1, 2, 4, 8");
     const int nw = g_attn_waves ? g_attn_waves : waves ? waves : 4;

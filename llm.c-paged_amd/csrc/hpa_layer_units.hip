@@ -554,6 +554,10 @@ template <int NH, int P, bool BF, bool ATTN, int NB = 4, int NCD = 4, int NE = 4
 int launch(const HpaLayerArgs* h, int G) {
     HPA_REQUIRE((hpa::resident_blocks<decode_layer_kernel<NH, P, BF, ATTN, NB, NCD, NE>>(768) >= 1),
                 "decode layer: the persistent workgroup does not fit a CU");
+#if HPA_ATTN_SWP  // as hpa_attn.hip: 32-bit buffer offsets in the pipelined fp32 tile loop
+    HPA_REQUIRE(BF || !ATTN || h->pool->layer_elems * h->pool->elem_bytes < 0x7fffffffull,
+                "decode layer (HPA_ATTN_SWP): a layer's pages must be < 2 GiB (32-bit offsets)");
+#endif
     KA a;
     fill_ka(h, G, a);
     decode_layer_kernel<NH, P, BF, ATTN, NB, NCD, NE><<<G, 768, 0, hpa_stream()>>>(a);

@@ -3277,6 +3277,14 @@ int gpt2_decode_fork(GPT2* model, int src, int dst, int n_tokens) {
 
 int gpt2_decode_free_pages(GPT2* model) { return model->decode ? bm_free_pages(model->decode->bm) : -1; }
 
+int gpt2_decode_page_slots(GPT2* model, int* out, int n) {
+    GPT2Decode* d = model->decode;
+    if (!d || !d->pv.map || !out) return -1;
+    if (n > d->pool.num_pages) n = d->pool.num_pages;
+    for (int i = 0; i < n; i++) out[i] = d->pv.map[i];
+    return n < 0 ? 0 : n;
+}
+
 int gpt2_decode_step_async(GPT2* model, const int* tokens) { return dec_enqueue(model, tokens); }
 
 int gpt2_decode_step(GPT2* model, const int* tokens, int* next_tokens) {

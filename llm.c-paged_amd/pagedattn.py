@@ -252,6 +252,7 @@ def lib():
     _sig(L, "hpa_pool_copy_pages", i, [P, _I, _I, i])
     _sig(L, "gpt2_decode_fork", i, [v, i, i, i])
     _sig(L, "gpt2_decode_free_pages", i, [v])
+    _sig(L, "gpt2_decode_page_slots", i, [v, _I, i])
     # model + decode engine
     _sig(L, "gpt2_alloc", v, [])
     _sig(L, "gpt2_release", None, [v])
@@ -1240,6 +1241,14 @@ class Model:
     def free_pages(self):
         """free pages of the engine's block manager"""
         return lib().gpt2_decode_free_pages(self.h)
+
+    def page_slots(self, n):
+        """gpt2_decode_page_slots: the pool slot of each of the manager's pages 0 .. n-1"""
+        out = np.zeros(int(n), np.int32)
+        got = lib().gpt2_decode_page_slots(self.h, out.ctypes.data_as(_I), int(n))
+        if got < 0:
+            raise RuntimeError("page_slots: no engine")
+        return out[:got]
 
     def set_sampling(self, enable=True, seed=1337, filtered=False):
         """token choice: greedy (enable=False), the reference's multinomial

@@ -400,21 +400,38 @@ def prefill_cases(dtype, starts=PREFILL_STARTS, lens=(130, 130, 130, 130), seed=
 
 
 # ---------------------------------------------------------------- poisoned pools (GPU tests)
-def poisoned_pool(hip, cs, P, dtype, extra_pages=3, seed=0):
+def pages_needed(cs, P):
+    """pages poisoned_pool hands out for cs.seqs at page size P"""
+    return sum((k.shape[0] + P - 1) // P for k, _ in cs.seqs)
+
+
+def poisoned_pool(hip, cs, P, dtype, extra_pages=3, seed=0, num_pages=None, candidates=None):
     """a 1-layer pool holding cs.seqs with no clean byte outside the contexts:
     the whole slab 0xFF (a NaN in fp32, bf16 and e4m3fn) before anything is
     written, the slots past a context in its last page NaN, pages handed out
     in a random permutation, table entries past a sequence's pages -1.
+    num_pages: the pool's page count (default: the pages the sequences need
+    plus extra_pages).  candidates: the page indices the sequences may get
+    (default: every page), most wanted first -- the first pages_needed(cs, P)
+    of them are permuted and handed out, so a pool far larger than its
+    contents (tests/test_gpu_pool_large.py) places them where the caller says.
     Returns (pool, tables (n_seqs, maxp))."""
     L = hip.lib()
     npg = [(k.shape[0] + P - 1) // P for k, _ in cs.seqs]
-    num_pages = sum(npg) + extra_pages
+    if num_pages is None:
+        num_pages = sum(npg) + extra_pages
     pool = hip.Pool(1, NH, P, num_pages, dtype=dtype)
     hip.check(L.hpa_memset_async(pool.s.base, 0xFF, pool.s.bytes), "poison")
     hip.check(L.hpa_synchronize())
     if dtype == HPA_FP8:
         pool.set_scales(K_SCALE[None, :], V_SCALE[None, :])
-    perm = np.random.default_rng([seed, P, int(dtype)]).permutation(num_pages).astype(np.int32)
+    rng = np.random.default_rng([seed, P, int(dtype)])
+    if candidates is None:
+        perm = rng.permutation(num_pages).astype(np.int32)
+    else:
+        cand = np.asarray(candidates, np.int64).reshape(-1)[:sum(npg)]
+        assert cand.size == sum(npg) == np.unique(cand).size and cand.min() >= 0 and cand.max() < num_pages
+        perm = rng.permutation(cand).astype(np.int32)
     tables = np.full((len(cs.seqs), max(npg)), -1, np.int32)
     nxt = 0
     for si, (k, v) in enumerate(cs.seqs):

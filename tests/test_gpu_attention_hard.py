@@ -59,11 +59,13 @@ def _pool_id(p):
 
 
 class _Set:
-    """one poisoned pool with its case batch uploaded: shared by every test of the (dtype, P)"""
+    """one poisoned pool with its case batch uploaded: shared by every test of the (dtype, P);
+    pool_kw: attn_ref64.poisoned_pool's further arguments (tests/test_gpu_pool_large.py)"""
 
-    def __init__(self, hip, cs, P, dtype):
+    def __init__(self, hip, cs, P, dtype, **pool_kw):
         self.cs, self.P, self.dtype = cs, P, dtype
-        self.pool, tables = ar.poisoned_pool(hip, cs, P, dtype)
+        self.pool, tables = ar.poisoned_pool(hip, cs, P, dtype, **pool_kw)
+        self.tables = tables
         self.bt = np.ascontiguousarray(tables[cs.seq])  # a row's table is its sequence's (rows share pages)
         self.maxp = self.bt.shape[1]
         self.B = len(cs.seq)

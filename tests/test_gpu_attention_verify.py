@@ -43,9 +43,10 @@ def _drop_sets():
 
 
 class _Set:
-    """a case batch in a poisoned pool of page size P, its tables uploaded"""
+    """a case batch in a poisoned pool of page size P, its tables uploaded;
+    pool_kw: callable(cs) -> attn_ref64.poisoned_pool's further arguments (tests/test_gpu_pool_large.py)"""
 
-    def __init__(self, hip, starts, lens, P, dtype=ar.HPA_F32, seed=3):
+    def __init__(self, hip, starts, lens, P, dtype=ar.HPA_F32, seed=3, pool_kw=None):
         # a len = 0 sequence still owns a context (one row's worth) in the pool, so its table is real
         self.cs = ar.prefill_cases(dtype, starts=starts, lens=tuple(max(n, 1) for n in lens), seed=seed)
         self.lens = np.array(lens, np.int32)
@@ -54,7 +55,8 @@ class _Set:
         self.R = len(self.cs.seq)
         self.Rp = (self.R + 15) // 16 * 16
         self.P = P
-        self.pool, tables = ar.poisoned_pool(hip, self.cs, P, dtype)
+        self.pool, tables = ar.poisoned_pool(hip, self.cs, P, dtype, **(pool_kw(self.cs) if pool_kw else {}))
+        self.tables = tables
         self.maxp = tables.shape[1]
         self.d_q = hip.DeviceBuffer.from_array(self.cs.q)
         self.d_bt = hip.DeviceBuffer.from_array(np.ascontiguousarray(tables))

@@ -142,12 +142,14 @@ def _tree_cases(shape):
 
 
 class _Set:
-    """a shape's cases in a poisoned pool of page size P, tables uploaded"""
+    """a shape's cases in a poisoned pool of page size P, tables uploaded;
+    pool_kw: attn_ref64.poisoned_pool's further arguments (tests/test_gpu_pool_large.py)"""
 
-    def __init__(self, hip, shape, P, dtype=ar.HPA_F32):
+    def __init__(self, hip, shape, P, dtype=ar.HPA_F32, **pool_kw):
         self.cs = cs = _tree_cases(shape)
         self.Rp = (cs.R + 15) // 16 * 16
-        self.pool, tables = ar.poisoned_pool(hip, cs, P, dtype)
+        self.pool, tables = ar.poisoned_pool(hip, cs, P, dtype, **pool_kw)
+        self.tables = tables
         self.maxp = tables.shape[1]
         self.d_q = hip.DeviceBuffer.from_array(cs.q)
         self.d_bt = hip.DeviceBuffer.from_array(np.ascontiguousarray(tables))

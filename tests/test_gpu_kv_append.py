@@ -95,18 +95,21 @@ def _open(hip, C, NH, B, P, kv_bf16, w_bf16, select, form):
     return cfgd, params, m
 
 
-def _read_all(m, B, n):
-    return [[m.read_kv(l, b, int(n[b])) for b in range(B)] for l in range(L)]
+def _read_all(m, B, n, nl=L):
+    return [[m.read_kv(l, b, int(n[b])) for b in range(B)] for l in range(nl)]
 
 
-def _run_case(hip, C, NH, B, P, kv_bf16, w_bf16, select, form):
-    cfgd, params, m = _open(hip, C, NH, B, P, kv_bf16, w_bf16, select, form)
+def _run_case(hip, C, NH, B, P, kv_bf16, w_bf16, select, form, opener=_open):
+    """opener: what opens and initialises the engine (_open; tests/test_gpu_pool_large.py
+    passes one whose pool is large and whose model may have fewer layers)"""
+    cfgd, params, m = opener(hip, C, NH, B, P, kv_bf16, w_bf16, select, form)
+    nl = cfgd["L"]
     ref = ref64.Ref64(cfgd, params, w_bf16=w_bf16, kv_bf16=kv_bf16)
     rng = np.random.default_rng(1000 * C + 10 * B + P)
     pos = ref64.ragged_positions(B, P, F)
     ref64.check_position_mix(pos, P)
     m.fill_random(F, seed=C + B)
-    before = _read_all(m, B, np.full(B, F))
+    before = _read_all(m, B, np.full(B, F), nl)
     m.set_positions(pos)
     toks = rng.integers(0, cfgd["V"], (4, B)).astype(np.int32)
     xs = []
@@ -120,7 +123,7 @@ def _run_case(hip, C, NH, B, P, kv_bf16, w_bf16, select, form):
     assert np.array_equal(m.positions(), pos + 4)
     n_after = np.maximum(pos + 4, F)
     m.set_positions(n_after)  # keeps pages: only makes the rows readable again
-    after = _read_all(m, B, n_after)
+    after = _read_all(m, B, n_after, nl)
     m.close()
 
     # the ragged wpe lookup, exact
@@ -128,7 +131,7 @@ def _run_case(hip, C, NH, B, P, kv_bf16, w_bf16, select, form):
         assert np.array_equal(xs[s][0], ref.embed(toks[s], pos + s)), s
     # reference rows: traced steps on every layer, graph steps on layer 0
     refs = []
-    for l in range(L):
+    for l in range(nl):
         k = np.full((4, B, C), np.nan)
         v = np.full((4, B, C), np.nan)
         for s in range(4):
@@ -141,7 +144,7 @@ def _run_case(hip, C, NH, B, P, kv_bf16, w_bf16, select, form):
     # every layer of the traced steps on the pool's own K/V
     out_ratio = 0.0
     for s in range(2):
-        for l in range(L):
+        for l in range(nl):
             out = ref.layer_out(xs[s][l], l, [after[l][b][0] for b in range(B)], [after[l][b][1] for b in range(B)],
                                 pos + s + 1)
             got = xs[s][l + 1].astype(np.float64)

@@ -87,16 +87,25 @@ def _model_params(C, NH):
     return cfgd, _params[C]
 
 
-def _steps(hip, C, NH, B, P, kv, select, form, traced=True, attn_4_waves=False):
-    """two steps of a fresh engine from fill_random(F) at ragged positions.
-    traced: step_traced (the residual stream entering every layer), else plain
-    eager steps.  attn_4_waves: the attention launch as one range of 4 waves.
-    Returns (cfgd, params, pos, toks, xs, logits, before, after)."""
-    Lb = hip.lib()
-    kv_dtype = {"f32": hip.HPA_F32, "bf16": hip.HPA_BF16, "fp8": hip.HPA_FP8}[kv]
+def _open(hip, C, NH, B, P, kv_dtype):
+    """the engine of a case, initialised: (cfgd, params, model)"""
     cfgd, params = _model_params(C, NH)
     m = hip.Model(cfgd, params=params)
     m.decode_init(B, P, MAX_CTX, kv_dtype=kv_dtype)
+    return cfgd, params, m
+
+
+def _steps(hip, C, NH, B, P, kv, select, form, traced=True, attn_4_waves=False, opener=_open):
+    """two steps of a fresh engine from fill_random(F) at ragged positions.
+    traced: step_traced (the residual stream entering every layer), else plain
+    eager steps.  attn_4_waves: the attention launch as one range of 4 waves.
+    opener: what opens and initialises the engine (_open; tests/test_gpu_pool_large.py
+    passes one whose pool is large and whose model may have fewer layers).
+    Returns (cfgd, params, pos, toks, xs, logits, before, after)."""
+    Lb = hip.lib()
+    kv_dtype = {"f32": hip.HPA_F32, "bf16": hip.HPA_BF16, "fp8": hip.HPA_FP8}[kv]
+    cfgd, params, m = opener(hip, C, NH, B, P, kv_dtype)
+    nl = cfgd["L"]
     if select is not None:
         m.set_layer_kernel(select)
     assert m.layer_form() == form, (m.layer_form(), form)
@@ -104,13 +113,13 @@ def _steps(hip, C, NH, B, P, kv, select, form, traced=True, attn_4_waves=False):
     pos = ref64.ragged_positions(B, P, F)
     ref64.check_position_mix(pos, P)
     if kv == "fp8":
-        m.set_kv_scales(*_engine_scales(NH))  # every sequence at position 0
+        m.set_kv_scales(*(s[:nl] for s in _engine_scales(NH)))  # every sequence at position 0
     if attn_4_waves:
         m.set_attn_splits(1)
         hip.check(Lb.hpa_set_attention_waves(4), "waves")
     try:
         m.fill_random(F, seed=C + B)
-        before = [[m.read_kv(l, b, F) for b in range(B)] for l in range(L)]
+        before = [[m.read_kv(l, b, F) for b in range(B)] for l in range(nl)]
         m.set_positions(pos)
         toks = rng.integers(0, cfgd["V"], (2, B)).astype(np.int32)
         xs, logits = [], []
@@ -128,14 +137,15 @@ def _steps(hip, C, NH, B, P, kv, select, form, traced=True, attn_4_waves=False):
     assert np.array_equal(m.positions(), pos + 2)
     n_after = np.maximum(pos + 2, F)
     m.set_positions(n_after)  # keeps pages: only makes the rows readable again
-    after = [[m.read_kv(l, b, int(n_after[b])) for b in range(B)] for l in range(L)]
+    after = [[m.read_kv(l, b, int(n_after[b])) for b in range(B)] for l in range(nl)]
     m.close()
     return cfgd, params, pos, toks, xs, logits, before, after
 
 
-def _run_case(hip, C, NH, B, P, kv, select, form, attn_4_waves=False):
+def _run_case(hip, C, NH, B, P, kv, select, form, attn_4_waves=False, opener=_open):
     cfgd, params, pos, toks, xs, logits, before, after = _steps(hip, C, NH, B, P, kv, select, form,
-                                                                attn_4_waves=attn_4_waves)
+                                                                attn_4_waves=attn_4_waves, opener=opener)
+    nl = cfgd["L"]
     ref = ref64.Ref64(cfgd, params, kv_bf16=kv == "bf16")
     for s in range(2):
         assert np.array_equal(xs[s][0], ref.embed(toks[s], pos + s)), s
@@ -148,7 +158,7 @@ def _run_case(hip, C, NH, B, P, kv, select, form, attn_4_waves=False):
     refs = None
     if kv != "fp8":
         refs = []
-        for l in range(L):
+        for l in range(nl):
             rows = [ref.kv_rows_exact(xs[s][l], l) for s in range(2)]
             refs.append([(np.stack([rows[s][0][b] for s in range(2)]), np.stack([rows[s][1][b] for s in range(2)]))
                          for b in range(B)])
@@ -157,7 +167,7 @@ def _run_case(hip, C, NH, B, P, kv, select, form, attn_4_waves=False):
     bar = FP8_OUT_RTOL if kv == "fp8" else FP32_LAYER_RTOL
     worst, where = 0.0, None
     for s in range(2):
-        for l in range(L):
+        for l in range(nl):
             out = ref.layer_out(xs[s][l], l, [after[l][b][0] for b in range(B)], [after[l][b][1] for b in range(B)],
                                 pos + s + 1)
             got = xs[s][l + 1].astype(np.float64)
