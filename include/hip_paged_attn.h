@@ -200,6 +200,43 @@ int hpa_attn_pick_waves(int B, int num_heads, int splits, int num_cus);
 int hpa_paged_attention_decode_split(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
                                      int bt_stride, const int* pos, float* out, int B, int splits, void* ws,
                                      int out_frag);
+
+/* ---------------- shared-prefix decode attention (hpa_attn_shared.hip) ----
+ * out[b] is hpa_paged_attention_decode's: row b over keys 0 .. pos[b], the
+ * -10000 floor and the zero row included.  The device tables only decide which
+ * workgroup streams which tiles: a unit is up to HPA_SHARED_MAX_ROWS sequences
+ * that hold the SAME pages for tokens [0, 64 * unit_tiles) and have at least
+ * that many cached (gpt2_attn_shared_plan, paged_infer.h, builds them).
+ *   unit_members [max_units][HPA_SHARED_MAX_ROWS]  sequence indices, -1 padded
+ *   unit_tiles   [max_units]                       64-token tiles, 0 = unused
+ *   seq_skip     [B]                               the tiles b's unit streams, else 0
+ * Two launches on the current stream: the prefix launch, grid max_units x
+ * num_heads x prefix_splits, streams each unit's tiles once for all its
+ * members' rows (page ids from the first member's table row, no key masked)
+ * and writes the unnormalised (m, l, acc) of every (member, head, split) as a
+ * 68-float record into ws; the suffix launch, one workgroup per (sequence,
+ * head), is the decode kernel from tile seq_skip[b] on, whose final fold takes
+ * in b's records in split order ahead of its wave states.  No in-launch
+ * hand-off: the records cross the kernel boundary.  A launch repeats bit for
+ * bit; with every unit_tiles and seq_skip 0 (or max_units 0) the bits are
+ * hpa_paged_attention_decode_split_w(splits = 1) at the same waves, and so is
+ * every row outside the units.  ws: hpa_attn_shared_ws_bytes, 16-byte aligned,
+ * needs no zeroing.  waves: the suffix workgroup's (0: 4; 1, 2, 4, 8); the
+ * prefix workgroup has 8 waves when that is 8, else 4.
+ * Nonzero, nothing launched: a pool that is not fp32, head size != 64, a page
+ * size other than 8 / 16 / 32 / 64, prefix_splits outside 1 ..
+ * HPA_ATTN_MAX_SPLITS, a null or misaligned ws with max_units > 0. */
+#define HPA_SHARED_MAX_ROWS 8
+size_t hpa_attn_shared_ws_bytes(int B, int num_heads, int prefix_splits);
+/* the engine's prefix_splits, pure, by shape only (num_cus <= 0: 256): the
+ * smallest power of two at which units * num_heads * splits reaches two
+ * workgroups per CU, capped so that a range keeps about three of the largest
+ * unit's max_tiles tiles */
+int hpa_attn_shared_pick_splits(int units, int num_heads, int max_tiles, int num_cus);
+int hpa_paged_attention_decode_shared(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
+                                      int bt_stride, const int* pos, float* out, int B, const int* unit_members,
+                                      const int* unit_tiles, int max_units, const int* seq_skip, int prefix_splits,
+                                      void* ws, int out_frag, int waves);
 /* synthetic K/V fill of positions [0, ctx) for every sequence with U(-1,1)
  * from a counter-based hash (attention microbench / bench synthetic prefill) */
 int hpa_pool_fill_random(const HpaKVPool* pool, const int* block_table, int bt_stride, int B,

@@ -418,6 +418,72 @@ int  gpt2_decode_release(GPT2* model, int seq);
  * leaves the pages to the others.  gpt2_decode_fill_random* refuses while
  * pages are shared.  Waits for queued work like gpt2_decode_release. */
 int  gpt2_decode_fork(GPT2* model, int src, int dst, int n_tokens);
+/* ---------------- shared-prefix attention ----------------
+ * Forks of one prefix hold the same pages for it, and the decode attention
+ * still streams them once per sequence.  With this on (default off) the decode
+ * attention streams the leading 64-token tiles that a unit of up to
+ * HPA_SHARED_MAX_ROWS sequences hold in the same pages ONCE per unit
+ * (hpa_paged_attention_decode_shared, hip_paged_attn.h): a prefix launch and a
+ * suffix launch wherever the decode attention is its own launch (the five-launch
+ * loop and every form whose plan has attn_launch = 1, traced steps and
+ * gpt2_decode_time_attention included).  Outputs are the plain step's within
+ * fp32 rounding (another summation grouping); a sequence outside every unit
+ * gets the plain kernel's bits, and while no unit exists the step is the plain
+ * step, launch for launch.
+ *
+ * The plan, pure (no device, allocation or global).  block_table [B][bt_stride]:
+ * page ids, -1 for none; pos[b]: b's cached tokens.  common(a, b) = the
+ * leading i with bt[a][i] == bt[b][i] >= 0; share(a, b) = min(common *
+ * page_size, pos[a], pos[b]) / 64, whole 64-token tiles.
+ *   1. unassigned = every b with pos[b] >= 64, in index order;
+ *   2. the leader a = the lowest unassigned index;
+ *   3. its candidates = the unassigned b > a with share(a, b) >= min_tiles,
+ *      by share descending, then index ascending;
+ *   4. for k = 1 .. min(7, candidates), t_k = the k-th candidate's share: the
+ *      k with the largest k * t_k, the larger k on a tie;
+ *   5. k + 1 >= min_members: the unit (a, the first k candidates, tiles = t_k)
+ *      is emitted and its members leave the set; else a leaves alone;
+ *   6. from 2 until the set is empty.
+ * unit_members [max_units][HPA_SHARED_MAX_ROWS] (-1 padded), unit_tiles
+ * [max_units] (0 = unused), seq_skip[b] = the tiles of b's unit, else 0.
+ * Every unit: members pairwise identical in every page covering tokens
+ * [0, 64 * tiles), 64 * tiles <= pos[m] for each member, a sequence in at most
+ * one unit.  Returns the number of units; < 0 for a null pointer, B,
+ * bt_stride or page_size < 1, min_tiles < 1, min_members < 2 or max_units <
+ * B / 2. */
+int  gpt2_attn_shared_plan(const int* block_table, int bt_stride, const int* pos, int B, int page_size,
+                           int min_tiles, int min_members, int max_units, int* unit_members, int* unit_tiles,
+                           int* seq_skip);
+/* 1 on, 0 off (default).  Refused on a bf16 or fp8 pool (message, nonzero,
+ * nothing changed).  Toggling drops a captured graph.  The engine rebuilds
+ * its plan only while pages are shared and only after gpt2_decode_fork,
+ * gpt2_decode_release, gpt2_decode_reset, an eviction, a copy-on-write,
+ * gpt2_decode_set_positions or this call -- never in a plain step: appends add
+ * private pages at the end and positions only grow, so a plan stays valid
+ * across steps, prefill and verify passes (which are unchanged).  The tables
+ * are sized for B / 2 units and uploaded through pinned staging; a plan change
+ * keeps the graph unless it goes between no unit and some unit or changes the
+ * prefix launch's ranges (hpa_attn_shared_pick_splits).  Forms that run the
+ * attention inside a persistent launch (A/B builds) do not take it. */
+int  gpt2_decode_set_shared_attention(GPT2* model, int enable);
+int  gpt2_decode_shared_attention(GPT2* model);
+/* the plan in use: unit_of[b] = b's unit or -1, shared_tokens[b] = the tokens
+ * its unit streams for it (each nullable, [B]).  Returns the units (0 while
+ * off, while nothing is shared, or while the units cover fewer than
+ * min_covered sequences), -1 without an engine. */
+int  gpt2_decode_shared_plan(GPT2* model, int* unit_of, int* shared_tokens);
+/* the plan's min_tiles (>= 1) and min_members (>= 2), and min_covered (>= 2):
+ * a plan whose units hold fewer sequences than that is not used (no unit:
+ * the plain step).  The defaults are the measured ones, 15 / 2 / 64 (README
+ * "Shared-prefix attention": the two launches beat the one only where the
+ * whole batch of 64 shares long prefixes).  Takes effect at the next step. */
+int  gpt2_decode_set_shared_thresholds(GPT2* model, int min_tiles, int min_members, int min_covered);
+int  gpt2_decode_shared_thresholds(GPT2* model, int* min_tiles, int* min_members, int* min_covered);
+/* the prefix launch's ranges per (unit, head): 0 (default) by shape
+ * (hpa_attn_shared_pick_splits), else 1..HPA_ATTN_MAX_SPLITS (timing tools);
+ * takes effect at the next step.  And the value of the plan in use. */
+int  gpt2_decode_set_shared_splits(GPT2* model, int splits);
+int  gpt2_decode_shared_splits(GPT2* model);
 /* free pages of the engine's manager (-1 without an engine) */
 int  gpt2_decode_free_pages(GPT2* model);
 /* where the engine keeps the manager's pages: out[i] = the pool slot (the page

@@ -665,6 +665,23 @@ struct GPT2Decode {
     int attn_waves;   /* waves per attention workgroup (hpa_attn_pick_waves of the global batch) */
     void* d_attn_ws;  /* split records + counters (hpa_attn_ws_bytes at HPA_ATTN_MAX_SPLITS) */
     size_t attn_ws_bytes;
+    /* shared-prefix attention (gpt2_decode_set_shared_attention), allocated on
+     * first enable: the plan's device tables d_sh = members [sh_max][HPA_SHARED_MAX_ROWS],
+     * tiles [sh_max], skip [B] (sh_max = the worst case, B / 2 units), their
+     * double-buffered pinned staging (as h_bt) and the prefix records.  The plan
+     * in use: sh_units units (0: the step is the plain step) of h_sh_plan (the
+     * tables' host copy), streamed over sh_splits ranges.  sh_dirty: an event
+     * that can change leading pages or lower a position happened since the plan
+     * was built (dec_shared_sync rebuilds it before the next launch). */
+    int sh_on, sh_dirty, sh_units, sh_splits, sh_max;
+    int sh_want_splits; /* gpt2_decode_set_shared_splits: 0 by shape, else 1..HPA_ATTN_MAX_SPLITS */
+    int sh_min_tiles, sh_min_members, sh_min_covered;
+    int* d_sh;
+    int* h_sh[2];
+    void* ev_sh[2];
+    int sh_k;
+    int* h_sh_plan;
+    void* d_sh_ws;
     int sample;       /* 0: greedy argmax; 1: multinomial with per-sequence xorshift; 2: filtered */
     unsigned long long* d_rng; /* [B] sampler states */
     float* d_samp_t;  /* [B] per-sequence temperature, top-k, top-p (read by mode 2 only) */
@@ -937,6 +954,12 @@ static void dec_free(GPT2Decode* d) {
     hpa_free(d->d_wpack);
     hpa_free(d->d_fold);
     hpa_free(d->d_attn_ws);
+    hpa_free(d->d_sh); hpa_free(d->d_sh_ws);
+    for (int k = 0; k < 2; k++) {
+        if (d->ev_sh[k]) hpa_event_destroy(d->ev_sh[k]);
+        if (d->h_sh[k]) hpa_host_free(d->h_sh[k]);
+    }
+    free(d->h_sh_plan);
     hpa_free(d->pl_rec); hpa_free(d->pl_slab); hpa_free(d->pl_ctr);
     hpa_free(d->d_pipe_lay); hpa_free(d->pipe_slab);
     hpa_free(d->d_rng);
@@ -1072,6 +1095,22 @@ static int dec_pick_B(const GPT2Decode* d) {
     const int lim = d->w_bf16 ? 256 : 64;
     return d->pl_global_B > 0 && d->pl_global_B <= lim ? d->pl_global_B : d->B;
 }
+
+/* the shared-prefix plan's thresholds (gpt2_decode_set_shared_thresholds
+ * overrides them): units form only where the measurement showed the two
+ * launches beat the one the caches already serve (GPT-2 124M, page 16, ctx
+ * 1000, profiles/r16/shared_attention.txt).  At B = 64 with every sequence in
+ * a unit and 15 shared tiles: 29.1 -> 25.7 us (1 x 64 forks), 39.2 -> 29.1
+ * (8 x 8), 60.9 -> 41.2 (32 x 2); at 12 tiles 8 x 8 and 32 x 2 still win and
+ * 1 x 64 loses (34.5 -> 35.1), at 8 tiles only 32 x 2 wins, at 4 none.  With
+ * fewer sequences in units it loses at every shape measured: 32 of 64 42.4 ->
+ * 50.0, 16 of 64 50.3 -> 65.9, 8 of 64 55.3 -> 69.6, and the whole batch at
+ * B = 32 (17.3 -> 21.1), 16 (12.1 -> 19.8) and 8 (9.5 -> 23.7): the second
+ * launch costs more than the prefix's loads, which mostly hit in cache.  So:
+ * 15 tiles, and the plan is used only when its units cover 64 sequences. */
+#define DEC_SHARED_MIN_TILES 15
+#define DEC_SHARED_MIN_MEMBERS 2
+#define DEC_SHARED_MIN_COVERED 64
 
 /* ints after the per-layer counter blocks: the step's own error word (zeroed
  * with the counters, so one timed-out wait cannot make later steps bail out;
@@ -1411,6 +1450,10 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
     gpt2_decode_free(model);
     GPT2Decode* d = (GPT2Decode*)calloc(1, sizeof(GPT2Decode));
     if (!d) return 1;
+    d->sh_min_tiles = DEC_SHARED_MIN_TILES;
+    d->sh_min_members = DEC_SHARED_MIN_MEMBERS;
+    d->sh_min_covered = DEC_SHARED_MIN_COVERED;
+    d->sh_splits = 1;
     if (model->manager) {
         d->bm = model->manager;
         page_size = d->bm->block_size;
@@ -1624,6 +1667,7 @@ static int dec_note_eviction(GPT2Decode* d, int ev, const int* busy, int* evicte
     if (evicted) ++*evicted;
     d->h_evicted[ev] = 1;
     d->h_pos[ev] = 0;
+    d->sh_dirty = 1;
     if (hpa_memcpy(d->d_pos + ev, &d->h_pos[ev], sizeof(int))) return 1;
     if (dec_pr_zero(d, ev)) return 1;
     if (busy && busy[ev]) {
@@ -1644,6 +1688,7 @@ static int dec_unshare(GPT2Decode* d, int b, int first, int last, const int* bus
         int old = -1;
         if (bm_page_refs(d->bm, d->bm->prompt_block_list[b][i]) <= 1) continue;
         const int fresh = bm_make_private(d->bm, b, i, &old);
+        d->sh_dirty = 1;
         if (dec_note_eviction(d, d->bm->last_evicted_prompt, busy, evicted)) return 1;
         if (fresh < 0) {
             if (d->bm->last_evicted_prompt == b) return 0; /* b restarts at 0 without pages: nothing left to copy */
@@ -1835,9 +1880,132 @@ static int dec_pick_ex(GPT2* model, const int* active, const int* exclude) {
 
 static int dec_pick(GPT2* model, const int* active) { return dec_pick_ex(model, active, NULL); }
 
+/* ---- shared-prefix attention: the plan ----
+ * Which sequences stream their leading tiles together (hip_paged_attn.h,
+ * hpa_paged_attention_decode_shared).  Pure: no device, no allocation, no
+ * global.  paged_infer.h states the algorithm. */
+static int shared_tiles(const int* bt, int bt_stride, const int* pos, int P, int a, int b) {
+    const int lim = pos[a] < pos[b] ? pos[a] : pos[b];
+    const int* ra = bt + (size_t)a * bt_stride;
+    const int* rb = bt + (size_t)b * bt_stride;
+    int common = 0; /* leading pages both hold; pages past `lim` tokens cannot raise the share */
+    while (common < bt_stride && common * P < lim && ra[common] >= 0 && ra[common] == rb[common]) common++;
+    const int tok = common * P < lim ? common * P : lim;
+    return tok / 64;
+}
+
+int gpt2_attn_shared_plan(const int* block_table, int bt_stride, const int* pos, int B, int page_size, int min_tiles,
+                          int min_members, int max_units, int* unit_members, int* unit_tiles, int* seq_skip) {
+    enum { MR = HPA_SHARED_MAX_ROWS };
+    if (!block_table || !pos || !unit_members || !unit_tiles || !seq_skip) return -1;
+    if (B <= 0 || bt_stride <= 0 || page_size <= 0 || min_tiles < 1 || min_members < 2) return -1;
+    if (max_units < B / 2 || max_units < 0) return -1;
+    for (int i = 0; i < max_units * MR; i++) unit_members[i] = -1;
+    for (int i = 0; i < max_units; i++) unit_tiles[i] = 0;
+    /* seq_skip doubles as the unassigned set until the end: -1 unassigned, else b's tiles */
+    for (int b = 0; b < B; b++) seq_skip[b] = pos[b] >= 64 ? -1 : 0;
+    int units = 0;
+    for (int a = 0; a < B; a++) {
+        if (seq_skip[a] != -1) continue;
+        /* the 7 best candidates: share descending, then index ascending (b ascends, so a tie stays behind) */
+        int cand[MR - 1], share[MR - 1], nc = 0;
+        for (int b = a + 1; b < B; b++) {
+            if (seq_skip[b] != -1) continue;
+            const int t = shared_tiles(block_table, bt_stride, pos, page_size, a, b);
+            if (t < min_tiles) continue;
+            int at = nc;
+            while (at > 0 && share[at - 1] < t) at--;
+            if (at >= MR - 1) continue;
+            if (nc < MR - 1) nc++;
+            for (int j = nc - 1; j > at; j--) {
+                cand[j] = cand[j - 1];
+                share[j] = share[j - 1];
+            }
+            cand[at] = b;
+            share[at] = t;
+        }
+        int best_k = 0;
+        long best = -1;
+        for (int k = 1; k <= nc; k++)
+            if ((long)k * share[k - 1] >= best) { /* a tie: the larger k */
+                best = (long)k * share[k - 1];
+                best_k = k;
+            }
+        seq_skip[a] = 0;
+        if (best_k == 0 || best_k + 1 < min_members || units >= max_units) continue;
+        const int t = share[best_k - 1];
+        unit_members[units * MR] = a;
+        for (int k = 0; k < best_k; k++) {
+            unit_members[units * MR + 1 + k] = cand[k];
+            seq_skip[cand[k]] = t;
+        }
+        seq_skip[a] = t;
+        unit_tiles[units++] = t;
+    }
+    return units;
+}
+
+/* prefix_splits of the plan in use: by shape only (units, heads, the largest unit's tiles, CUs) */
+static int dec_shared_pick_splits(const GPT2Decode* d, int units) {
+    if (d->sh_want_splits) return d->sh_want_splits;
+    int ncu = 0, max_tiles = 0;
+    hpa_device_info(NULL, 0, &ncu, NULL);
+    for (int u = 0; u < units; u++) {
+        const int t = d->h_sh_plan[d->sh_max * HPA_SHARED_MAX_ROWS + u];
+        if (t > max_tiles) max_tiles = t;
+    }
+    return hpa_attn_shared_pick_splits(units, d->pool.num_heads, max_tiles, ncu);
+}
+
+/* the plan up to date with the pages and positions: rebuilt only after an
+ * event that can change a leading page or lower a position (sh_dirty: fork,
+ * release, reset, eviction, dec_unshare, set_positions, the toggle) -- a plain
+ * step only appends private pages and raises positions, which keeps every
+ * unit's invariants.  The manager's page ids serve as well as the pool slots
+ * (a permutation of them: equality is all the plan asks).  The tables go up
+ * through the pinned staging; a captured graph is dropped where the step's
+ * launches change: between no unit and some unit, or another prefix_splits. */
+static int dec_shared_sync(GPT2Decode* d) {
+    if (!d->sh_dirty) return 0;
+    d->sh_dirty = 0;
+    const int B = d->B, MR = HPA_SHARED_MAX_ROWS, n_int = d->sh_max * (MR + 1) + B;
+    int units = 0;
+    if (d->sh_on && bm_shared_pages(d->bm)) {
+        units = gpt2_attn_shared_plan(d->bm->block_table, d->bt_stride, d->h_pos, B, d->P, d->sh_min_tiles,
+                                      d->sh_min_members, d->sh_max, d->h_sh_plan, d->h_sh_plan + d->sh_max * MR,
+                                      d->h_sh_plan + d->sh_max * (MR + 1));
+        if (units < 0) return 1;
+        int covered = 0; /* sequences in units: below sh_min_covered the plain step is the faster one */
+        for (int b = 0; b < B; b++) covered += d->h_sh_plan[d->sh_max * (MR + 1) + b] > 0;
+        if (covered < d->sh_min_covered) units = 0;
+    }
+    const int splits = units ? dec_shared_pick_splits(d, units) : d->sh_splits;
+    if (d->graph && ((units != 0) != (d->sh_units != 0) || splits != d->sh_splits)) {
+        if (hpa_synchronize()) return 1;
+        hpa_graph_destroy(d->graph);
+        d->graph = NULL;
+        if (dec_rezero(d)) return 1;
+    }
+    d->sh_units = units;
+    d->sh_splits = splits;
+    if (!units) return 0;
+    const int k = d->sh_k;
+    if (hpa_event_synchronize(d->ev_sh[k])) return 1;
+    memcpy(d->h_sh[k], d->h_sh_plan, n_int * sizeof(int));
+    if (hpa_memcpy_async(d->d_sh, d->h_sh[k], n_int * sizeof(int)) || hpa_event_record(d->ev_sh[k])) return 1;
+    d->sh_k ^= 1;
+    return 0;
+}
+
 /* one decode-attention launch: the (sequence, head, context range) grid,
- * frag output */
+ * frag output; while the shared-prefix plan has a unit, its two launches */
 static int dec_attn_call(GPT2Decode* d, int l, const int* pos, float* out) {
+    if (d->sh_units) {
+        const int MR = HPA_SHARED_MAX_ROWS;
+        return hpa_paged_attention_decode_shared(d->d_q, &d->pool, l, d->d_bt, d->bt_stride, pos, out, d->B, d->d_sh,
+                                                 d->d_sh + d->sh_max * MR, d->sh_max, d->d_sh + d->sh_max * (MR + 1),
+                                                 d->sh_splits, d->d_sh_ws, 1, d->attn_waves);
+    }
     return hpa_paged_attention_decode_split_w(d->d_q, &d->pool, l, d->d_bt, d->bt_stride, pos, out, d->B,
                                               d->attn_splits, d->d_attn_ws, 1, d->attn_waves);
 }
@@ -2377,6 +2545,98 @@ int gpt2_decode_attn_splits(GPT2* model) { return model->decode ? model->decode-
 /* waves per attention workgroup the engine picked (hpa_set_attention_waves may override it) */
 int gpt2_decode_attn_waves(GPT2* model) { return model->decode ? model->decode->attn_waves : 0; }
 
+/* shared-prefix attention on / off (paged_infer.h); the buffers on first enable */
+int gpt2_decode_set_shared_attention(GPT2* model, int enable) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (enable && (d->pool.dtype != HPA_F32 || d->pool.head_size != 64)) {
+        fprintf(stderr, "[paged_infer] shared attention: fp32 KV pools with head size 64 only\n");
+        return 1;
+    }
+    if (hpa_synchronize()) return 1;
+    if (enable && !d->d_sh) {
+        const int MR = HPA_SHARED_MAX_ROWS;
+        d->sh_max = d->B / 2 > 0 ? d->B / 2 : 1;
+        const size_t n_int = (size_t)d->sh_max * (MR + 1) + d->B;
+        d->d_sh = (int*)hpa_malloc(n_int * sizeof(int));
+        d->d_sh_ws = hpa_malloc(hpa_attn_shared_ws_bytes(d->B, d->pool.num_heads, HPA_ATTN_MAX_SPLITS));
+        d->h_sh_plan = (int*)calloc(n_int, sizeof(int));
+        for (int k = 0; k < 2; k++) {
+            d->h_sh[k] = (int*)hpa_host_alloc(n_int * sizeof(int));
+            d->ev_sh[k] = hpa_event_create_nt();
+        }
+        if (!d->d_sh || !d->d_sh_ws || !d->h_sh_plan || !d->h_sh[0] || !d->h_sh[1] || !d->ev_sh[0] || !d->ev_sh[1]) {
+            hpa_free(d->d_sh);
+            d->d_sh = NULL; /* the rest is freed with the engine; the next enable starts over */
+            return 1;
+        }
+        if (hpa_memset_async(d->d_sh, 0, n_int * sizeof(int))) return 1;
+    }
+    if (d->sh_on == (enable != 0)) return 0;
+    d->sh_on = enable != 0;
+    d->sh_dirty = 1;
+    if (d->graph) { /* recapture with the other attention */
+        hpa_graph_destroy(d->graph);
+        d->graph = NULL;
+        if (dec_rezero(d)) return 1;
+    }
+    return dec_shared_sync(d);
+}
+
+int gpt2_decode_shared_attention(GPT2* model) { return model && model->decode ? model->decode->sh_on : 0; }
+
+int gpt2_decode_set_shared_thresholds(GPT2* model, int min_tiles, int min_members, int min_covered) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (min_tiles < 1 || min_members < 2 || min_covered < 2) {
+        fprintf(stderr, "[paged_infer] shared attention: min_tiles >= 1, min_members >= 2, min_covered >= 2\n");
+        return 1;
+    }
+    d->sh_min_tiles = min_tiles;
+    d->sh_min_members = min_members;
+    d->sh_min_covered = min_covered;
+    d->sh_dirty = 1;
+    return 0;
+}
+
+int gpt2_decode_shared_thresholds(GPT2* model, int* min_tiles, int* min_members, int* min_covered) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) return 1;
+    if (min_tiles) *min_tiles = d->sh_min_tiles;
+    if (min_members) *min_members = d->sh_min_members;
+    if (min_covered) *min_covered = d->sh_min_covered;
+    return 0;
+}
+
+int gpt2_decode_shared_plan(GPT2* model, int* unit_of, int* shared_tokens) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) return -1;
+    if (dec_shared_sync(d)) return -1;
+    for (int b = 0; b < d->B; b++) {
+        if (unit_of) unit_of[b] = -1;
+        if (shared_tokens) shared_tokens[b] = 0;
+    }
+    const int MR = HPA_SHARED_MAX_ROWS;
+    for (int u = 0; u < d->sh_units; u++)
+        for (int r = 0; r < MR; r++) {
+            const int b = d->h_sh_plan[u * MR + r];
+            if (b < 0) break;
+            if (unit_of) unit_of[b] = u;
+            if (shared_tokens) shared_tokens[b] = 64 * d->h_sh_plan[d->sh_max * MR + u];
+        }
+    return d->sh_units;
+}
+
+int gpt2_decode_set_shared_splits(GPT2* model, int splits) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d || splits < 0 || splits > HPA_ATTN_MAX_SPLITS) return 1;
+    d->sh_want_splits = splits;
+    d->sh_dirty = 1;
+    return 0;
+}
+
+int gpt2_decode_shared_splits(GPT2* model) { return model && model->decode ? model->decode->sh_splits : 0; }
+
 static int dec_enqueue(GPT2* model, const int* tokens) {
     GPT2Decode* d = model->decode;
     if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
@@ -2389,6 +2649,7 @@ static int dec_enqueue(GPT2* model, const int* tokens) {
     }
     if (dec_ensure_pages(d)) return 1;
     if (dec_sync_block_table(d)) return 1;
+    if (dec_shared_sync(d)) return 1;
     if (tokens && dec_upload_tokens(d, tokens)) return 1;
     if (d->use_graph && !d->profiling && !d->trace_x) {
         if (!d->graph) {
@@ -3204,6 +3465,7 @@ int gpt2_decode_release(GPT2* model, int seq) {
     if (hpa_synchronize()) return 1; /* the pages may still be read by queued work */
     if (d->bm->prompt_block_count[seq]) free_blocks_for_prompt(d->bm, seq);
     d->h_pos[seq] = 0;
+    d->sh_dirty = 1;
     if (hpa_memcpy(d->d_pos + seq, &d->h_pos[seq], sizeof(int))) return 1;
     if (dec_pr_zero(d, seq)) return 1;
     return dec_sync_block_table(d);
@@ -3237,6 +3499,7 @@ int gpt2_decode_fork(GPT2* model, int src, int dst, int n_tokens) {
         return 1;
     }
     if (hpa_synchronize()) return 1; /* as gpt2_decode_release: queued work may still use the pages */
+    d->sh_dirty = 1;
     if (bm_fork_prompt(d->bm, src, dst, full)) return 1;
     if (tail) {
         const int from = d->pv.map[d->bm->prompt_block_list[src][full]];
@@ -3391,6 +3654,7 @@ int gpt2_decode_reset(GPT2* model) {
         if (d->bm->prompt_block_count[b]) free_blocks_for_prompt(d->bm, b);
         d->h_pos[b] = 0;
     }
+    d->sh_dirty = 1;
     if (hpa_memset_async(d->d_pos, 0, d->B * sizeof(int))) return 1;
     if (d->proc) {
         if (hpa_memset_async(d->pr_cnt, 0, dec_pr_cnt_bytes(d))) return 1;
@@ -3569,6 +3833,7 @@ int gpt2_decode_time_attention(GPT2* model, int iters, double* ms_per_launch, do
             fprintf(stderr, "[paged_infer] time_attention: run a step first\n");
             return 1;
         }
+    if (dec_shared_sync(d)) return 1;
     int* d_p = (int*)hpa_malloc(B * sizeof(int));
     int* h_p = (int*)malloc(B * sizeof(int));
     float* out = (float*)hpa_malloc(hpa_frag_elems(B, C) * sizeof(float));
@@ -4045,6 +4310,7 @@ int gpt2_decode_set_positions(GPT2* model, const int* pos) {
     for (int b = 0; b < d->B; b++) {
         const int moved = d->h_pos[b] != pos[b];
         d->h_pos[b] = pos[b];
+        if (moved) d->sh_dirty = 1;
         if (moved && dec_pr_recount(d, b)) return 1;
     }
     return hpa_memcpy(d->d_pos, d->h_pos, d->B * sizeof(int));

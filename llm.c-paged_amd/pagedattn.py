@@ -215,6 +215,9 @@ def lib():
     _sig(L, "hpa_attn_pick_splits", i, [i, i, i, i])
     _sig(L, "hpa_paged_attention_decode_split", i, [v, P, i, v, i, v, v, i, i, v, i])
     _sig(L, "hpa_paged_attention_decode_split_w", i, [v, P, i, v, i, v, v, i, i, v, i, i])
+    _sig(L, "hpa_attn_shared_ws_bytes", sz, [i, i, i])
+    _sig(L, "hpa_attn_shared_pick_splits", i, [i, i, i, i])
+    _sig(L, "hpa_paged_attention_decode_shared", i, [v, P, i, v, i, v, v, i, v, v, i, v, i, v, i, i])
     _sig(L, "hpa_comm_id_bytes", sz, [])
     _sig(L, "hpa_comm_unique_id", i, [v, sz])
     _sig(L, "hpa_comm_init", i, [i, i, v])
@@ -323,6 +326,14 @@ def lib():
     _sig(L, "gpt2_decode_verify_sampled", i, [v, _I, _I, _I, _I, _F])
     _sig(L, "gpt2_decode_verify_plan", i, [i, i, i, i, i])
     _sig(L, "gpt2_decode_set_verify_attention", i, [v, i])
+    _sig(L, "gpt2_attn_shared_plan", i, [_I, i, _I, i, i, i, i, i, _I, _I, _I])
+    _sig(L, "gpt2_decode_set_shared_attention", i, [v, i])
+    _sig(L, "gpt2_decode_shared_attention", i, [v])
+    _sig(L, "gpt2_decode_shared_plan", i, [v, _I, _I])
+    _sig(L, "gpt2_decode_set_shared_thresholds", i, [v, i, i, i])
+    _sig(L, "gpt2_decode_shared_thresholds", i, [v, _I, _I, _I])
+    _sig(L, "gpt2_decode_shared_splits", i, [v])
+    _sig(L, "gpt2_decode_set_shared_splits", i, [v, i])
     _sig(L, "gpt2_ngram_draft", i, [_I, i, i, i, i, _I])
     _U8 = ctypes.POINTER(ctypes.c_ubyte)
     _sig(L, "hpa_paged_attention_verify_tree", i, [_F, v, i, _I, i, _I, _I, _I, _U8, i, i, _F])
@@ -466,6 +477,33 @@ def verify_plan(max_rows, kv_dtype=0, page_size=16, head_size=64, request=0):
     0 auto, 1 the prefill kernel, 2 the verify kernel where it applies"""
     return int(lib().gpt2_decode_verify_plan(int(max_rows), int(kv_dtype), int(page_size), int(head_size),
                                              int(request)))
+
+
+SHARED_MAX_ROWS = 8  # HPA_SHARED_MAX_ROWS
+
+
+def attn_shared_plan(block_table, pos, page_size, min_tiles=1, min_members=2, max_units=None):
+    """gpt2_attn_shared_plan (host only, pure): which sequences stream their
+    leading 64-token tiles together.  block_table [B][stride] page ids (-1: none),
+    pos [B] cached tokens.  Returns (units, unit_members [max_units][8] -1 padded,
+    unit_tiles [max_units], seq_skip [B]); raises on arguments the C side refuses"""
+    bt = np.ascontiguousarray(np.asarray(block_table, np.int32))
+    if bt.ndim != 2:
+        raise ValueError("attn_shared_plan: block_table [B][stride]")
+    B, stride = bt.shape
+    ps = np.ascontiguousarray(np.asarray(pos, np.int32).reshape(-1))
+    if ps.size != B:
+        raise ValueError("attn_shared_plan: one position per table row")
+    mu = max(B // 2, 1) if max_units is None else int(max_units)
+    members = np.full((max(mu, 1), SHARED_MAX_ROWS), -1, np.int32)
+    tiles = np.zeros(max(mu, 1), np.int32)
+    skip = np.zeros(B, np.int32)
+    n = lib().gpt2_attn_shared_plan(bt.ctypes.data_as(_I), int(stride), ps.ctypes.data_as(_I), int(B), int(page_size),
+                                    int(min_tiles), int(min_members), mu, members.ctypes.data_as(_I),
+                                    tiles.ctypes.data_as(_I), skip.ctypes.data_as(_I))
+    if n < 0:
+        raise RuntimeError("gpt2_attn_shared_plan: bad arguments")
+    return int(n), members, tiles, skip
 
 
 def ngram_draft(history, k, max_ngram=3, min_ngram=1):
@@ -1237,6 +1275,47 @@ class Model:
         them dst also inherits src's pending next id (step(None) continues
         both); its sampler state stays its own."""
         check(lib().gpt2_decode_fork(self.h, int(src), int(dst), int(n_tokens)), "fork")
+
+    def set_shared_attention(self, on=True, min_tiles=None, min_members=None, min_covered=None):
+        """gpt2_decode_set_shared_attention: the decode attention streams the
+        leading 64-token tiles that up to 8 forks hold in the same pages once
+        per unit (fp32 pools only; raises on a bf16 / fp8 pool).  min_tiles /
+        min_members / min_covered override the plan's measured thresholds
+        (15 tiles, 2 members, units covering 64 sequences)."""
+        if min_tiles is not None or min_members is not None or min_covered is not None:
+            t, m, c = self.shared_thresholds()
+            check(lib().gpt2_decode_set_shared_thresholds(self.h, int(t if min_tiles is None else min_tiles),
+                                                          int(m if min_members is None else min_members),
+                                                          int(c if min_covered is None else min_covered)),
+                  "set_shared_thresholds")
+        check(lib().gpt2_decode_set_shared_attention(self.h, int(bool(on))), "set_shared_attention")
+
+    def shared_attention(self):
+        return bool(lib().gpt2_decode_shared_attention(self.h))
+
+    def shared_thresholds(self):
+        """the plan's (min_tiles, min_members, min_covered)"""
+        t, m, c = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        check(lib().gpt2_decode_shared_thresholds(self.h, ctypes.byref(t), ctypes.byref(m), ctypes.byref(c)),
+              "shared_thresholds")
+        return t.value, m.value, c.value
+
+    def shared_plan(self):
+        """gpt2_decode_shared_plan: (units, unit_of [B] (-1: none), shared_tokens [B])"""
+        unit_of = np.zeros(self.B, np.int32)
+        tok = np.zeros(self.B, np.int32)
+        n = lib().gpt2_decode_shared_plan(self.h, unit_of.ctypes.data_as(_I), tok.ctypes.data_as(_I))
+        if n < 0:
+            raise RuntimeError("shared_plan: no engine")
+        return int(n), unit_of, tok
+
+    def shared_splits(self):
+        """ranges per (unit, head) of the prefix launch of the plan in use"""
+        return int(lib().gpt2_decode_shared_splits(self.h))
+
+    def set_shared_splits(self, splits):
+        """0: by shape (hpa_attn_shared_pick_splits), else 1..16"""
+        check(lib().gpt2_decode_set_shared_splits(self.h, int(splits)), "set_shared_splits")
 
     def free_pages(self):
         """free pages of the engine's block manager"""
