@@ -20,7 +20,7 @@
  *                 [--temperature X] [--top-k N] [--top-p X] [--perplexity] [--logprobs]
  *                 [--speculate K] [--speculate-sampled K] [--repetition-penalty R] [--presence-penalty X]
  *                 [--frequency-penalty X] [--ban ID]... [--top-logprobs K]
- *                 [--speculate-tree N] [--tree-depth D] [--tree-branches W]
+ *                 [--speculate-tree N] [--tree-depth D] [--tree-branches W] [--speculate-tree-sampled N]
  *     -g greedy (default: sampling as the reference), -o writes the B x
  *     (prompt + new) token ids as int32, -q prints only the summary line.
  *     --temperature / --top-k / --top-p: any of them selects filtered
@@ -52,6 +52,15 @@
  *     many (sequence, pass) pairs continued from a node that was not on the
  *     tree's first branch (what a chain draft would have lost).  Exclusive with
  *     --speculate, --speculate-sampled, sampling and processor flags.
+ *     --speculate-tree-sampled N (1..7 nodes, without -g; with --tree-depth,
+ *     --tree-branches, --temperature, --top-k, --top-p): the tree loop under
+ *     filtered sampling (mode 2).  gpt2_decode_verify_tree_sampled examines the
+ *     children of a node in turn, each against what the siblings rejected
+ *     before it left of the node's distribution, and draws the sequence's own
+ *     token from the rest: the emitted tokens are distributed as token-by-token
+ *     sampling.  Reports the passes that continued off the first branch like
+ *     --speculate-tree.  Not with -g, the other --speculate flags or the
+ *     penalty flags.
  *     --repetition-penalty R (> 0, 1 = off; the HF rule), --presence-penalty X,
  *     --frequency-penalty X (0 = off; the OpenAI rule) and --ban ID (repeatable,
  *     up to HPA_LOGIT_BIAS_MAX ids that are never produced): any of them turns
@@ -113,7 +122,7 @@ int main(int argc, char** argv) {
     const char *ckpt = NULL, *tok_path = NULL, *tokens_path = NULL, *ids_out = NULL;
     int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
     int perplexity = 0, logprobs = 0, speculate = 0, spec_sampled = 0, top_lp = 0;
-    int spec_tree = 0, spec_chain = 0, tree_depth = 4, tree_branches = 3;
+    int spec_tree = 0, spec_chain = 0, tree_depth = 4, tree_branches = 3, tree_flags = 0;
     float temperature = 1.0f, top_p = 1.0f;
     int processors = 0, n_ban = 0, ban[HPA_LOGIT_BIAS_MAX];
     float repetition = 1.0f, presence = 0.0f, frequency = 0.0f, ban_value[HPA_LOGIT_BIAS_MAX];
@@ -137,7 +146,12 @@ int main(int argc, char** argv) {
         else if (!strcmp(a, "--top-p")) { top_p = (float)atof(v); filtered = 1; }
         else if (!strcmp(a, "--speculate")) { speculate = atoi(v); spec_chain = 1; }
         else if (!strcmp(a, "--speculate-sampled")) { speculate = atoi(v); spec_chain = spec_sampled = filtered = 1; }
-        else if (!strcmp(a, "--speculate-tree")) { speculate = atoi(v); spec_tree = 1; }
+        else if (!strcmp(a, "--speculate-tree")) { speculate = atoi(v); spec_tree = 1; tree_flags++; }
+        else if (!strcmp(a, "--speculate-tree-sampled")) {
+            speculate = atoi(v);
+            spec_tree = spec_sampled = filtered = 1;
+            tree_flags += 2;
+        }
         else if (!strcmp(a, "--tree-depth")) tree_depth = atoi(v);
         else if (!strcmp(a, "--tree-branches")) tree_branches = atoi(v);
         else if (!strcmp(a, "--top-logprobs")) {
@@ -159,10 +173,10 @@ int main(int argc, char** argv) {
         else { fprintf(stderr, "unknown option %s\n", a); return 2; }
         i++;
     }
-    if (spec_tree && (spec_chain || speculate < 1 || speculate > HPA_VERIFY_MAX_ROWS - 1 || tree_depth < 1 ||
+    if (spec_tree && (spec_chain || tree_flags > 2 || speculate < 1 || speculate > HPA_VERIFY_MAX_ROWS - 1 || tree_depth < 1 ||
                       tree_branches < 1)) {
-        fprintf(stderr, "--speculate-tree takes 1..%d nodes (--tree-depth and --tree-branches >= 1) and does not go "
-                        "with --speculate or --speculate-sampled\n", HPA_VERIFY_MAX_ROWS - 1);
+        fprintf(stderr, "--speculate-tree and --speculate-tree-sampled take 1..%d nodes (--tree-depth and --tree-branches "
+                        ">= 1) and go with no other --speculate flag\n", HPA_VERIFY_MAX_ROWS - 1);
         return 2;
     }
     if (speculate) {
@@ -171,7 +185,8 @@ int main(int argc, char** argv) {
             return 2;
         }
         if (spec_sampled && greedy) {
-            fprintf(stderr, "--speculate-sampled samples (mode 2): not with -g (--speculate is the greedy pass)\n");
+            fprintf(stderr, "--speculate-sampled and --speculate-tree-sampled sample (mode 2): not with -g (--speculate and "
+                            "--speculate-tree are the greedy passes)\n");
             return 2;
         }
         if (!spec_sampled && (!greedy || filtered || logprobs || top_lp)) {
@@ -332,7 +347,9 @@ int main(int argc, char** argv) {
                 live++;
             }
             if (!live) break;
-            if (spec_tree      ? gpt2_decode_verify_tree(&model, drafts, parents, n_draft, n_acc, out, nodes)
+            if (spec_tree && spec_sampled
+                    ? gpt2_decode_verify_tree_sampled(&model, drafts, parents, n_draft, n_acc, out, nodes, NULL)
+                : spec_tree    ? gpt2_decode_verify_tree(&model, drafts, parents, n_draft, n_acc, out, nodes)
                 : spec_sampled ? gpt2_decode_verify_sampled(&model, drafts, n_draft, n_acc, out, NULL)
                                : gpt2_decode_verify(&model, drafts, n_draft, n_acc, out, NULL))
                 return 1;

@@ -775,6 +775,57 @@ int hpa_sample_filtered_prob(const float* logits, int R, int V, const int* seq, 
 int hpa_spec_accept(const unsigned long long* w_target, const unsigned long long* w_total, const int* drafts,
                     const int* draft0, const int* start, const int* row0, const int* len, int B,
                     unsigned long long* state, int* n_accepted, int* cont_row, int* exclude, int* pos);
+/* ---- sampled tree speculation: the list forms (HPA_VERIFY_MAX_ROWS - 1 = 7
+ * ids a row at the most) ----
+ * hpa_sample_filtered_prob with a list of ids per row: targets [R][7], of which
+ * the first n_targets[r] (clamped to [0, 7]) count.  The row is read once
+ * whatever the list's length (one tie-rank counter per id); the kept total,
+ * n_kept and cut are computed once.  Entry i's mass goes to w_target[dst[r][i]]
+ * and the row's total to w_total[dst[r][i]] (dst [R][7]: indices into arrays
+ * the caller packs as it likes, hpa_spec_tree_accept's by draft; a negative
+ * index writes nothing).  Every (mass, total) pair, n_kept[r] and cut[r]
+ * (nullable, [R]) are what hpa_sample_filtered_prob reports for that (row, id),
+ * bit for bit: an id outside [0, V) has mass 0, duplicates each get their mass,
+ * a temperature-0 row gives (1, 1) to the lowest-index argmax and (0, 1) to
+ * anything else.  One workgroup per row. */
+int hpa_sample_filtered_prob_multi(const float* logits, int R, int V, const int* seq, const float* temperature,
+                                   const int* top_k, const float* top_p, const int* targets, const int* n_targets,
+                                   const int* dst, int* n_kept, float* cut, unsigned long long* w_target,
+                                   unsigned long long* w_total);
+/* hpa_sample_filtered_ex with a list of ids per row taken out of the draw:
+ * exclude [B][7], of which the first n_exclude[b] (clamped to [0, 7]) count.
+ * Each listed id that is in the kept set loses its mass from the draw and from
+ * the total; ids outside [0, V), ids outside the kept set and repeats remove
+ * nothing.  If the removals would leave nothing, all of them are dropped (the
+ * plain draw).  Greedy rows ignore the list.  One coin; n_kept / cut report the
+ * filter, not the removal.  With n_exclude[b] <= 1 every output is
+ * hpa_sample_filtered_ex's for that id (or -1) bit for bit. */
+int hpa_sample_filtered_exn(const float* logits, int B, int V, const float* temperature, const int* top_k,
+                            const float* top_p, unsigned long long* state, int* next, int* tokens, int* pos,
+                            const int* active, int* n_kept, float* cut, const int* exclude, const int* n_exclude);
+/* The accept walk of sampled tree speculation, one thread per sequence.
+ * Sequence b's len[b] rows are the nodes of hpa_verify_tree_rows (node 0 the
+ * pending id, draft j = node j + 1 under parents[draft0[b] + j], clamped into
+ * [0, j]); w_target / w_total [draft0[b] + j]: draft j's fixed-point mass at
+ * its parent's row and that row's kept total (hpa_sample_filtered_prob_multi,
+ * the same total for all children of one node).  From cur = node 0:
+ *   rem = the total of cur's row; the children c of cur in ascending node
+ *   index, one coin j = xorshift_u32(state[b]) >> 8 each: c is accepted iff
+ *   w_c * 2^24 > rem * j (128-bit integers) -- then cur = c and the walk
+ *   starts over there; else rem -= w_c (a rejected child has w_c < rem) and
+ *   the next child is examined.  The walk ends at a leaf or when every child
+ *   of cur was rejected.
+ * Outputs: n_accepted[b] = a = depth(cur); path[b * HPA_VERIFY_MAX_ROWS + i],
+ * i < a: the accepted nodes, strictly increasing; cont_row[b] = row0[b] + cur;
+ * pos[b] = start[b] + a (as hpa_verify_tree_accept); exclude [B][7] / n_exclude
+ * [B]: the tokens of cur's rejected children in child order (-1 beyond), which
+ * hpa_sample_filtered_exn takes out of the sequence's own draw.  state[b]
+ * advances once per examined child.  len[b] == 0: n_accepted = cont_row = -1,
+ * n_exclude = 0, exclude = -1; state, pos and path untouched. */
+int hpa_spec_tree_accept(const unsigned long long* w_target, const unsigned long long* w_total, const int* drafts,
+                         const int* parents, const int* draft0, const int* start, const int* row0, const int* len, int B,
+                         unsigned long long* state, int* n_accepted, int* path, int* cont_row, int* exclude,
+                         int* n_exclude, int* pos);
 /* ---------------- logit processors (hpa_process.hip) ----------------
  * Repetition, presence and frequency penalties and a sparse logit bias, per
  * row, from the raw logits [B][V] and a dense count table counts [B][V]

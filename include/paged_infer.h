@@ -325,7 +325,8 @@ int  gpt2_ngram_draft(const int* history, int n, int max_ngram, int min_ngram, i
  * Afterwards pos[b] += a + 1 and the engine is in the state a + 1 greedy steps
  * would leave, K/V slots included.  The slots past the new position hold
  * rejected nodes' rows, which nothing reads.
- * Limits: greedy only (no sampled tree verification); fp32 KV pools (the
+ * Limits: greedy (gpt2_decode_verify_tree_sampled is the pass for sampling
+ * mode 2); fp32 KV pools (the
  * bf16 / fp8 pools' prefill kernel has no tree mask); at most
  * HPA_VERIFY_MAX_ROWS nodes; no drafted-token log-probability output (a node
  * with several children has several targets and the SCORE epilogue takes one
@@ -353,6 +354,66 @@ int  gpt2_decode_verify_tree(GPT2* model, const int* drafts, const int* parents,
  * depth <= max_nodes the tree's first-child chain is that draft. */
 int  gpt2_ngram_draft_tree(const int* history, int n, int max_ngram, int min_ngram, int max_nodes, int depth,
                            int max_branches, int* draft, int* parents);
+/* Sampled tree speculation: gpt2_decode_verify_tree under sampling mode 2.
+ * Arguments and layouts are gpt2_decode_verify_tree's.  The drafts are
+ * point-mass proposals (a deterministic drafter: gpt2_ngram_draft_tree, a
+ * greedy draft model), siblings carry distinct tokens, and multi-draft
+ * rejection sampling reduces to a rule that is exact in the sampler's
+ * fixed-point integers.  With p_i the distribution mode 2 draws from at node
+ * i's row (hpa_sample_filtered's kept set and masses under b's settings) and
+ * S_i its kept total, the walk starts at cur = node 0:
+ *   1. rem = S_cur; the children c of cur are examined in ascending node
+ *      index, w_c = the mass of c's token in p_cur (0 outside the kept set);
+ *   2. per child one coin j = xorshift_u32(state[b]) >> 8; c is accepted iff
+ *      w_c * 2^24 > rem * j (128-bit integers): then cur = c and the walk
+ *      restarts at 1; else rem -= w_c and the next child is examined;
+ *   3. the walk ends when cur is a leaf or every child of cur was rejected;
+ *   4. b's own token is one more mode-2 draw from p_cur with every rejected
+ *      child of cur removed (total rem; hpa_sample_filtered_exn), one more coin.
+ * At one node the first child c_1 is emitted with probability p(c_1); otherwise
+ * the walk goes on under p with c_1 removed and renormalised, which is where a
+ * token-by-token draw that did not give c_1 stands: by induction over the
+ * children the emitted token is distributed as p, and over the depth the
+ * emitted sequence as token-by-token mode-2 sampling.  A rejected child has
+ * w_c < rem, so rem > 0 throughout; a child that is the whole remaining kept
+ * set is always accepted; a temperature-0 sequence accepts exactly the child
+ * that carries the greedy id (its coins are still drawn).  b's sampler state
+ * advances once per examined child and once for its own token.  A chain
+ * (parents[j] = j) is exactly gpt2_decode_verify_sampled.
+ * The pass: hpa_verify_tree_rows; the layers with the tree attention kernel;
+ * the internal nodes (those with a child: gpt2_tree_dense_tables) through the
+ * dense route in chunks of gpt2_decode_set_score_chunk rows -- one LOGITS GEMM
+ * into the [chunk][V] workspace and one hpa_sample_filtered_prob_multi, each
+ * internal node once however many children it has, so that all of them are
+ * judged against one total; hpa_spec_tree_accept; hpa_pool_compact_path; then
+ * the tail from cur's row (gather, logits GEMM, hpa_sample_filtered_exn,
+ * log-probabilities / top log-probabilities as set).  As in the chain pass the
+ * accept decision reads the dense route's row and the pick recomputes its
+ * masses from the tail's row.
+ *   draft_probs (nullable, stride HPA_VERIFY_MAX_ROWS): entry j < n_draft[b] =
+ *     (float)((double)w_j / S_parent(j)): draft j's unconditional mass at its
+ *     parent's row, for every draft, examined or not.
+ * Afterwards pos[b] += a + 1 and the K/V slots are those of a + 1 mode-2 steps.
+ * Refused (message, nonzero, nothing changed -- positions, pages, pending ids,
+ * sampler states): a sampling mode other than 2, logit processors on, and
+ * everything gpt2_decode_verify_tree refuses otherwise.  Buffers are allocated
+ * on first use and freed with the engine. */
+int  gpt2_decode_verify_tree_sampled(GPT2* model, const int* drafts, const int* parents, const int* n_draft,
+                                     int* n_accepted, int* out_tokens, int* accepted_nodes, float* draft_probs);
+/* The tables of that pass's dense route, host only (no device, allocation or
+ * I/O).  drafts / parents / n_draft: gpt2_decode_verify_tree's (a parent
+ * outside [0, j] is clamped into it); row0[b]: sequence b's first packed row
+ * (node i of b is row row0[b] + i).  Per internal node -- a node with at least
+ * one child -- in (sequence, node) order: rows[k] its packed row, seq[k] its
+ * sequence, targets[k * 7 ..] its children's tokens in ascending child order,
+ * n_targets[k] their number, dst[k * 7 ..] each child's index as a packed
+ * draft (draft j of b: the drafts before b's, plus j); unused entries -1.
+ * rows, seq and n_targets need room for one entry per draft, targets and dst
+ * for 7.  Returns the number of internal nodes (at most the number of drafts).
+ * This is the one place that decides which rows reach the LOGITS GEMM: each
+ * internal node once, however many children it has. */
+int  gpt2_tree_dense_tables(const int* drafts, const int* parents, const int* n_draft, int B, const int* row0,
+                            int* rows, int* seq, int* targets, int* n_targets, int* dst);
 /* enable != 0: every pick (decode step, prefill, ragged prefill, score) is
  * followed by one hpa_logprob_rows launch: the log-probability of the chosen
  * id under the raw model distribution (temperature 1, no filter, in every

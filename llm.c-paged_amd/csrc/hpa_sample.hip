@@ -32,6 +32,13 @@
 // before the draw (hpa_sample_filtered: the instantiation without it);
 // hpa_spec_accept walks a sequence's drafted rows, one coin each, and accepts
 // while  w_target * 2^24 > w_total * j.
+//
+// Sampled tree speculation (gpt2_decode_verify_tree_sampled) adds the list
+// forms: hpa_sample_filtered_prob_multi (up to 7 ids per row in one pass over
+// the row: sf_parts keeps one tie-rank counter per id), hpa_sample_filtered_exn
+// (the sampler with a list of ids taken out, a third instantiation) and
+// hpa_spec_tree_accept (the multi-draft walk: the children of a node in turn,
+// each against what the siblings rejected before it left of the node's total).
 #include <limits.h>
 #include <math.h>
 
@@ -42,6 +49,7 @@ typedef unsigned long long u64;
 constexpr int kSfThreads = 1024;
 constexpr int kSfWaves = kSfThreads / 64;
 constexpr int kSfSegs = kSfWaves + 2;  // head scalars, one part per wave, tail scalars
+constexpr int kSfMulti = HPA_VERIFY_MAX_ROWS - 1;  // ids a row can single out in the list forms
 
 struct SfShared {
     unsigned cnt[256];
@@ -49,12 +57,17 @@ struct SfShared {
     float red_max[kSfWaves], red_min[kSfWaves];
     int red_arg[kSfWaves];
     unsigned seg_ties[kSfSegs];
-    unsigned seg_tlt[kSfSegs];  // ties below the singled-out id (sf_parts<true>)
+    unsigned seg_tlt[kSfSegs];  // ties below the singled-out id (sf_parts<1>)
     u64 seg_mass[kSfSegs];
     unsigned digit, bin_count, c_above;
     u64 m_above, target;
     int pick;
     unsigned cut_bits;
+};
+// the list forms' tie ranks: one row of parts per singled-out id
+template <int N>
+struct SfTies {
+    unsigned v[N][kSfSegs];
 };
 
 // order-preserving key: a > b  <=>  key(a) > key(b)   (no NaNs; -0 is read as +0)
@@ -370,15 +383,20 @@ __device__ __forceinline__ bool sf_filter(SfShared& sh, SfRow& r, float T, int k
 }
 
 // Ties and mass above the cut of every part of the row, in index order: part 0
-// the head scalars, part 1 + w the float4s of wave w, last the tail.  EX: also
-// the ties at an index below e (the tie rank of one singled-out id).  The
-// caller synchronises before it reads sh.seg_*.
-template <bool EX>
-__device__ __forceinline__ void sf_parts(SfShared& sh, const SfRow& r, float cutv, int e) {
+// the head scalars, part 1 + w the float4s of wave w, last the tail.  NE > 0:
+// also, per singled-out id e[i], the ties at an index below it (its tie rank),
+// into seg_tlt[i]; one pass over the row whatever NE is (e: NE ids, at least
+// one slot).  The caller synchronises before it reads sh.seg_* and seg_tlt.
+template <int NE>
+__device__ __forceinline__ void sf_parts(SfShared& sh, const SfRow& r, float cutv, const int (&e)[NE > 0 ? NE : 1],
+                                         unsigned (*seg_tlt)[kSfSegs]) {
+    constexpr int NT = NE > 0 ? NE : 1;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int Q = (r.nq + kSfWaves - 1) / kSfWaves;
     const int qlo = min(r.nq, w * Q), qhi = min(r.nq, qlo + Q);
-    unsigned ties = 0, tlt = 0;
+    unsigned ties = 0, tlt[NT];
+#pragma unroll
+    for (int i = 0; i < NT; ++i) tlt[i] = 0;
     u64 mass = 0;
     const float4* q4 = r.q4();
     for (int q0 = qlo; q0 < qhi; q0 += 64 * kSfLoads) {
@@ -393,33 +411,51 @@ __device__ __forceinline__ void sf_parts(SfShared& sh, const SfRow& r, float cut
                 for (int c = 0; c < 4; ++c) {
                     if (x[c] > cutv) mass += r.w(x[c]);
                     ties += x[c] == cutv;
-                    if (EX) tlt += x[c] == cutv && r.head + 4 * (q0 + lane + 64 * u) + c < e;
+                    if (NE == 1) tlt[0] += x[c] == cutv && r.head + 4 * (q0 + lane + 64 * u) + c < e[0];
+                    if (NE > 1 && x[c] == cutv) {  // ties are few: the NE compares stay off the common path
+#pragma unroll
+                        for (int i = 0; i < NT; ++i) tlt[i] += r.head + 4 * (q0 + lane + 64 * u) + c < e[i];
+                    }
                 }
             }
         }
     }
     ties = wave_sum_u32(ties);
     mass = wave_sum_u64(mass);
-    if (EX) tlt = wave_sum_u32(tlt);
+    if (NE > 0) {
+#pragma unroll
+        for (int i = 0; i < NT; ++i) tlt[i] = wave_sum_u32(tlt[i]);
+    }
     if (lane == 0) {
         sh.seg_ties[1 + w] = ties;
         sh.seg_mass[1 + w] = mass;
-        if (EX) sh.seg_tlt[1 + w] = tlt;
+        if (NE > 0) {
+#pragma unroll
+            for (int i = 0; i < NT; ++i) seg_tlt[i][1 + w] = tlt[i];
+        }
     }
     if (t == 0) {
         for (int s = 0; s < 2; ++s) {
             const int lo = s ? r.tail0 : 0, hi = s ? r.V : r.head;
-            unsigned tc = 0, tl = 0;
+            unsigned tc = 0, tl[NT];
+#pragma unroll
+            for (int i = 0; i < NT; ++i) tl[i] = 0;
             u64 mc = 0;
             for (int i = lo; i < hi; ++i) {
                 const float x = r.lg[i] + 0.f;
                 if (x > cutv) mc += r.w(x);
                 tc += x == cutv;
-                if (EX) tl += x == cutv && i < e;
+                if (NE > 0) {
+#pragma unroll
+                    for (int j = 0; j < NT; ++j) tl[j] += x == cutv && i < e[j];
+                }
             }
             sh.seg_ties[s ? kSfSegs - 1 : 0] = tc;
             sh.seg_mass[s ? kSfSegs - 1 : 0] = mc;
-            if (EX) sh.seg_tlt[s ? kSfSegs - 1 : 0] = tl;
+            if (NE > 0) {
+#pragma unroll
+                for (int j = 0; j < NT; ++j) seg_tlt[j][s ? kSfSegs - 1 : 0] = tl[j];
+            }
         }
     }
 }
@@ -440,11 +476,13 @@ __device__ __forceinline__ u64 sf_total(const SfShared& sh, unsigned ties_kept, 
     return S;
 }
 
-// the mass id e (in [0, V)) has in the draw, after sf_parts<true>(.., e): above
-// the cut its own, at the cut wcut if its tie rank is kept, else 0
-__device__ __forceinline__ u64 sf_id_mass(const SfShared& sh, const SfRow& r, float cutv, u64 wcut, unsigned jj, int e) {
+// the mass id e (in [0, V)) has in the draw, after sf_parts singled it out with
+// its tie ranks in seg_tlt: above the cut its own, at the cut wcut if its tie
+// rank is kept, else 0
+__device__ __forceinline__ u64 sf_id_mass(const unsigned* seg_tlt, const SfRow& r, float cutv, u64 wcut, unsigned jj,
+                                          int e) {
     unsigned tlt = 0;
-    for (int s = 0; s < kSfSegs; ++s) tlt += sh.seg_tlt[s];
+    for (int s = 0; s < kSfSegs; ++s) tlt += seg_tlt[s];
     const float xe = r.lg[e] + 0.f;
     return xe > cutv ? r.w(xe) : (xe == cutv && tlt < jj) ? wcut : 0;
 }
@@ -457,14 +495,18 @@ __device__ __forceinline__ int sf_seg_of(const SfRow& r, int e) {
     return 1 + ((e - r.head) >> 2) / Q;
 }
 
-// EX: exclude[b] (nullable, -1: none) is taken out of the kept set before the draw
-template <bool EX>
+// EX = 1: exclude[b] (-1: none) is taken out of the kept set before the draw;
+// EX = 2: the first n_exclude[b] ids of exclude[b][kSfMulti] are
+template <int EX>
 __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
     const float* __restrict__ logits, int V, const float* __restrict__ temperature, const int* __restrict__ top_k,
     const float* __restrict__ top_p, unsigned long long* __restrict__ state, int* __restrict__ next,
     int* __restrict__ tokens, int* __restrict__ pos, const int* __restrict__ active, int* __restrict__ n_kept,
-    float* __restrict__ cut_out, const int* __restrict__ exclude, int shift) {
+    float* __restrict__ cut_out, const int* __restrict__ exclude, const int* __restrict__ n_exclude, int shift) {
+    constexpr int NX = EX == 2 ? kSfMulti : 1;
     __shared__ SfShared sh;
+    __shared__ SfTies<NX> tie_sh;  // EX < 2: sh.seg_tlt serves, this one is never touched
+    unsigned (*seg_tlt)[kSfSegs] = EX == 2 ? tie_sh.v : &sh.seg_tlt;
     const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, w = t >> 6;
     if (active && active[b] <= 0) return;  // row left as it is (its RNG state too)
     SfRow r;
@@ -475,10 +517,24 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
     sf_settings(T, k, P);
     unsigned long long st = state[b];
     const u64 coin = hpa::xorshift_u32(st) >> 8;  // u = coin / 2^24
-    int ex = -1;
-    if (EX) {
-        ex = exclude[b];
-        if (ex < 0 || ex >= V) ex = -1;
+    int ex[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) ex[i] = -1;
+    if (EX == 1) {
+        ex[0] = exclude[b];
+        if (ex[0] < 0 || ex[0] >= V) ex[0] = -1;
+    }
+    if (EX == 2) {  // ids outside [0, V) and repeats remove nothing
+        const int nx = min(max(n_exclude[b], 0), NX);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            int id = i < nx ? exclude[b * NX + i] : -1;
+            if (id < 0 || id >= V) id = -1;
+#pragma unroll
+            for (int j = 0; j < i; ++j)
+                if (ex[j] == id) id = -1;
+            ex[i] = id;
+        }
     }
 
     int am;
@@ -500,22 +556,39 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
     // draw, stage 1: the parts
     const int Q = (r.nq + kSfWaves - 1) / kSfWaves;
     const int qlo = min(r.nq, w * Q), qhi = min(r.nq, qlo + Q);
-    sf_parts<EX>(sh, r, cutv, ex);
+    sf_parts<EX == 2 ? NX : EX>(sh, r, cutv, ex, seg_tlt);
     __syncthreads();
     // every thread: the kept total, the coin's threshold, and which part holds
     // the crossing and the last kept tie
     unsigned jj;
     u64 S = sf_total(sh, ties_kept, wcut, jj);
-    // the excluded id's mass leaves its part and the total; an exclusion that
-    // would leave nothing (or that removes nothing) is dropped
-    u64 wex = 0;
-    int exseg = -1;
-    if (EX && ex >= 0) {
-        wex = sf_id_mass(sh, r, cutv, wcut, jj, ex);
-        if (wex >= S) wex = 0;
-        if (wex == 0) ex = -1;
-        else exseg = sf_seg_of(r, ex);
-        S -= wex;
+    // an excluded id's mass leaves its part and the total; exclusions that
+    // would leave nothing are dropped, all of them, and one that removes nothing is
+    u64 wex[NX];
+    int exseg[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) {
+        wex[i] = 0;
+        exseg[i] = -1;
+    }
+    if (EX) {
+        u64 wsum = 0;
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            if (ex[i] >= 0) wex[i] = sf_id_mass(seg_tlt[i], r, cutv, wcut, jj, ex[i]);
+            wsum += wex[i];
+        }
+        if (wsum >= S) {
+            wsum = 0;
+#pragma unroll
+            for (int i = 0; i < NX; ++i) wex[i] = 0;
+        }
+#pragma unroll
+        for (int i = 0; i < NX; ++i) {
+            if (wex[i] == 0) ex[i] = -1;
+            else exseg[i] = sf_seg_of(r, ex[i]);
+        }
+        S -= wsum;
     }
     // running / S > u  <=>  running > floor(S * coin / 2^24)
     const u64 thr = (__umul64hi(S, coin) << 40) | ((S * coin) >> 24);
@@ -530,7 +603,11 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
             const unsigned ts = sh.seg_ties[s];
             const unsigned kt = tb >= jj ? 0u : min(ts, jj - tb);
             u64 ms = sh.seg_mass[s] + (u64)kt * wcut;
-            if (EX && s == exseg) ms -= wex;
+            if (EX) {
+#pragma unroll
+                for (int i = 0; i < NX; ++i)
+                    if (s == exseg[i]) ms -= wex[i];
+            }
             if (cross_seg < 0 && mb + ms > thr) cross_seg = s;
             if (jj > 0 && tb <= jj - 1 && jj - 1 < tb + ts) tie_seg = s;
             if (s == 1 + w) {
@@ -584,7 +661,11 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
                     if (want_bits && rank == jj - 1) sh.cut_bits = raw[c];
                     ++rank;
                 }
-                if (EX && r.head + 4 * q + c == ex) mw[c] = 0;
+                if (EX) {
+#pragma unroll
+                    for (int i = 0; i < NX; ++i)
+                        if (r.head + 4 * q + c == ex[i]) mw[c] = 0;
+                }
                 ml += mw[c];
             }
             u64 mi = ml;  // inclusive scan of the kept mass
@@ -616,7 +697,11 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
                 const unsigned ts = sh.seg_ties[q];
                 const unsigned kt = tb >= jj ? 0u : min(ts, jj - tb);
                 mb += sh.seg_mass[q] + (u64)kt * wcut;
-                if (EX && q == exseg) mb -= wex;
+                if (EX) {
+#pragma unroll
+                    for (int i = 0; i < NX; ++i)
+                        if (q == exseg[i]) mb -= wex[i];
+                }
                 tb += ts;
             }
             const int lo = s ? r.tail0 : 0, hi = s ? V : r.head;
@@ -629,7 +714,11 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_kernel(
                     if (want_bits && tb == jj - 1) sh.cut_bits = __float_as_uint(xr);
                     ++tb;
                 }
-                if (EX && i == ex) mw = 0;
+                if (EX) {
+#pragma unroll
+                    for (int j = 0; j < NX; ++j)
+                        if (i == ex[j]) mw = 0;
+                }
                 if (mb <= thr && mb + mw > thr) sh.pick = i;
                 mb += mw;
             }
@@ -746,7 +835,8 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_prob_kernel(
         return;
     }
     const u64 wcut = r.w(cutv);
-    sf_parts<true>(sh, r, cutv, d);
+    const int ds[1] = {d};
+    sf_parts<1>(sh, r, cutv, ds, &sh.seg_tlt);
     __syncthreads();
     unsigned jj;
     const u64 S = sf_total(sh, ties_kept, wcut, jj);
@@ -758,8 +848,75 @@ __global__ __launch_bounds__(kSfThreads) void sample_filtered_prob_kernel(
     if (t == 0) {
         if (n_kept) n_kept[row] = (int)n;
         if (cut_out) cut_out[row] = want_bits ? __uint_as_float(sh.cut_bits) : cutv;
-        w_target[row] = d >= 0 ? sf_id_mass(sh, r, cutv, wcut, jj, d) : 0ull;
+        w_target[row] = d >= 0 ? sf_id_mass(sh.seg_tlt, r, cutv, wcut, jj, d) : 0ull;
         w_total[row] = S;
+    }
+}
+
+// sample_filtered_prob_kernel for a list of ids per row: the row is read once
+// (one tie-rank counter per id in sf_parts); the total, n_kept and the cut are
+// computed once.  Entry i's mass and the row's total go to w_target / w_total
+// [dst[row][i]]: the caller's packing (by draft, in the tree pass).
+__global__ __launch_bounds__(kSfThreads) void sample_filtered_prob_multi_kernel(
+    const float* __restrict__ logits, int V, const int* __restrict__ seq, const float* __restrict__ temperature,
+    const int* __restrict__ top_k, const float* __restrict__ top_p, const int* __restrict__ targets,
+    const int* __restrict__ n_targets, const int* __restrict__ dst, int* __restrict__ n_kept,
+    float* __restrict__ cut_out, unsigned long long* __restrict__ w_target, unsigned long long* __restrict__ w_total,
+    int shift) {
+    __shared__ SfShared sh;
+    __shared__ SfTies<kSfMulti> tie_sh;
+    const int row = blockIdx.x, t = threadIdx.x;
+    const int b = seq ? seq[row] : row;
+    SfRow r;
+    sf_row_init(r, logits + (size_t)row * V, V, shift);
+    float T = temperature[b];
+    int k = top_k[b];
+    float P = top_p[b];
+    sf_settings(T, k, P);
+    const int m = min(max(n_targets[row], 0), kSfMulti);
+    int d[kSfMulti], o[kSfMulti];
+#pragma unroll
+    for (int i = 0; i < kSfMulti; ++i) {
+        d[i] = i < m ? targets[row * kSfMulti + i] : -1;
+        if (d[i] < 0 || d[i] >= V) d[i] = -1;
+        o[i] = i < m ? dst[row * kSfMulti + i] : -1;
+    }
+
+    int am;
+    float cutv;
+    unsigned ties_kept, n;
+    if (!sf_filter(sh, r, T, k, P, am, cutv, ties_kept, n)) {  // greedy row: a point mass at the argmax
+        if (t == 0) {
+            if (n_kept) n_kept[row] = 1;
+            if (cut_out) cut_out[row] = r.lg[am];
+#pragma unroll
+            for (int i = 0; i < kSfMulti; ++i)
+                if (o[i] >= 0) {
+                    w_target[o[i]] = d[i] == am ? 1ull : 0ull;
+                    w_total[o[i]] = 1ull;
+                }
+        }
+        return;
+    }
+    const u64 wcut = r.w(cutv);
+    sf_parts<kSfMulti>(sh, r, cutv, d, tie_sh.v);
+    __syncthreads();
+    unsigned jj;
+    const u64 S = sf_total(sh, ties_kept, wcut, jj);
+    const bool want_bits = cut_out && cutv == 0.f;  // the only value with two encodings
+    if (want_bits) {
+        sf_cut_bits(sh, r, cutv, jj);
+        __syncthreads();
+    }
+    if (t == 0) {
+        if (n_kept) n_kept[row] = (int)n;
+        if (cut_out) cut_out[row] = want_bits ? __uint_as_float(sh.cut_bits) : cutv;
+#pragma unroll
+        for (int i = 0; i < kSfMulti; ++i)
+            if (o[i] >= 0) {
+                w_target[o[i]] = d[i] >= 0 ? sf_id_mass(tie_sh.v[i], r, cutv, wcut, jj, d[i]) : 0ull;
+                w_total[o[i]] = S;
+            }
     }
 }
 
@@ -801,6 +958,65 @@ __global__ __launch_bounds__(64) void spec_accept_kernel(
     pos[b] = start[b] + a;
 }
 
+// The accept walk of sampled tree speculation, one thread per sequence: the
+// children of the current node in ascending node index, one coin each, against
+// what is left of the node's total once the children rejected before are
+// taken out.  w_target / w_total are packed by draft (draft j = node j + 1):
+// the draft's mass at its parent's row and that row's total.  A parent
+// outside [0, j] is clamped as in verify_tree_rows_kernel: an accepted child
+// has a larger index than its parent, so the walk takes at most n - 1 steps
+// whatever the table holds.
+__global__ __launch_bounds__(64) void spec_tree_accept_kernel(
+    const unsigned long long* __restrict__ w_target, const unsigned long long* __restrict__ w_total,
+    const int* __restrict__ drafts, const int* __restrict__ parents, const int* __restrict__ doffs,
+    const int* __restrict__ start, const int* __restrict__ row0, const int* __restrict__ len, int B,
+    unsigned long long* __restrict__ state, int* __restrict__ n_accepted, int* __restrict__ path,
+    int* __restrict__ cont_row, int* __restrict__ exclude, int* __restrict__ n_exclude, int* __restrict__ pos) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= B) return;
+    int* excl = exclude + (size_t)b * kSfMulti;
+    const int n = min(len[b], HPA_VERIFY_MAX_ROWS);
+    if (n <= 0) {  // untouched: state and position left as they are
+        n_accepted[b] = -1;
+        cont_row[b] = -1;
+        n_exclude[b] = 0;
+        for (int i = 0; i < kSfMulti; ++i) excl[i] = -1;
+        return;
+    }
+    const int doff = doffs[b];
+    unsigned long long st = state[b];
+    int cur = 0, a = 0, nrej = 0;
+    for (;;) {
+        nrej = 0;  // the rejected children of this node, in child order
+        u64 rem = 0;
+        int next = -1;
+        for (int c = cur + 1; c < n; ++c) {
+            if (min(max(parents[doff + c - 1], 0), c - 1) != cur) continue;
+            if (nrej == 0) rem = w_total[doff + c - 1];  // the first child: the node's kept total
+            const u64 j = hpa::xorshift_u32(st) >> 8;  // u = j / 2^24
+            const u64 wt = w_target[doff + c - 1];
+            // wt * 2^24 > rem * j
+            const u64 lhi = wt >> 40, llo = wt << 24;
+            const u64 rhi = __umul64hi(rem, j), rlo = rem * j;
+            if (lhi > rhi || (lhi == rhi && llo > rlo)) {
+                next = c;
+                break;
+            }
+            rem -= wt < rem ? wt : rem;  // a rejected child has wt < rem
+            excl[nrej++] = drafts[doff + c - 1];
+        }
+        if (next < 0) break;
+        path[b * HPA_VERIFY_MAX_ROWS + a++] = next;  // next > cur: at most n - 1 steps
+        cur = next;
+    }
+    for (int i = nrej; i < kSfMulti; ++i) excl[i] = -1;
+    state[b] = st;
+    n_accepted[b] = a;
+    cont_row[b] = row0[b] + cur;
+    n_exclude[b] = nrej;
+    pos[b] = start[b] + a;
+}
+
 // V masses of at most 2^shift sum below 2^62
 int sf_shift(int V) {
     int lg = 0;  // ceil(log2 V)
@@ -816,11 +1032,23 @@ int hpa_sample_filtered_ex(const float* logits, int B, int V, const float* tempe
                 "sample_filtered: bad arguments");
     const int shift = sf_shift(V);
     if (exclude)
-        sample_filtered_kernel<true><<<B, kSfThreads, 0, hpa_stream()>>>(
-            logits, V, temperature, top_k, top_p, state, next, tokens, pos, active, n_kept, cut, exclude, shift);
+        sample_filtered_kernel<1><<<B, kSfThreads, 0, hpa_stream()>>>(
+            logits, V, temperature, top_k, top_p, state, next, tokens, pos, active, n_kept, cut, exclude, nullptr, shift);
     else
-        sample_filtered_kernel<false><<<B, kSfThreads, 0, hpa_stream()>>>(
-            logits, V, temperature, top_k, top_p, state, next, tokens, pos, active, n_kept, cut, nullptr, shift);
+        sample_filtered_kernel<0><<<B, kSfThreads, 0, hpa_stream()>>>(
+            logits, V, temperature, top_k, top_p, state, next, tokens, pos, active, n_kept, cut, nullptr, nullptr, shift);
+    HPA_LAUNCH_CHECK();
+    return 0;
+}
+
+int hpa_sample_filtered_exn(const float* logits, int B, int V, const float* temperature, const int* top_k,
+                            const float* top_p, unsigned long long* state, int* next, int* tokens, int* pos,
+                            const int* active, int* n_kept, float* cut, const int* exclude, const int* n_exclude) {
+    HPA_REQUIRE(logits && temperature && top_k && top_p && state && next && exclude && n_exclude && B > 0 && V > 0,
+                "sample_filtered_exn: bad arguments");
+    sample_filtered_kernel<2><<<B, kSfThreads, 0, hpa_stream()>>>(logits, V, temperature, top_k, top_p, state, next,
+                                                                  tokens, pos, active, n_kept, cut, exclude, n_exclude,
+                                                                  sf_shift(V));
     HPA_LAUNCH_CHECK();
     return 0;
 }
@@ -851,6 +1079,33 @@ int hpa_spec_accept(const unsigned long long* w_target, const unsigned long long
                 "spec accept: bad arguments");
     spec_accept_kernel<<<(unsigned)((B + 63) / 64), 64, 0, hpa_stream()>>>(
         w_target, w_total, drafts, draft0, start, row0, len, B, state, n_accepted, cont_row, exclude, pos);
+    HPA_LAUNCH_CHECK();
+    return 0;
+}
+
+int hpa_sample_filtered_prob_multi(const float* logits, int R, int V, const int* seq, const float* temperature,
+                                   const int* top_k, const float* top_p, const int* targets, const int* n_targets,
+                                   const int* dst, int* n_kept, float* cut, unsigned long long* w_target,
+                                   unsigned long long* w_total) {
+    HPA_REQUIRE(logits && temperature && top_k && top_p && targets && n_targets && dst && w_target && w_total && R > 0 &&
+                    V > 0,
+                "sample_filtered_prob_multi: bad arguments");
+    sample_filtered_prob_multi_kernel<<<R, kSfThreads, 0, hpa_stream()>>>(
+        logits, V, seq, temperature, top_k, top_p, targets, n_targets, dst, n_kept, cut, w_target, w_total, sf_shift(V));
+    HPA_LAUNCH_CHECK();
+    return 0;
+}
+
+int hpa_spec_tree_accept(const unsigned long long* w_target, const unsigned long long* w_total, const int* drafts,
+                         const int* parents, const int* draft0, const int* start, const int* row0, const int* len, int B,
+                         unsigned long long* state, int* n_accepted, int* path, int* cont_row, int* exclude,
+                         int* n_exclude, int* pos) {
+    HPA_REQUIRE(w_target && w_total && drafts && parents && draft0 && start && row0 && len && state && n_accepted &&
+                    path && cont_row && exclude && n_exclude && pos && B > 0,
+                "spec tree accept: bad arguments");
+    spec_tree_accept_kernel<<<(unsigned)((B + 63) / 64), 64, 0, hpa_stream()>>>(
+        w_target, w_total, drafts, parents, draft0, start, row0, len, B, state, n_accepted, path, cont_row, exclude,
+        n_exclude, pos);
     HPA_LAUNCH_CHECK();
     return 0;
 }

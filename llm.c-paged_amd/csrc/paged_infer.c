@@ -783,6 +783,13 @@ struct GPT2Decode {
     int* vt_int;
     unsigned char* vt_anc;
     int* h_vt;
+    /* sampled tree speculation (gpt2_decode_verify_tree_sampled), allocated on
+     * first use, BD = B * (MR - 1): ts_int = the dense route's tables (seq [BD],
+     * n_targets [BD], targets [BD * 7], dst [BD * 7]: gpt2_tree_dense_tables),
+     * then exclude [B * 7] and n_exclude [B]; h_ts = the internal nodes' packed
+     * rows [BD], then the host copy of the tables */
+    int* ts_int;
+    int* h_ts;
     const int* pf_slot;
     /* logit processors (gpt2_decode_set_processors).  The settings' host
      * mirrors exist from gpt2_decode_init on (they may be set while off); the
@@ -886,6 +893,9 @@ static void dec_verify_free(GPT2Decode* d) {
     hpa_free(d->vt_int); hpa_free(d->vt_anc);
     free(d->h_vt);
     d->vt_int = NULL; d->vt_anc = NULL; d->h_vt = NULL;
+    hpa_free(d->ts_int);
+    free(d->h_ts);
+    d->ts_int = NULL; d->h_ts = NULL;
 }
 
 static void dec_shard_free(GPT2Decode* d) {
@@ -1837,8 +1847,9 @@ static int dec_gemm(GPT2* model, int l, int which) {
 }
 
 /* greedy or sampled next token; active (nullable): rows with active[b] <= 0
- * are left untouched */
-static int dec_pick_ids(GPT2* model, const int* active, const int* exclude) {
+ * are left untouched; exclude (nullable, mode 2): one id per row, or with
+ * n_exclude a list [B][HPA_VERIFY_MAX_ROWS - 1] (gpt2_decode_verify_tree_sampled) */
+static int dec_pick_ids(GPT2* model, const int* active, const int* exclude, const int* n_exclude) {
     GPT2Decode* d = model->decode;
     const int V = model->config.vocab_size;
     const float* lg = d->d_logits;
@@ -1851,6 +1862,9 @@ static int dec_pick_ids(GPT2* model, const int* active, const int* exclude) {
             return hpa_argmax_final(d->pr_part, d->pr_slices, d->Mp, B, d->d_next, d->d_tokens, d->d_pos, active);
         lg = d->pr_logits;
     }
+    if (d->sample == 2 && n_exclude)
+        return hpa_sample_filtered_exn(lg, d->B, V, d->d_samp_t, d->d_samp_k, d->d_samp_p, d->d_rng, d->d_next,
+                                       d->d_tokens, d->d_pos, active, NULL, NULL, exclude, n_exclude);
     if (d->sample == 2)
         return hpa_sample_filtered_ex(lg, d->B, V, d->d_samp_t, d->d_samp_k, d->d_samp_p, d->d_rng, d->d_next,
                                       d->d_tokens, d->d_pos, active, NULL, NULL, exclude);
@@ -1867,9 +1881,9 @@ static int dec_pick_ids(GPT2* model, const int* active, const int* exclude) {
  * log-probabilities (the pick has advanced pos and written d_next; the
  * log-probability kernel reads d_logits and d_next only); with
  * gpt2_decode_set_top_logprobs on, the raw rows' k best columns */
-static int dec_pick_ex(GPT2* model, const int* active, const int* exclude) {
+static int dec_pick_ex(GPT2* model, const int* active, const int* exclude, const int* n_exclude) {
     GPT2Decode* d = model->decode;
-    int rc = dec_pick_ids(model, active, exclude);
+    int rc = dec_pick_ids(model, active, exclude, n_exclude);
     if (d->logprobs && !rc)
         rc = hpa_logprob_rows(d->d_logits, d->B, model->config.vocab_size, d->d_next, active, d->d_lp);
     if (d->top_k && !rc)
@@ -1878,7 +1892,7 @@ static int dec_pick_ex(GPT2* model, const int* active, const int* exclude) {
     return rc;
 }
 
-static int dec_pick(GPT2* model, const int* active) { return dec_pick_ex(model, active, NULL); }
+static int dec_pick(GPT2* model, const int* active) { return dec_pick_ex(model, active, NULL, NULL); }
 
 /* ---- shared-prefix attention: the plan ----
  * Which sequences stream their leading tiles together (hip_paged_attn.h,
@@ -3180,29 +3194,23 @@ int gpt2_decode_set_verify_attention(GPT2* model, int request) {
     return 0;
 }
 
-/* the drafted rows' masses under mode 2 (gpt2_decode_verify_sampled): the dense
- * route of dec_score_top_rows over the ND drafted rows only, in chunks: gather,
- * one LOGITS GEMM into the [chunk][V] workspace, one hpa_sample_filtered_prob
- * with the drafts as targets.  Drafted row draft0[b] + i is packed row
- * row0[b] + i; hrow0 / hlen: the host row tables */
-static int dec_spec_rows(GPT2* model, int R, int ND, const int* hrow0, const int* hlen, const int* v_drafts) {
+/* The dense route of the sampled verify passes: the packed rows hrows [ND]
+ * (host) of the R-row pass through the route of dec_score_top_rows in chunks:
+ * gather, one LOGITS GEMM into the [chunk][V] workspace, then the masses.
+ * d_seq [ND] (device): the rows' sequences.  Chain (t_targets NULL): one
+ * hpa_sample_filtered_prob per chunk with v_drafts as targets, masses by row.
+ * Tree: one hpa_sample_filtered_prob_multi with the lists t_targets / t_n /
+ * t_dst (device, gpt2_tree_dense_tables), masses scattered by draft. */
+static int dec_spec_dense(GPT2* model, int R, int ND, const int* hrows, const int* d_seq, const int* v_drafts,
+                          const int* t_targets, const int* t_n, const int* t_dst) {
     GPT2Decode* d = model->decode;
     const GPT2Config c = model->config;
-    const int B = d->B, C = c.channels, V = c.vocab_size;
+    const int B = d->B, C = c.channels, V = c.vocab_size, NT = HPA_VERIFY_MAX_ROWS - 1;
     const int Rp = (R + 15) / 16 * 16, NDp = (ND + 15) / 16 * 16;
     int chunk = d->sc_chunk ? d->sc_chunk : DEC_SCORE_TOP_CHUNK;
     if (chunk > NDp) chunk = NDp;
     if (dec_score_reserve(model, chunk) || dec_score_top_reserve(model, chunk)) return 1;
-    int* hrows = (int*)malloc(2 * (size_t)ND * sizeof(int));
-    if (!hrows) return 1;
-    int* hseq = hrows + ND;
-    int nd = 0;
-    for (int b = 0; b < B; b++)
-        for (int i = 0; i + 1 < hlen[b]; i++, nd++) {
-            hrows[nd] = hrow0[b] + i;
-            hseq[nd] = b;
-        }
-    int rc = hpa_memcpy(d->sp_i, hseq, (size_t)ND * sizeof(int));
+    int rc = 0;
     unsigned long long *w_target = d->sp_w, *w_total = d->sp_w + (size_t)B * (HPA_VERIFY_MAX_ROWS - 1);
     for (int r0 = 0; r0 < ND && !rc; r0 += chunk) {
         const int n = ND - r0 < chunk ? ND - r0 : chunk, np = (n + 15) / 16 * 16;
@@ -3224,17 +3232,59 @@ static int dec_spec_rows(GPT2* model, int R, int ND, const int* hrow0, const int
         g.out = d->st_logits;
         g.part_out = d->sc_part; /* not read (dec_score_top_rows) */
         rc |= hpa_gemm_fused(&g);
-        if (!rc)
-            rc |= hpa_sample_filtered_prob(d->st_logits, n, V, d->sp_i + r0, d->d_samp_t, d->d_samp_k, d->d_samp_p,
+        if (!rc && t_targets)
+            rc |= hpa_sample_filtered_prob_multi(d->st_logits, n, V, d_seq + r0, d->d_samp_t, d->d_samp_k, d->d_samp_p,
+                                                 t_targets + (size_t)r0 * NT, t_n + r0, t_dst + (size_t)r0 * NT, NULL,
+                                                 NULL, w_target, w_total);
+        else if (!rc)
+            rc |= hpa_sample_filtered_prob(d->st_logits, n, V, d_seq + r0, d->d_samp_t, d->d_samp_k, d->d_samp_p,
                                            v_drafts + r0, NULL, NULL, w_target + r0, w_total + r0);
     }
+    return rc;
+}
+
+/* the drafted rows' masses under mode 2 (gpt2_decode_verify_sampled): the ND
+ * drafted rows through the dense route.  Drafted row draft0[b] + i is packed
+ * row row0[b] + i; hrow0 / hlen: the host row tables */
+static int dec_spec_rows(GPT2* model, int R, int ND, const int* hrow0, const int* hlen, const int* v_drafts) {
+    GPT2Decode* d = model->decode;
+    const int B = d->B;
+    int* hrows = (int*)malloc(2 * (size_t)ND * sizeof(int));
+    if (!hrows) return 1;
+    int* hseq = hrows + ND;
+    int nd = 0;
+    for (int b = 0; b < B; b++)
+        for (int i = 0; i + 1 < hlen[b]; i++, nd++) {
+            hrows[nd] = hrow0[b] + i;
+            hseq[nd] = b;
+        }
+    int rc = hpa_memcpy(d->sp_i, hseq, (size_t)ND * sizeof(int));
+    if (!rc) rc = dec_spec_dense(model, R, ND, hrows, d->sp_i, v_drafts, NULL, NULL, NULL);
     free(hrows);
     return rc;
 }
 
+/* the drafts' masses of a sampled tree pass (gpt2_decode_verify_tree_sampled):
+ * the internal nodes, once each, through the dense route; every draft's mass
+ * at its parent's row and that row's total land at the draft's packed index */
+static int dec_spec_tree_rows(GPT2* model, int R, const int* hrow0, const int* drafts, const int* parents,
+                              const int* n_draft) {
+    GPT2Decode* d = model->decode;
+    const size_t BD = (size_t)d->B * (HPA_VERIFY_MAX_ROWS - 1), NT = HPA_VERIFY_MAX_ROWS - 1;
+    int *hrows = d->h_ts, *hseq = hrows + BD, *hnt = hseq + BD, *htg = hnt + BD, *hdst = htg + NT * BD;
+    const int NI = gpt2_tree_dense_tables(drafts, parents, n_draft, d->B, hrow0, hrows, hseq, htg, hnt, hdst);
+    if (NI <= 0) return NI < 0;
+    int *t_seq = d->ts_int, *t_n = t_seq + BD, *t_tg = t_n + BD, *t_dst = t_tg + NT * BD;
+    if (hpa_memcpy(t_seq, hseq, (2 + 2 * NT) * BD * sizeof(int))) return 1;
+    return dec_spec_dense(model, R, NI, hrows, t_seq, NULL, t_tg, t_n, t_dst);
+}
+
 /* sampled: gpt2_decode_verify_sampled (draft_out: the drafts' probabilities);
  * else gpt2_decode_verify (draft_out: their raw log-probabilities).
- * parents != NULL (greedy only): gpt2_decode_verify_tree -- the rows are tree
+ * parents != NULL: gpt2_decode_verify_tree, and with sampled
+ * gpt2_decode_verify_tree_sampled (the internal nodes through the dense route,
+ * the multi-draft accept walk, the own token with the final node's rejected
+ * children taken out) -- the rows are tree
  * nodes: depth positions, slot appends and ancestor masks in the layers, no
  * SCORE targets, the accept walk, then the accepted path's K/V compacted into
  * consecutive slots ahead of the tail; accepted_nodes (nullable): the path */
@@ -3245,7 +3295,9 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
     const int tree = parents != NULL;
     if (sampled && d->sample != 2) {
         fprintf(stderr, "[paged_infer] verify_sampled: sampling mode 2 only (mode %d is on%s)\n", d->sample,
-                d->sample ? ": its float sampler has no integer masses" : ": gpt2_decode_verify is the greedy pass");
+                d->sample ? ": its float sampler has no integer masses"
+                : tree    ? ": gpt2_decode_verify_tree is the greedy pass"
+                          : ": gpt2_decode_verify is the greedy pass");
         return 1;
     }
     if (!sampled && d->sample) {
@@ -3320,6 +3372,12 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
         d->h_sp_w = (unsigned long long*)malloc(2 * (size_t)B * (MR - 1) * sizeof(unsigned long long));
         if (!d->sp_w || !d->sp_i || !d->h_sp_w) { dec_verify_free(d); return 1; }
     }
+    if (tree && sampled && !d->ts_int) {
+        const size_t BD = (size_t)B * (MR - 1);
+        d->ts_int = (int*)hpa_malloc(((2 + 2 * (MR - 1)) * BD + (size_t)B * (MR - 1) + B) * sizeof(int));
+        d->h_ts = (int*)calloc((3 + 2 * (MR - 1)) * BD, sizeof(int));
+        if (!d->ts_int || !d->h_ts) { dec_verify_free(d); return 1; }
+    }
     if (tree && !d->vt_int) {
         d->vt_int = (int*)hpa_malloc((2 * (size_t)B * (MR - 1) + B + 2 * (size_t)B * MR) * sizeof(int));
         d->vt_anc = (unsigned char*)hpa_malloc((size_t)B * MR);
@@ -3327,6 +3385,11 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
         if (!d->vt_int || !d->vt_anc || !d->h_vt) { dec_verify_free(d); return 1; }
     }
     int* sp_excl = sampled ? d->sp_i + (size_t)B * (MR - 1) : NULL;
+    int* sp_nexcl = NULL; /* a sampled tree pass: the lists of hpa_spec_tree_accept */
+    if (sampled && tree) {
+        sp_excl = d->ts_int + (2 + 2 * (size_t)(MR - 1)) * B * (MR - 1);
+        sp_nexcl = sp_excl + (size_t)B * (MR - 1);
+    }
     int *v_drafts = d->vf_int, *v_d0 = v_drafts + (size_t)B * (MR - 1), *v_acc = v_d0 + B, *v_tgt = v_acc + B,
         *v_top = v_tgt + (size_t)B * MR;
     int *hst = d->h_vf, *hr0 = hst + B, *hln = hr0 + B, *hd0 = hln + B, *hacc = hd0 + B;
@@ -3367,10 +3430,10 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
     const int* d_len = d->pf_start + 2 * B;
     const int Rp = (R + 15) / 16 * 16;
     int rc;
-    if (tree) { /* no row has a single target: the SCORE GEMM runs with -1 throughout */
+    if (tree) { /* no row has a single target: the SCORE GEMM (greedy) runs with -1 throughout */
         rc = hpa_verify_tree_rows(d->d_next, v_drafts, t_par, v_d0, d->pf_start, d_row0, d_len, B, d->pf_tok, d->pf_pos,
                                   d->pf_seq, t_slot, d->vt_anc) ||
-             hpa_memset_async(v_tgt, 0xFF, (size_t)R * sizeof(int));
+             (!sampled && hpa_memset_async(v_tgt, 0xFF, (size_t)R * sizeof(int)));
         d->pf_slot = t_slot;
         if (!rc) rc = dec_prefill_layers(model, R, T, 2);
         d->pf_slot = NULL;
@@ -3383,7 +3446,12 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
     }
     /* the accepted row of every live sequence -> the decode rows, logits, pick
      * (which advances pos by one from start + accepted) */
-    if (sampled) {
+    if (sampled && tree) {
+        if (!rc && ND) rc = dec_spec_tree_rows(model, R, hr0, drafts, parents, n_draft);
+        rc |= hpa_spec_tree_accept(d->sp_w, d->sp_w + (size_t)B * (MR - 1), v_drafts, t_par, v_d0, d->pf_start, d_row0,
+                                   d_len, B, d->d_rng, v_acc, t_path, d->pf_last, sp_excl, sp_nexcl, d->d_pos);
+        rc |= hpa_pool_compact_path(&d->pool, d->d_bt, d->bt_stride, d->pf_start, t_path, v_acc, B);
+    } else if (sampled) {
         if (!rc && ND) rc = dec_spec_rows(model, R, ND, hr0, hln, v_drafts);
         rc |= hpa_spec_accept(d->sp_w, d->sp_w + (size_t)B * (MR - 1), v_drafts, v_d0, d->pf_start, d_row0, d_len, B,
                               d->d_rng, v_acc, d->pf_last, sp_excl, d->d_pos);
@@ -3400,7 +3468,7 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
     }
     rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->pf_last, B, d->res, d->st1, d->Mp, C);
     rc |= dec_gemm(model, 0, G_LOGITS);
-    rc |= dec_pick_ex(model, d_len, sp_excl);
+    rc |= dec_pick_ex(model, d_len, sp_excl, sp_nexcl);
     if (rc) return 1;
     if (hpa_memcpy(hacc, v_acc, (tree ? B + (size_t)B * MR : (size_t)B) * sizeof(int)) ||
         hpa_memcpy(d->h_next, d->d_next, B * sizeof(int)) ||
@@ -3448,6 +3516,17 @@ int gpt2_decode_verify_tree(GPT2* model, const int* drafts, const int* parents, 
     if (any && !parents) return dec_trace_disarm(d, 1);
     return dec_trace_disarm(d, dec_verify_armed(model, drafts, parents ? parents : no_parents, n_draft, n_accepted,
                                                 out_tokens, NULL, 0, accepted_nodes));
+}
+
+int gpt2_decode_verify_tree_sampled(GPT2* model, const int* drafts, const int* parents, const int* n_draft,
+                                    int* n_accepted, int* out_tokens, int* accepted_nodes, float* draft_probs) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    int any = 0;
+    for (int b = 0; n_draft && b < d->B; b++) any |= n_draft[b] > 0;
+    if (any && !parents) return dec_trace_disarm(d, 1);
+    return dec_trace_disarm(d, dec_verify_armed(model, drafts, parents ? parents : no_parents, n_draft, n_accepted,
+                                                out_tokens, draft_probs, 1, accepted_nodes));
 }
 
 int gpt2_decode_verify_sampled(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,

@@ -342,6 +342,8 @@ def lib():
     _sig(L, "hpa_pool_compact_path", i, [P, _I, i, _I, _I, _I, i])
     _sig(L, "gpt2_decode_verify_tree", i, [v, _I, _I, _I, _I, _I, _I])
     _sig(L, "gpt2_ngram_draft_tree", i, [_I, i, i, i, i, i, i, _I, _I])
+    _sig(L, "gpt2_decode_verify_tree_sampled", i, [v, _I, _I, _I, _I, _I, _I, _F])
+    _sig(L, "gpt2_tree_dense_tables", i, [_I, _I, _I, i, _I, _I, _I, _I, _I, _I])
     _sig(L, "gpt2_decode_step", i, [v, _I, _I])
     _sig(L, "gpt2_decode_step_async", i, [v, _I])
     _sig(L, "gpt2_decode_step_traced", i, [v, _I, _I, _F])
@@ -410,6 +412,9 @@ def lib():
     _sig(L, "hpa_sample_filtered_ex", i, [v, i, i, v, v, v, v, v, v, v, v, v, v, v])
     _sig(L, "hpa_sample_filtered_prob", i, [v, i, i, v, v, v, v, v, v, v, v, v])
     _sig(L, "hpa_spec_accept", i, [v, v, v, v, v, v, v, i, v, v, v, v, v])
+    _sig(L, "hpa_sample_filtered_prob_multi", i, [v, i, i, v, v, v, v, v, v, v, v, v, v, v])
+    _sig(L, "hpa_sample_filtered_exn", i, [v, i, i, v, v, v, v, v, v, v, v, v, v, v, v])
+    _sig(L, "hpa_spec_tree_accept", i, [v, v, v, v, v, v, v, v, i, v, v, v, v, v, v, v])
     _sig(L, "hpa_paged_attention_decode_frag", i, [v, P, i, v, i, v, v, i])
     _sig(L, "gpt2_decode_set_positions", i, [v, _I])
     _sig(L, "gpt2_decode_logits", v, [v])
@@ -530,6 +535,53 @@ def ngram_draft_tree(history, max_nodes=7, depth=4, max_branches=3, max_ngram=3,
     n = lib().gpt2_ngram_draft_tree(h.ctypes.data_as(_I), int(h.size), int(max_ngram), int(min_ngram), int(max_nodes),
                                     int(depth), int(max_branches), ids.ctypes.data_as(_I), par.ctypes.data_as(_I))
     return ids[:n].tolist(), par[:n].tolist()
+
+
+def tree_dense_tables(trees, row0=None):
+    """gpt2_tree_dense_tables (host only): the dense-route tables of a sampled
+    tree pass.  trees: as Model.verify_tree_sampled; row0 [B]: every sequence's
+    first packed row (default: the rows packed in sequence order).  Returns
+    (rows, seq, targets, n_targets, dst) for the NI internal nodes: targets and
+    dst are (NI, VERIFY_MAX_ROWS - 1), unused entries -1"""
+    B, NT = len(trees), VERIFY_MAX_ROWS - 1
+    nd = np.array([-1 if t is None else len(t[0]) for t in trees], np.int32)
+    live = [t for t in trees if t is not None and len(t[0])]
+    cat = lambda k: np.ascontiguousarray(  # noqa: E731
+        np.concatenate([np.asarray(t[k], np.int32).reshape(-1) for t in live]) if live else np.zeros(1, np.int32),
+        np.int32)
+    flat, par = cat(0), cat(1)
+    if row0 is None:
+        row0 = np.cumsum(nd + 1) - (nd + 1)
+    row0 = np.ascontiguousarray(row0, np.int32)
+    ND = max(int(np.maximum(nd, 0).sum()), 1)
+    rows, seq, nt = (np.full(ND, -1, np.int32) for _ in range(3))
+    tg, dst = (np.full((ND, NT), -1, np.int32) for _ in range(2))
+    ni = lib().gpt2_tree_dense_tables(flat.ctypes.data_as(_I), par.ctypes.data_as(_I), nd.ctypes.data_as(_I), B,
+                                      row0.ctypes.data_as(_I), rows.ctypes.data_as(_I), seq.ctypes.data_as(_I),
+                                      tg.ctypes.data_as(_I), nt.ctypes.data_as(_I), dst.ctypes.data_as(_I))
+    return rows[:ni], seq[:ni], tg[:ni], nt[:ni], dst[:ni]
+
+
+def sample_filtered_prob_multi(logits, R, V, seq, temperature, top_k, top_p, targets, n_targets, dst, n_kept, cut,
+                               w_target, w_total):
+    """hpa_sample_filtered_prob_multi on device pointers (None where nullable)"""
+    check(lib().hpa_sample_filtered_prob_multi(logits, int(R), int(V), seq, temperature, top_k, top_p, targets,
+                                               n_targets, dst, n_kept, cut, w_target, w_total),
+          "hpa_sample_filtered_prob_multi")
+
+
+def sample_filtered_exn(logits, B, V, temperature, top_k, top_p, state, nxt, tokens, pos, active, n_kept, cut, exclude,
+                        n_exclude):
+    """hpa_sample_filtered_exn on device pointers (None where nullable)"""
+    check(lib().hpa_sample_filtered_exn(logits, int(B), int(V), temperature, top_k, top_p, state, nxt, tokens, pos,
+                                        active, n_kept, cut, exclude, n_exclude), "hpa_sample_filtered_exn")
+
+
+def spec_tree_accept(w_target, w_total, drafts, parents, draft0, start, row0, lens, B, state, n_accepted, path,
+                     cont_row, exclude, n_exclude, pos):
+    """hpa_spec_tree_accept on device pointers"""
+    check(lib().hpa_spec_tree_accept(w_target, w_total, drafts, parents, draft0, start, row0, lens, int(B), state,
+                                     n_accepted, path, cont_row, exclude, n_exclude, pos), "hpa_spec_tree_accept")
 
 
 class DeviceBuffer:
@@ -1174,6 +1226,37 @@ class Model:
         return ([int(acc[b]) if live[b] else None for b in range(self.B)],
                 [toks[b, :acc[b] + 1].tolist() if live[b] else None for b in range(self.B)],
                 [nodes[b, :acc[b]].tolist() if live[b] else None for b in range(self.B)])
+
+    def verify_tree_sampled(self, trees, want_probs=False):
+        """gpt2_decode_verify_tree_sampled: verify_tree under sampling mode 2
+        (multi-draft rejection sampling over point-mass siblings, exact).
+        Arguments and the first three results as verify_tree(); with
+        want_probs a fourth, probs[b] = the mass mode 2 gives every drafted id
+        at its parent's row, examined or not."""
+        assert len(trees) == self.B
+        nd = np.array([-1 if t is None else len(t[0]) for t in trees], np.int32)
+        assert all(t is None or len(t[0]) == len(t[1]) for t in trees)
+        live_parts = [t for t in trees if t is not None and len(t[0])]
+        cat = lambda k: np.ascontiguousarray(  # noqa: E731
+            np.concatenate([np.asarray(t[k], np.int32).reshape(-1) for t in live_parts]) if live_parts
+            else np.zeros(1, np.int32), np.int32)
+        flat, par = cat(0), cat(1)
+        acc = np.zeros(self.B, np.int32)
+        toks = np.zeros((self.B, VERIFY_MAX_ROWS), np.int32)
+        nodes = np.zeros((self.B, VERIFY_MAX_ROWS), np.int32)
+        pr = np.zeros((self.B, VERIFY_MAX_ROWS), np.float32)
+        check(lib().gpt2_decode_verify_tree_sampled(self.h, flat.ctypes.data_as(_I), par.ctypes.data_as(_I),
+                                                    nd.ctypes.data_as(_I), acc.ctypes.data_as(_I),
+                                                    toks.ctypes.data_as(_I), nodes.ctypes.data_as(_I),
+                                                    pr.ctypes.data_as(_F) if want_probs else None),
+              "verify_tree_sampled")
+        live = [int(n) >= 0 for n in nd]
+        out = ([int(acc[b]) if live[b] else None for b in range(self.B)],
+               [toks[b, :acc[b] + 1].tolist() if live[b] else None for b in range(self.B)],
+               [nodes[b, :acc[b]].tolist() if live[b] else None for b in range(self.B)])
+        if want_probs:
+            out += ([pr[b, :nd[b]].copy() if live[b] else None for b in range(self.B)],)
+        return out
 
     def verify_sampled(self, drafts, want_probs=False):
         """gpt2_decode_verify_sampled: one speculative pass under sampling
