@@ -21,6 +21,7 @@
  *                 [--speculate K] [--speculate-sampled K] [--repetition-penalty R] [--presence-penalty X]
  *                 [--frequency-penalty X] [--ban ID]... [--top-logprobs K]
  *                 [--speculate-tree N] [--tree-depth D] [--tree-branches W] [--speculate-tree-sampled N]
+ *                 [--park-at N]
  *     -g greedy (default: sampling as the reference), -o writes the B x
  *     (prompt + new) token ids as int32, -q prints only the summary line.
  *     --temperature / --top-k / --top-p: any of them selects filtered
@@ -74,6 +75,13 @@
  *     sampling settings and processors); with --perplexity the prompt pass is
  *     gpt2_decode_score_top and every prompt position of sequence 0 prints its
  *     K alternatives.  Not with --speculate.
+ *     --park-at N (1 <= N < new_tokens): after N generated tokens every sequence
+ *     is parked (gpt2_decode_park: its K/V pages and everything else that
+ *     belongs to it into host memory), the pool is shown empty
+ *     (gpt2_decode_free_pages), and sequence b is unparked into slot (b + 1) % B
+ *     (gpt2_decode_unpark), where it continues as if it had never left: the
+ *     text and the ids are those of the run without the flag, sampled runs
+ *     included (the sampler state travels).  Not with --speculate.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -122,7 +130,7 @@ int main(int argc, char** argv) {
     const char *ckpt = NULL, *tok_path = NULL, *tokens_path = NULL, *ids_out = NULL;
     int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
     int perplexity = 0, logprobs = 0, speculate = 0, spec_sampled = 0, top_lp = 0;
-    int spec_tree = 0, spec_chain = 0, tree_depth = 4, tree_branches = 3, tree_flags = 0;
+    int spec_tree = 0, spec_chain = 0, tree_depth = 4, tree_branches = 3, tree_flags = 0, park_on = 0, park_at = 0;
     float temperature = 1.0f, top_p = 1.0f;
     int processors = 0, n_ban = 0, ban[HPA_LOGIT_BIAS_MAX];
     float repetition = 1.0f, presence = 0.0f, frequency = 0.0f, ban_value[HPA_LOGIT_BIAS_MAX];
@@ -152,6 +160,7 @@ int main(int argc, char** argv) {
             spec_tree = spec_sampled = filtered = 1;
             tree_flags += 2;
         }
+        else if (!strcmp(a, "--park-at")) { park_at = atoi(v); park_on = 1; }
         else if (!strcmp(a, "--tree-depth")) tree_depth = atoi(v);
         else if (!strcmp(a, "--tree-branches")) tree_branches = atoi(v);
         else if (!strcmp(a, "--top-logprobs")) {
@@ -199,6 +208,10 @@ int main(int argc, char** argv) {
                             "--frequency-penalty or --ban: a verify pass has no per-row counts\n");
             return 2;
         }
+    }
+    if (park_on && (speculate || park_at < 1 || park_at >= new_tokens)) {
+        fprintf(stderr, "--park-at takes 1..new_tokens - 1 and does not go with the --speculate flags\n");
+        return 2;
     }
     GPT2 model;
     if (ckpt) {
@@ -376,19 +389,46 @@ int main(int argc, char** argv) {
         }
         free(count); free(n_draft); free(n_acc); free(drafts); free(out); free(parents); free(nodes); free(d0);
     }
+    int s0 = 0; /* the slot sequence 0 lives in; slot s holds sequence (s - s0 + B) % B */
     for (int t = 1; t < new_tokens && !speculate; t++) {
-        if (!quiet) print_token(&tk, next[0]);
-        if (!quiet && logprobs) printf("[%.4f] ", lp[0]);
-        if (!quiet && top_lp) { print_alternatives(&tk, alt_ids, alt_lps, top_lp); printf("\n"); }
+        if (!quiet) print_token(&tk, next[s0]);
+        if (!quiet && logprobs) printf("[%.4f] ", lp[s0]);
+        if (!quiet && top_lp) {
+            print_alternatives(&tk, alt_ids + (size_t)s0 * top_lp, alt_lps + (size_t)s0 * top_lp, top_lp);
+            printf("\n");
+        }
+        if (park_on && t == park_at) { /* t tokens are out: every sequence leaves the pool and comes back one slot on */
+            GPT2Parked** parked = (GPT2Parked**)malloc(B * sizeof(GPT2Parked*));
+            if (!parked) return 1;
+            size_t bytes = 0;
+            const double p0 = now_s();
+            for (int b = 0; b < B; b++) {
+                if (!(parked[b] = gpt2_decode_park(&model, b, 0))) return 1;
+                bytes += gpt2_parked_bytes(parked[b]);
+            }
+            const double p1 = now_s();
+            const int free_pages = gpt2_decode_free_pages(&model);
+            for (int b = 0; b < B; b++)
+                if (gpt2_decode_unpark(&model, parked[b], (b + 1) % B)) return 1;
+            const double p2 = now_s();
+            fprintf(stderr, "parked %d sequences of %d tokens (%.1f MB of K/V) in %.3f ms: %d of %d pages free; "
+                            "unparked into slots (b + 1) %% %d in %.3f ms\n", B, gpt2_parked_tokens(parked[0]),
+                    1e-6 * (double)bytes, 1e3 * (p1 - p0), free_pages, B * max_pages, B, 1e3 * (p2 - p1));
+            if (free_pages != B * max_pages) { fprintf(stderr, "the pool is not empty after parking\n"); return 1; }
+            for (int b = 0; b < B; b++) gpt2_parked_free(parked[b]);
+            free(parked);
+            s0 = 1 % B;
+        }
         /* the previous ids stay on the device and feed this step */
         if (gpt2_decode_step(&model, NULL, next)) return 1;
         if (logprobs && gpt2_decode_logprobs(&model, lp)) return 1;
         if (top_lp && gpt2_decode_top_logprobs(&model, alt_ids, alt_lps)) return 1;
-        for (int b = 0; b < B; b++) gen[(size_t)b * total + prompt_len + t] = next[b];
+        for (int b = 0; b < B; b++) gen[(size_t)b * total + prompt_len + t] = next[(b + s0) % B];
     }
-    if (!quiet && new_tokens > 0 && !speculate) print_token(&tk, next[0]);
-    if (!quiet && logprobs && new_tokens > 0) printf("[%.4f] ", lp[0]);
-    if (!quiet && top_lp && new_tokens > 0) print_alternatives(&tk, alt_ids, alt_lps, top_lp);
+    if (!quiet && new_tokens > 0 && !speculate) print_token(&tk, next[s0]);
+    if (!quiet && logprobs && new_tokens > 0) printf("[%.4f] ", lp[s0]);
+    if (!quiet && top_lp && new_tokens > 0)
+        print_alternatives(&tk, alt_ids + (size_t)s0 * top_lp, alt_lps + (size_t)s0 * top_lp, top_lp);
     double t2 = now_s();
     if (!quiet) printf("\n---\nFinished!\n");
     printf("prefill %d x %d tokens in %.3f ms; generated %d tokens x %d sequences (%s) in %.3f ms: "

@@ -161,6 +161,33 @@ size_t hpa_pool_v_index(const HpaKVPool* pool, int layer, int page, int head, in
  * otherwise nonzero and nothing is launched. */
 #define HPA_COPY_MAX_PAGES 64
 int  hpa_pool_copy_pages(const HpaKVPool* pool, const int* src_pages, const int* dst_pages, int n);
+/* whole pages between the pool and ONE contiguous buffer, every layer (the data
+ * path of gpt2_decode_park / gpt2_decode_unpark).  The buffer holds page i of
+ * layer l at byte hpa_park_offset(pool, n_pages, l, i) = (l * n_pages + i) *
+ * page_bytes, page_bytes = page_elems * elem_bytes, hpa_park_bytes(pool,
+ * n_pages) = num_layers * n_pages * page_bytes in all (both pure host
+ * arithmetic: they read the pool's shape only): the layout does not depend on
+ * where the pages sat in the pool.  Bytes only, whatever the dtype.
+ * gather: page pages[i] of every layer -> the buffer; scatter: the buffer ->
+ * page pages[i] of every layer.  pages is a HOST array of pool slots, n_pages
+ * >= 1 without an upper bound; dst / src is 16-byte aligned memory a kernel may
+ * dereference over all hpa_park_bytes (device memory, or pinned host memory:
+ * hpa_is_device_accessible).  ceil(n_pages / HPA_PARK_MAX_PAGES) asynchronous
+ * launches on the current stream, each over every layer with its page ids by
+ * value in the kernel arguments: no staging table, no sync, no allocation.  A
+ * slot out of range, a slot listed twice in a scatter, or an inaccessible
+ * buffer: nonzero and nothing is launched. */
+#define HPA_PARK_MAX_PAGES 64   /* page ids per launch, by value in the kernel arguments */
+size_t hpa_park_bytes(const HpaKVPool* pool, int n_pages);
+size_t hpa_park_offset(const HpaKVPool* pool, int n_pages, int layer, int i);
+int  hpa_pool_gather_pages(const HpaKVPool* pool, const int* pages, int n_pages, void* dst);
+int  hpa_pool_scatter_pages(const HpaKVPool* pool, const int* pages, int n_pages, const void* src);
+/* the pool side of the two kernels as non-temporal accesses (a measurement
+ * knob of tools/park_scan.py): bit 0 the gather's loads, bit 1 the scatter's
+ * stores.  3 (default): both (profiles/r18/park.txt: the loads a measured gain, the
+ * stores a wash) */
+int  hpa_park_set_nontemporal(int mask);
+int  hpa_park_nontemporal(void);
 
 /* ---------------- decode-step kernels (fp32) ----------------
  * B = sequences in the batch, C = channels, NH heads of head_size 64.

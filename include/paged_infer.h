@@ -479,6 +479,59 @@ int  gpt2_decode_release(GPT2* model, int seq);
  * leaves the pages to the others.  gpt2_decode_fill_random* refuses while
  * pages are shared.  Waits for queued work like gpt2_decode_release. */
 int  gpt2_decode_fork(GPT2* model, int src, int dst, int n_tokens);
+/* ---------------- parking: preemption by swap ----------------
+ * gpt2_decode_park copies everything that belongs to sequence seq at position
+ * n = pos[seq] >= 1 into host memory and returns a handle; gpt2_decode_unpark
+ * puts a handle into a fresh or released slot, which then is in the state the
+ * parked sequence was in: gpt2_decode_step(model, NULL, ..) continues it bit
+ * for bit and every per-sequence readback returns what it returned before the
+ * park.  The other answer to a full pool besides the LRU eviction (a sequence
+ * thrown away and prefilled again), and a way to set an idle conversation aside.
+ *
+ * park waits for queued work like gpt2_decode_release, then copies:
+ *   - the K/V: the ceil(n / P) pages of every layer into ONE pinned host
+ *     allocation, by hpa_pool_gather_pages writing straight into it (layout:
+ *     hpa_park_offset).  The partly filled last page travels whole (its slots
+ *     past n hold bytes no kernel reads, as in any reused page); shared pages
+ *     are read like any others;
+ *   - the device words d_next[seq], d_tokens[seq] and, once
+ *     gpt2_decode_set_sampling was called, the sampler state;
+ *   - the readback rows: the logits row [V] and, where the feature is on, the
+ *     processed-logits row, the pending id's log-probability, the top
+ *     log-probability row (ids and values, k of them);
+ *   - the settings: temperature / top-k / top-p, the penalties, from_pos, the
+ *     bias list;
+ *   - with processors on the recorded history [0, n);
+ *   - the geometry: kv dtype, P, num_layers, num_heads, head_size, vocab_size,
+ *     and of an fp8 pool the 2 * L * NH K/V scales.
+ * keep == 0: the slot is then released exactly as gpt2_decode_release does it
+ * (only after the copy has completed).  keep != 0: the sequence stays live and
+ * untouched -- a checkpoint.  No engine, seq out of range, pos[seq] == 0 or a
+ * failed allocation: NULL with a message, nothing changed.
+ *
+ * unpark: the target must be fresh or released (position 0, no pages), as for
+ * gpt2_decode_fork.  Refused -- message, nonzero, no page, position, setting or
+ * device word changed -- when the target is live or out of range; when a
+ * geometry field differs (on fp8: a scale, bit for bit); when n > max_ctx; when
+ * processors are on in the engine and the handle carries no history; when
+ * gpt2_decode_free_pages() < ceil(n / P).  An unpark never evicts anyone: the
+ * caller parks someone else first.  On success the slot takes ceil(n / P)
+ * private pages, the payload is scattered into them (hpa_pool_scatter_pages),
+ * every word, row and setting above is restored (with processors on: the
+ * history uploaded and the counts recounted over the slot's window), pos[seq]
+ * = n.  A row of a feature that was off at the park and is on now is left as
+ * it is until the next pick rewrites it.  A captured decode graph stays valid:
+ * everything it reads is a device array.  Waits for its copies.
+ * The handle is host memory only and is not consumed: unparking it into two
+ * slots is a host-level fork, and it may go into another engine of the same
+ * geometry.  gpt2_parked_tokens: n; gpt2_parked_bytes: the K/V payload
+ * (hpa_park_bytes); gpt2_parked_free(NULL) is fine. */
+typedef struct GPT2Parked GPT2Parked;
+GPT2Parked* gpt2_decode_park(GPT2* model, int seq, int keep);
+int    gpt2_decode_unpark(GPT2* model, const GPT2Parked* parked, int seq);
+int    gpt2_parked_tokens(const GPT2Parked* parked);
+size_t gpt2_parked_bytes(const GPT2Parked* parked);
+void   gpt2_parked_free(GPT2Parked* parked);
 /* ---------------- shared-prefix attention ----------------
  * Forks of one prefix hold the same pages for it, and the decode attention
  * still streams them once per sequence.  With this on (default off) the decode
@@ -710,6 +763,10 @@ int    gpt2_decode_sampling_params(GPT2* model, int seq, float* temperature, int
  * gpt2_decode_set_sampling call (no states yet) and for seq out of range.
  * Waits for queued work. */
 int    gpt2_decode_seed_sequence(GPT2* model, int seq, unsigned long long seed);
+/* sequence seq's sampler state as it stands (what gpt2_decode_park carries
+ * along); nonzero before any gpt2_decode_set_sampling call and for seq out of
+ * range.  Waits for queued work. */
+int    gpt2_decode_sampler_state(GPT2* model, int seq, unsigned long long* state);
 /* ---------------- logit processors ----------------
  * Repetition (CTRL / HF rule), presence and frequency (OpenAI rule) penalties
  * and a logit bias, per sequence, applied on the device before every pick.

@@ -2529,6 +2529,12 @@ int gpt2_decode_seed_sequence(GPT2* model, int seq, unsigned long long seed) {
     return hpa_memcpy(d->d_rng + seq, &seed, sizeof(seed));
 }
 
+int gpt2_decode_sampler_state(GPT2* model, int seq, unsigned long long* state) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d || !d->d_rng || seq < 0 || seq >= d->B || !state) return 1;
+    return hpa_synchronize() || hpa_memcpy(state, d->d_rng + seq, sizeof(*state));
+}
+
 int gpt2_decode_set_graph(GPT2* model, int enable) {
     GPT2Decode* d = model->decode;
     if (!d) return 1;
@@ -3613,6 +3619,191 @@ int gpt2_decode_fork(GPT2* model, int src, int dst, int n_tokens) {
         if (hpa_memcpy_async(d->d_next + dst, d->d_next + src, sizeof(int)) ||
             hpa_memcpy_async(d->d_tokens + dst, d->d_tokens + src, sizeof(int)))
             return 1;
+    }
+    return dec_sync_block_table(d) || hpa_synchronize();
+}
+
+/* ---- parking: a sequence's state in host memory (contract: paged_infer.h) ----
+ * The K/V payload is one pinned allocation the gather kernel writes straight
+ * into (profiles/r18/park.txt: the route through a device buffer and one copy
+ * is no faster); everything else is a few words and rows in pageable memory. */
+struct GPT2Parked {
+    int n, n_pages;                                      /* tokens, ceil(n / P) */
+    int kv_dtype, P, L, NH, HS, V;                       /* geometry */
+    float* kv_scale;                                     /* fp8: K [L][NH] then V [L][NH]; else NULL */
+    void* kv;                                            /* pinned: hpa_park_offset layout */
+    size_t kv_bytes;
+    int next, token;                                     /* d_next[seq], d_tokens[seq] */
+    int has_rng, has_proc, has_lp, top_k;                /* which of the rows below are valid */
+    unsigned long long rng;
+    float* logits;                                       /* [V] */
+    float* pr_logits;                                    /* [V], has_proc */
+    float lp;                                            /* has_lp */
+    int top_ids[HPA_TOP_LOGPROBS_MAX];                   /* top_k entries */
+    float top_lps[HPA_TOP_LOGPROBS_MAX];
+    float temperature, top_p, repetition, presence, frequency;
+    int samp_k, from_pos, n_bias;
+    int bias_ids[HPA_LOGIT_BIAS_MAX];
+    float bias_values[HPA_LOGIT_BIAS_MAX];
+    int* history;                                        /* [n], has_proc */
+};
+
+void gpt2_parked_free(GPT2Parked* p) {
+    if (!p) return;
+    if (p->kv) hpa_host_free(p->kv);
+    free(p->kv_scale); free(p->logits); free(p->pr_logits); free(p->history);
+    free(p);
+}
+
+int gpt2_parked_tokens(const GPT2Parked* p) { return p ? p->n : 0; }
+size_t gpt2_parked_bytes(const GPT2Parked* p) { return p ? p->kv_bytes : 0; }
+
+GPT2Parked* gpt2_decode_park(GPT2* model, int seq, int keep) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] park: gpt2_decode_init first\n"); return NULL; }
+    if (seq < 0 || seq >= d->B) { fprintf(stderr, "[paged_infer] park: no sequence %d\n", seq); return NULL; }
+    const int n = d->h_pos[seq], P = d->P, np = (n + P - 1) / P;
+    if (n < 1) { fprintf(stderr, "[paged_infer] park: sequence %d holds no tokens\n", seq); return NULL; }
+    if (d->bm->prompt_block_count[seq] < np) {
+        fprintf(stderr, "[paged_infer] park: sequence %d has no pages for %d tokens\n", seq, n);
+        return NULL;
+    }
+    if (hpa_synchronize()) return NULL; /* queued work still writes the pages and the rows */
+    const int L = model->config.num_layers, NH = model->config.num_heads, V = model->config.vocab_size;
+    const int B = d->B;
+    GPT2Parked* p = (GPT2Parked*)calloc(1, sizeof(GPT2Parked));
+    int* slots = (int*)malloc(np * sizeof(int));
+    if (!p || !slots) goto fail;
+    p->n = n; p->n_pages = np;
+    p->kv_dtype = d->pool.dtype; p->P = P; p->L = L; p->NH = NH; p->HS = d->pool.head_size; p->V = V;
+    p->kv_bytes = hpa_park_bytes(&d->pool, np);
+    p->has_rng = d->d_rng != NULL;
+    p->has_proc = d->proc != 0;
+    p->has_lp = d->logprobs && d->d_lp;
+    p->top_k = d->top_k && d->d_top_ids ? d->top_k : 0;
+    p->kv = hpa_host_alloc(p->kv_bytes);
+    p->logits = (float*)malloc((size_t)V * sizeof(float));
+    if (!p->kv || !p->logits) goto fail;
+    if (d->pool.dtype == HPA_FP8) {
+        const size_t ns = 2 * (size_t)L * NH;
+        p->kv_scale = (float*)malloc(ns * sizeof(float));
+        if (!p->kv_scale) goto fail;
+        memcpy(p->kv_scale, d->h_kv_scale, ns * sizeof(float));
+    }
+    if (p->has_proc) {
+        p->pr_logits = (float*)malloc((size_t)V * sizeof(float));
+        p->history = (int*)malloc((size_t)n * sizeof(int));
+        if (!p->pr_logits || !p->history) goto fail;
+    }
+    for (int i = 0; i < np; i++) slots[i] = d->pv.map[d->bm->prompt_block_list[seq][i]];
+    if (hpa_pool_gather_pages(&d->pool, slots, np, p->kv)) goto fail;
+    if (hpa_memcpy_async(&p->next, d->d_next + seq, sizeof(int)) ||
+        hpa_memcpy_async(&p->token, d->d_tokens + seq, sizeof(int)) ||
+        hpa_memcpy_async(p->logits, d->d_logits + (size_t)seq * V, (size_t)V * sizeof(float)))
+        goto fail;
+    if (p->has_rng && hpa_memcpy_async(&p->rng, d->d_rng + seq, sizeof(p->rng))) goto fail;
+    if (p->has_proc && (hpa_memcpy_async(p->pr_logits, d->pr_logits + (size_t)seq * V, (size_t)V * sizeof(float)) ||
+                        hpa_memcpy_async(p->history, d->pr_hist + (size_t)seq * d->max_ctx, (size_t)n * sizeof(int))))
+        goto fail;
+    if (p->has_lp && hpa_memcpy_async(&p->lp, d->d_lp + seq, sizeof(float))) goto fail;
+    if (p->top_k && (hpa_memcpy_async(p->top_ids, d->d_top_ids + (size_t)seq * p->top_k, p->top_k * sizeof(int)) ||
+                     hpa_memcpy_async(p->top_lps, d->d_top_lps + (size_t)seq * p->top_k, p->top_k * sizeof(float))))
+        goto fail;
+    if (hpa_synchronize()) goto fail;
+    p->temperature = d->h_samp_t[seq]; p->samp_k = d->h_samp_k[seq]; p->top_p = d->h_samp_p[seq];
+    p->repetition = d->h_pr_f[seq]; p->presence = d->h_pr_f[B + seq]; p->frequency = d->h_pr_f[2 * B + seq];
+    p->from_pos = d->h_pr_i[seq];
+    p->n_bias = d->h_pr_i[B + seq];
+    memcpy(p->bias_ids, d->h_pr_i + 2 * B + (size_t)seq * HPA_LOGIT_BIAS_MAX, p->n_bias * sizeof(int));
+    memcpy(p->bias_values, d->h_pr_bias + (size_t)seq * HPA_LOGIT_BIAS_MAX, p->n_bias * sizeof(float));
+    free(slots);
+    slots = NULL;
+    if (!keep && gpt2_decode_release(model, seq)) goto fail; /* only now: the copy has completed */
+    return p;
+fail:
+    fprintf(stderr, "[paged_infer] park: sequence %d not parked (allocation or copy failed)\n", seq);
+    free(slots);
+    gpt2_parked_free(p);
+    return NULL;
+}
+
+int gpt2_decode_unpark(GPT2* model, const GPT2Parked* p, int seq) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] unpark: gpt2_decode_init first\n"); return 1; }
+    if (!p) { fprintf(stderr, "[paged_infer] unpark: no handle\n"); return 1; }
+    if (seq < 0 || seq >= d->B) { fprintf(stderr, "[paged_infer] unpark: no sequence %d\n", seq); return 1; }
+    if (d->h_pos[seq] != 0 || d->bm->prompt_block_count[seq] != 0) {
+        fprintf(stderr, "[paged_infer] unpark: sequence %d is live (gpt2_decode_release it first)\n", seq);
+        return 1;
+    }
+    const int L = model->config.num_layers, NH = model->config.num_heads, V = model->config.vocab_size;
+    const int B = d->B, n = p->n, np = p->n_pages;
+    if (p->kv_dtype != d->pool.dtype || p->P != d->P || p->L != L || p->NH != NH || p->HS != d->pool.head_size ||
+        p->V != V) {
+        fprintf(stderr, "[paged_infer] unpark: the handle's geometry (kv dtype %d, page %d, %d layers, %d heads of %d, "
+                        "vocabulary %d) is not this engine's (%d, %d, %d, %d of %d, %d)\n", p->kv_dtype, p->P, p->L,
+                p->NH, p->HS, p->V, d->pool.dtype, d->P, L, NH, d->pool.head_size, V);
+        return 1;
+    }
+    if (d->pool.dtype == HPA_FP8 && memcmp(p->kv_scale, d->h_kv_scale, 2 * (size_t)L * NH * sizeof(float))) {
+        fprintf(stderr, "[paged_infer] unpark: the handle's fp8 K/V scales are not this engine's\n");
+        return 1;
+    }
+    if (n > d->max_ctx || p->from_pos > d->max_ctx) {
+        fprintf(stderr, "[paged_infer] unpark: %d tokens (penalty window from %d) do not fit max_ctx %d\n", n,
+                p->from_pos, d->max_ctx);
+        return 1;
+    }
+    if (d->proc && !p->has_proc) {
+        fprintf(stderr, "[paged_infer] unpark: logit processors are on and the handle carries no token history\n");
+        return 1;
+    }
+    if (bm_free_pages(d->bm) < np) {
+        fprintf(stderr, "[paged_infer] unpark: %d pages needed, %d free (park or release a sequence first)\n", np,
+                bm_free_pages(d->bm));
+        return 1;
+    }
+    if (hpa_synchronize()) return 1; /* queued steps still read the settings and rows of slot seq */
+    int* slots = (int*)malloc(np * sizeof(int));
+    if (!slots) return 1;
+    int rc = 0;
+    for (int i = 0; i < np && !rc; i++) { /* np pages are free: nobody is evicted */
+        KVBlock* blk = request_block(d->bm, seq);
+        if (!blk) rc = 1;
+        else slots[i] = d->pv.map[bm_block_index(d->bm, blk)];
+    }
+    if (!rc) rc = hpa_pool_scatter_pages(&d->pool, slots, np, p->kv);
+    free(slots);
+    if (rc) {
+        free_blocks_for_prompt(d->bm, seq);
+        dec_sync_block_table(d);
+        return 1;
+    }
+    d->sh_dirty = 1;
+    rc = hpa_memcpy_async(d->d_next + seq, &p->next, sizeof(int)) ||
+         hpa_memcpy_async(d->d_tokens + seq, &p->token, sizeof(int)) ||
+         hpa_memcpy_async(d->d_logits + (size_t)seq * V, p->logits, (size_t)V * sizeof(float));
+    if (!rc && p->has_rng && d->d_rng) rc = hpa_memcpy_async(d->d_rng + seq, &p->rng, sizeof(p->rng));
+    if (!rc && p->has_proc && d->proc)
+        rc = hpa_memcpy_async(d->pr_logits + (size_t)seq * V, p->pr_logits, (size_t)V * sizeof(float));
+    if (!rc && p->has_lp && d->d_lp) rc = hpa_memcpy_async(d->d_lp + seq, &p->lp, sizeof(float));
+    if (!rc && p->top_k && p->top_k == d->top_k && d->d_top_ids)
+        rc = hpa_memcpy_async(d->d_top_ids + (size_t)seq * p->top_k, p->top_ids, p->top_k * sizeof(int)) ||
+             hpa_memcpy_async(d->d_top_lps + (size_t)seq * p->top_k, p->top_lps, p->top_k * sizeof(float));
+    if (rc) return 1;
+    d->h_samp_t[seq] = p->temperature; d->h_samp_k[seq] = p->samp_k; d->h_samp_p[seq] = p->top_p;
+    d->h_pr_f[seq] = p->repetition; d->h_pr_f[B + seq] = p->presence; d->h_pr_f[2 * B + seq] = p->frequency;
+    d->h_pr_i[seq] = p->from_pos;
+    d->h_pr_i[B + seq] = p->n_bias;
+    memcpy(d->h_pr_i + 2 * B + (size_t)seq * HPA_LOGIT_BIAS_MAX, p->bias_ids, p->n_bias * sizeof(int));
+    memcpy(d->h_pr_bias + (size_t)seq * HPA_LOGIT_BIAS_MAX, p->bias_values, p->n_bias * sizeof(float));
+    if (dec_upload_sampling_params(d) || dec_pr_upload(d)) return 1;
+    d->h_pos[seq] = n;
+    if (hpa_memcpy_async(d->d_pos + seq, &d->h_pos[seq], sizeof(int))) return 1;
+    if (d->proc) { /* the history, counted over the slot's own window */
+        if (hpa_memcpy_async(d->pr_hist + (size_t)seq * d->max_ctx, p->history, (size_t)n * sizeof(int))) return 1;
+        d->h_pr_rec[seq] = n;
+        if (dec_pr_recount(d, seq)) return 1;
     }
     return dec_sync_block_table(d) || hpa_synchronize();
 }

@@ -184,6 +184,7 @@ def lib():
     _sig(L, "hpa_malloc_managed", v, [sz])
     _sig(L, "hpa_host_alloc", v, [sz])
     _sig(L, "hpa_free", i, [v])
+    _sig(L, "hpa_host_free", i, [v])
     _sig(L, "hpa_memcpy", i, [v, v, sz])
     _sig(L, "hpa_memcpy_async", i, [v, v, sz])
     _sig(L, "hpa_memset_async", i, [v, i, sz])
@@ -253,6 +254,17 @@ def lib():
     _sig(L, "bm_page_refs", i, [v, i])
     _sig(L, "bm_shared_pages", i, [v])
     _sig(L, "hpa_pool_copy_pages", i, [P, _I, _I, i])
+    _sig(L, "hpa_park_bytes", sz, [P, i])
+    _sig(L, "hpa_park_offset", sz, [P, i, i, i])
+    _sig(L, "hpa_pool_gather_pages", i, [P, _I, i, v])
+    _sig(L, "hpa_pool_scatter_pages", i, [P, _I, i, v])
+    _sig(L, "hpa_park_set_nontemporal", i, [i])
+    _sig(L, "hpa_park_nontemporal", i, [])
+    _sig(L, "gpt2_decode_park", v, [v, i, i])
+    _sig(L, "gpt2_decode_unpark", i, [v, v, i])
+    _sig(L, "gpt2_parked_tokens", i, [v])
+    _sig(L, "gpt2_parked_bytes", sz, [v])
+    _sig(L, "gpt2_parked_free", None, [v])
     _sig(L, "gpt2_decode_fork", i, [v, i, i, i])
     _sig(L, "gpt2_decode_free_pages", i, [v])
     _sig(L, "gpt2_decode_page_slots", i, [v, _I, i])
@@ -302,6 +314,7 @@ def lib():
     _sig(L, "gpt2_decode_set_sampling_params", i, [v, i, ctypes.c_float, i, ctypes.c_float])
     _sig(L, "gpt2_decode_sampling_params", i, [v, i, _F, _I, _F])
     _sig(L, "gpt2_decode_seed_sequence", i, [v, i, ctypes.c_ulonglong])
+    _sig(L, "gpt2_decode_sampler_state", i, [v, i, ctypes.POINTER(ctypes.c_ulonglong)])
     _sig(L, "gpt2_decode_set_processors", i, [v, i])
     _sig(L, "gpt2_decode_processors", i, [v])
     _sig(L, "gpt2_decode_set_penalties", i, [v, i, ctypes.c_float, ctypes.c_float, ctypes.c_float, i])
@@ -779,6 +792,29 @@ class Pool:
         check(lib().hpa_pool_copy_pages(self.ref, s.ctypes.data_as(_I), d.ctypes.data_as(_I), int(s.size)),
               "pool_copy_pages")
 
+    def park_bytes(self, n_pages):
+        """hpa_park_bytes: bytes of a parked buffer of n_pages pages (every layer)"""
+        return park_bytes(self.s, n_pages)
+
+    def park_offset(self, n_pages, layer, i):
+        """hpa_park_offset: where page i of `layer` sits in a parked buffer of n_pages pages"""
+        return park_offset(self.s, n_pages, layer, i)
+
+    def gather_pages(self, pages, dst):
+        """hpa_pool_gather_pages: the pages (pool slots) of every layer -> the
+        contiguous buffer at `dst` (a device or pinned-host address, or an
+        object with .ptr), park_bytes(len(pages)) bytes; asynchronous"""
+        s = np.ascontiguousarray(pages, np.int32).reshape(-1)
+        check(lib().hpa_pool_gather_pages(self.ref, s.ctypes.data_as(_I), int(s.size), getattr(dst, "ptr", dst)),
+              "pool_gather_pages")
+
+    def scatter_pages(self, pages, src):
+        """hpa_pool_scatter_pages: the buffer at `src` -> the pages (distinct
+        pool slots) of every layer; asynchronous"""
+        s = np.ascontiguousarray(pages, np.int32).reshape(-1)
+        check(lib().hpa_pool_scatter_pages(self.ref, s.ctypes.data_as(_I), int(s.size), getattr(src, "ptr", src)),
+              "pool_scatter_pages")
+
     def destroy(self):
         if self.s.base:
             lib().hpa_pool_destroy(self.ref)
@@ -786,6 +822,67 @@ class Pool:
     def __del__(self):
         try:
             self.destroy()
+        except Exception:
+            pass
+
+
+def park_bytes(pool, n_pages):
+    """hpa_park_bytes (pure: the pool's shape only; `pool` an HpaKVPool or a Pool)"""
+    return int(lib().hpa_park_bytes(ctypes.byref(getattr(pool, "s", pool)), int(n_pages)))
+
+
+def park_offset(pool, n_pages, layer, i):
+    """hpa_park_offset (pure): byte offset of page i of `layer` in a parked buffer"""
+    return int(lib().hpa_park_offset(ctypes.byref(getattr(pool, "s", pool)), int(n_pages), int(layer), int(i)))
+
+
+class PinnedBuffer:
+    """hpa_host_alloc'd (pinned, device-accessible) host memory; .array is a
+    uint8 numpy view of it"""
+
+    def __init__(self, nbytes):
+        self.nbytes = int(nbytes)
+        self.ptr = lib().hpa_host_alloc(self.nbytes)
+        if not self.ptr:
+            raise MemoryError(f"pinned allocation of {nbytes} bytes failed")
+        self.array = np.ctypeslib.as_array((ctypes.c_ubyte * max(self.nbytes, 1)).from_address(self.ptr))[:self.nbytes]
+
+    def free(self):
+        if self.ptr:
+            self.array = None
+            lib().hpa_host_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class Parked:
+    """a parked sequence (GPT2Parked): host memory only; Model.unpark does not
+    consume it"""
+
+    def __init__(self, h):
+        self.h = h
+
+    @property
+    def tokens(self):
+        return int(lib().gpt2_parked_tokens(self.h))
+
+    @property
+    def bytes(self):
+        return int(lib().gpt2_parked_bytes(self.h))
+
+    def free(self):
+        if self.h:
+            lib().gpt2_parked_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
         except Exception:
             pass
 
@@ -1359,6 +1456,25 @@ class Model:
         both); its sampler state stays its own."""
         check(lib().gpt2_decode_fork(self.h, int(src), int(dst), int(n_tokens)), "fork")
 
+    def park(self, seq, keep=False):
+        """gpt2_decode_park: everything that belongs to sequence seq (K/V pages,
+        pending id, sampler state, readback rows, settings, history) into host
+        memory; the slot is released unless keep (a checkpoint).  Returns a
+        Parked"""
+        h = lib().gpt2_decode_park(self.h, int(seq), int(bool(keep)))
+        if not h:
+            raise RuntimeError(f"park({seq}) refused")
+        return Parked(h)
+
+    def unpark(self, parked, seq):
+        """gpt2_decode_unpark: the parked sequence into slot seq (fresh or
+        released), in private pages; step(None) continues it bit for bit.
+        Raises, nothing changed, when refused (paged_infer.h)"""
+        if not isinstance(parked, Parked) or not parked.h:
+            raise ValueError("unpark: a live Parked handle expected")
+        if lib().gpt2_decode_unpark(self.h, parked.h, int(seq)) != 0:
+            raise RuntimeError(f"unpark into {seq} refused")
+
     def set_shared_attention(self, on=True, min_tiles=None, min_members=None, min_covered=None):
         """gpt2_decode_set_shared_attention: the decode attention streams the
         leading 64-token tiles that up to 8 forks hold in the same pages once
@@ -1435,6 +1551,12 @@ class Model:
     def seed_sequence(self, seq, seed):
         """restart sequence seq's coin stream at seed"""
         check(lib().gpt2_decode_seed_sequence(self.h, int(seq), int(seed)), "seed_sequence")
+
+    def sampler_state(self, seq):
+        """sequence seq's sampler state (its coin stream's position); waits for queued work"""
+        st = ctypes.c_ulonglong()
+        check(lib().gpt2_decode_sampler_state(self.h, int(seq), ctypes.byref(st)), "sampler_state")
+        return int(st.value)
 
     def set_processors(self, enable=True):
         """logit processors (penalties by the fed tokens, logit bias) before
