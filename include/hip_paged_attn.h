@@ -291,6 +291,26 @@ int hpa_unpack_frag(const float* src, int rows, int K, float* dst, int ld);
  * Values are fp32 rounded to nearest even (hpa_pack_frag_bf16, device -> device). */
 size_t hpa_frag_bf16_elems(int rows, int K);      /* padded element count (2 bytes each) */
 int hpa_pack_frag_bf16(const float* src, int rows, int K, int ld, void* dst);
+/* fp8 weights (w_dtype = HPA_FP8): weight-only e4m3fn quantisation of W [N][K]
+ * (row n = output channel n), one power-of-two scale per row: s_n = the
+ * smallest power of two with absmax_n / s_n <= 448, computed from the fields of
+ * absmax_n (so absmax_n / s_n lies in (224, 448]); 1 for an all-zero row; the
+ * exponent is clamped to [-64, 64]: a row with absmax below 224 * 2^-64 keeps
+ * 2^-64 and loses resolution, one above 448 * 2^64 keeps 2^64 and saturates.
+ * code = e4m3fn_rne(clamp(w / s_n, -448, 448)) (the division is exact), so
+ * decode(code) * s_n is exactly a bf16 value.
+ * fp8 frag layout ([rows][K], rows padded to 16, K % 64 == 0): the unit of
+ * (16-row block, 64-deep step s) is 1 KiB contiguous, 16 bytes per lane; lane
+ * l = (m % 16) + 16*g holds in dword d the codes of k = 64s + 16d + 4g + {0..3}
+ * (the float4 the same lane reads from the fp32 frag layout at k16-step 4s + d):
+ * bytes 0..7 feed one v_mfma_f32_16x16x32_bf16 k-step, bytes 8..15 the next.
+ * Code (m, k) at ((m/16 * K/64 + k/64) * 64 + m%16 + 16*((k%16)/4)) * 16 +
+ * 4*((k%64)/16) + k%4.  hpa_pack_frag_fp8 (device -> device, deterministic):
+ * W row-major with leading dimension ld, 16-byte aligned; dst_frag
+ * hpa_frag_fp8_bytes(N, K) bytes; scale the padded row count
+ * ((N + 15) / 16 * 16) floats.  Padded rows get code 0 and scale 1. */
+size_t hpa_frag_fp8_bytes(int rows, int K);
+int hpa_pack_frag_fp8(const float* W, int N, int K, int ld, unsigned char* dst_frag, float* scale);
 
 /* per-row LayerNorm statistics travel between kernels as partial sums
  * (sum x, sum x^2) over 16-column tiles: stats[tile][Mp][2]; a consumer sums
@@ -375,7 +395,16 @@ typedef struct {
                              weights in the bf16 frag layout (hpa_pack_frag_bf16), K % 32 == 0;
                              A is rounded to bf16 (RNE) after the LayerNorm, products are
                              summed in fp32 on v_mfma_f32_16x16x32_bf16 (variant 0, 1
-                             or 5; ln_fold_c1 must be NULL); waves 4/8. */
+                             or 5; ln_fold_c1 must be NULL); waves 4/8.
+                             HPA_FP8: w points at e4m3fn codes in the fp8 frag layout
+                             (hpa_pack_frag_fp8), K % 64 == 0, w_scale their per-column
+                             power-of-two scales.  A is rounded to bf16 (RNE) after the
+                             LayerNorm, the codes decode to bf16 exactly, products are summed
+                             in fp32 on v_mfma_f32_16x16x32_bf16 and the folded sum is
+                             multiplied by w_scale[n] once, before the bias: the bf16-weight
+                             numerics on W' = decode(code) * scale.  Variant 0 / 1 only
+                             (5 and the fp32-only variants are refused); ln_fold_c1 must be
+                             NULL; waves 4/8, the bf16 kernel's (row_blocks, col_tiles). */
     /* LOGITS on the activation-resident kernel (variant 4, fp32) only: non-NULL
      * pick_next makes the launch's last workgroup to finish (an arrival ticket on
      * pick_count: one int, zero before the first launch, left zero) reduce the
@@ -387,7 +416,7 @@ typedef struct {
     int* pick_tokens;
     int* pick_pos;
     int* pick_count;
-    /* SCORE (looped fp32 kernel: variant 0 / 1; bf16 weights: variant 0 / 1 / 5; any other
+    /* SCORE (looped fp32 kernel: variant 0 / 1; bf16 weights: variant 0 / 1 / 5; fp8 weights: 0 / 1; any other
      * variant is refused).  score_target: device [M], the column whose logit each row
      * reports, -1 (or a NULL array) = none.  score_part: device, hpa_score_workspace(N,
      * Mp) floats, 16-byte aligned; per (16-column tile t, row m) one float4 at
@@ -399,6 +428,8 @@ typedef struct {
      * Rows M <= m < Mp get (-inf, 0, -inf, 16 t): no NaN.  hpa_score_final combines them. */
     const int* score_target;
     float* score_part;
+    const float* w_scale; /* w_dtype = HPA_FP8 only: device [N], the weight's scale per output
+                             column (hpa_pack_frag_fp8 writes it); else not read */
 } HpaFusedGemm;
 /* LayerNorm folding for hpa_gemm_fused (layernorm_forward :49-89 followed by
  * matmul_forward :92-114, restated): for W [N][K] row-major (device), writes
@@ -432,6 +463,9 @@ void hpa_fused_pick(int M, int N, int K, int* out3);
 /* the launch shape of a bf16-weight GEMM (w_dtype = HPA_BF16) when waves /
  * row_blocks / col_tiles are 0 */
 void hpa_fused_pick_bf16(int M, int N, int K, int* out3);
+/* the launch shape of an fp8-weight GEMM (w_dtype = HPA_FP8): waves by K alone
+ * (8 from K = 2048, else 4), row blocks and column tiles as the bf16 table */
+void hpa_fused_pick_fp8(int M, int N, int K, int* out3);
 /* bf16 weights, A-resident kernel (variant 5: the workgroup's rows of A
  * LayerNorm'ed and rounded into LDS once, waves walking waves*rounds column
  * tiles over the whole K; col_tiles = rounds for this variant):

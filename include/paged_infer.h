@@ -168,7 +168,13 @@ int  gpt2_decode_init_ex(GPT2* model, int B, int page_size, int max_ctx, int kv_
  * "bf16 decode" -- the layer and logits weights packed bf16 in HBM, GEMM
  * inputs rounded to bf16 after their LayerNorm, fp32 accumulation on
  * v_mfma_f32_16x16x32_bf16; LayerNorm, attention, residuals, GELU, softmax
- * stay fp32) */
+ * stay fp32) or HPA_FP8 (2: weight-only fp8 -- the same matrices as e4m3fn
+ * codes, one byte each, with one power-of-two scale per output channel
+ * (hip_paged_attn.h, hpa_pack_frag_fp8), quantised at init from the fp32
+ * checkpoint; the bf16 mode's arithmetic on the dequantised weights
+ * decode(code) * scale, which are exactly bf16 values.  The embedding gather
+ * keeps reading the fp32 wte.  Five launches per layer for every layer-kernel
+ * request: the persistent chains take fp32 and bf16 packs only) */
 int  gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dtype, int w_dtype);
 /* one decode step for every sequence: tokens[b] (host) at position pos[b];
  * tokens == NULL feeds back the previous step's greedy ids (device-resident).
@@ -678,7 +684,8 @@ int  gpt2_decode_layer_kernel(GPT2* model);
  * global), so every routing rule can be checked without a GPU.  request 0..7
  * as gpt2_decode_set_layer_kernel; B the engine's batch (eligibility) and
  * pick_B the batch its shape picks follow (gpt2_decode_set_global_batch, else
- * B); kv_dtype HPA_F32 / HPA_BF16 / HPA_FP8; w_bf16 1 for bf16 weights (fp32
+ * B); kv_dtype HPA_F32 / HPA_BF16 / HPA_FP8; w_bf16 1 for bf16 weights, 2 for fp8
+ * weights (five launches per layer for every request) (fp32
  * weights are taken to have their LN-fold pack, as gpt2_decode_init* makes
  * it); num_cus the device's CU count (hpa_device_info).  out5:
  *   [0] form         what gpt2_decode_layer_kernel reports (0..5, above)
@@ -721,6 +728,11 @@ int    gpt2_decode_evicted(GPT2* model, int* mask);
 int    gpt2_decode_set_kv_scales(GPT2* model, const float* k_scale, const float* v_scale);
 /* the scales in use (either array may be NULL); nonzero on a non-fp8 engine */
 int    gpt2_decode_kv_scales(GPT2* model, float* k_scale, float* v_scale);
+/* fp8 weights (gpt2_decode_init_w with w_dtype = HPA_FP8): the power-of-two
+ * scale of every output channel (hip_paged_attn.h, hpa_pack_frag_fp8), into
+ * out [L * 9C + V]: per layer qkvw [3C], attprojw [C], fcw [4C], fcprojw [C],
+ * then wte [V].  Nonzero on an engine with fp32 / bf16 weights. */
+int    gpt2_decode_weight_scales(GPT2* model, float* out);
 /* K/V of positions [0, n) of sequence b at layer l, token-major [n][C] host
  * arrays (the reference page layout, block_manager.c:145-146); bf16 / fp8
  * pools: the values the stored codes stand for (fp8: decode(code) * scale) */

@@ -822,7 +822,7 @@ int hpa_gemm_fused(const HpaFusedGemm* g) {
 
 static int gemm_fused_launch(const HpaFusedGemm* g, FG& p) {
     int nw, mt, ntw;
-    // SCORE lives in the looped fp32 kernel and the two bf16-weight kernels only
+    // SCORE lives in the looped fp32 kernel, the two bf16-weight kernels and the fp8-weight kernel only
     const bool score = g->epilogue == HPA_FEPI_SCORE;
     HPA_REQUIRE(!score || g->variant == 0 || g->variant == 1 || (g->variant == 5 && g->w_dtype == HPA_BF16),
                 "gemm_fused SCORE: variant 0 or 1 (looped), or 5 on bf16 weights; not one-shot (2), ring (3), "
@@ -857,7 +857,23 @@ static int gemm_fused_launch(const HpaFusedGemm* g, FG& p) {
         if (ntw == 2 && mt == 1) ntw = 1;
         return launch_b16(p, g->epilogue, nw, mt, ntw);
     }
-    HPA_REQUIRE(g->w_dtype == HPA_F32, "gemm_fused: w_dtype must be HPA_F32 or HPA_BF16");
+    if (g->w_dtype == HPA_FP8) {  // fp8 weights: hpa_gemm_fp8w.hip
+        HPA_REQUIRE(g->variant == 0 || g->variant == 1,
+                    "gemm_fused fp8 weights: variant 0 or 1 (the looped fp8-weight kernel); not the A-resident "
+                    "bf16 kernel (5) or an fp32-only variant (2, 3, 4, 6)");
+        HPA_REQUIRE(!g->ln_fold_c1, "gemm_fused fp8 weights: ln_fold_c1 must be NULL (LN on the operand path)");
+        HPA_REQUIRE(g->w_scale, "gemm_fused fp8 weights: w_scale is NULL");
+        HPA_REQUIRE(g->K % 64 == 0, "gemm_fused fp8 weights: K % 64 != 0");
+        int pk[3];
+        hpa_fused_pick_fp8(g->M, g->N, g->K, pk);
+        nw = g->waves ? g->waves : pk[0];
+        mt = g->row_blocks ? g->row_blocks : pk[1];
+        ntw = g->col_tiles ? g->col_tiles : pk[2];
+        while (mt > 1 && (p.Mp / 16) % mt) mt >>= 1;  // row blocks of this M
+        if (ntw == 2 && mt == 1) ntw = 1;
+        return launch_f8w(p, g->w_scale, g->epilogue, nw, mt, ntw);
+    }
+    HPA_REQUIRE(g->w_dtype == HPA_F32, "gemm_fused: w_dtype must be HPA_F32, HPA_BF16 or HPA_FP8");
     if (g->variant == 6) return launch_sk(p, g->epilogue);  // stream-K (hpa_gemm_sk.hip)
     HPA_REQUIRE(g->row_blocks == 0 || g->row_blocks == 1 || g->row_blocks == 2 || g->row_blocks == 4,
                 "gemm_fused: row_blocks must be 1, 2 or 4");

@@ -167,6 +167,35 @@ struct Epi {
         apply(p, vals, tile, nt0, row0, wsum);
     }
 
+    // finish's fold alone, for a kernel that works on the folded sums before
+    // apply (the fp8-weight kernel scales them): the same stores, barrier and
+    // wave-order sums, kept beside finish so the two stay one text apart.
+    // finish does not call it: routed through it, the fp32 and bf16 instances
+    // came out scheduled differently, and they are held to their ISA.
+    __device__ __forceinline__ static void fold(const f32x4* acc, float* red, float* vals) {
+        const int lane = threadIdx.x & 63;
+        const int w = threadIdx.x >> 6;
+#pragma unroll
+        for (int j = 0; j < NTW; ++j)
+#pragma unroll
+            for (int r = 0; r < MT; ++r)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    red[w * NTW * TE + j * TE + (r * 4 + g) * 64 + lane] = acc[j * MT + r][g];
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < EPT; ++i) {
+            const int e = threadIdx.x + i * NT;
+            float val = 0.f;
+            if (e < NTW * TE) {
+                val = red[e];
+#pragma unroll
+                for (int ww = 1; ww < NW; ++ww) val += red[ww * NTW * TE + e];
+            }
+            vals[i] = val;
+        }
+    }
+
     // the epilogue proper on the folded values of the owned elements (vals[i]
     // = element threadIdx.x + i*NT); tile = LDS scratch for the row statistics
     __device__ __forceinline__ void apply(const FG& p, const float* vals, float* tile, int nt0, int row0,
@@ -677,6 +706,9 @@ int logits_resident_grid(const FG& p);  // workgroups = argmax partials per row 
 // bf16-weight GEMM launch (hpa_gemm_bf16.hip): waves 4/8, (row_blocks,
 // col_tiles) in {(1,1), (2,1), (4,1), (2,2), (4,2)}
 int launch_b16(const FG& p, int epi, int nw, int mt, int ntw);
+// fp8-weight GEMM launch (hpa_gemm_fp8w.hip): e4m3 codes in the fp8 frag
+// layout, w_scale [N] per output column; the shapes of launch_b16
+int launch_f8w(const FG& p, const float* w_scale, int epi, int nw, int mt, int ntw);
 // A-resident bf16 variant (variant 5): waves 4/8, row_blocks (mt) 1/2/4 with
 // mt*K <= 3200; each workgroup takes waves*rounds column tiles
 int launch_b16_ares(const FG& p, int epi, int nw, int mt, int rounds);

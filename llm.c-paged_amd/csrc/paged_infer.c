@@ -652,7 +652,10 @@ struct GPT2Decode {
     int* ring_cnt;
     size_t ring_cnt_n;
     float* d_wpack;   /* packed qkvw, attprojw, fcw, fcprojw of every layer, then wte */
-    int w_bf16;       /* weights packed bf16 (hpa_pack_frag_bf16; offsets in elements) */
+    int w_dtype;      /* HPA_F32, HPA_BF16 (hpa_pack_frag_bf16) or HPA_FP8 (hpa_pack_frag_fp8): the
+                         packs' storage; offsets in elements of it */
+    float* d_wscale;  /* fp8 weights: the scale of every output channel -- per layer qkv [3C],
+                         attproj [C], fc [4C], fcproj [C], then wte [V padded to 16]; else NULL */
     size_t wpack_off[5]; /* per-layer offsets (0..3) and wte offset (4) */
     size_t wpack_layer;  /* elements of one layer's four packs */
     float* d_fold;    /* LN folded into qkvw / fcw (hpa_ln_fold_pack): per layer c1, c2 of
@@ -962,6 +965,7 @@ static void dec_free(GPT2Decode* d) {
     hpa_free(d->sk_slab); hpa_free(d->sk_cnt);
     hpa_free(d->ring_slab); hpa_free(d->ring_cnt);
     hpa_free(d->d_wpack);
+    hpa_free(d->d_wscale);
     hpa_free(d->d_fold);
     hpa_free(d->d_attn_ws);
     hpa_free(d->d_sh); hpa_free(d->d_sh_ws);
@@ -992,9 +996,19 @@ void gpt2_decode_free(GPT2* model) {
     }
 }
 
-/* packed weights at element offset off (fp32 or bf16 pack) */
+/* bytes per packed weight element */
+static size_t wpack_elem_bytes(const GPT2Decode* d) {
+    return d->w_dtype == HPA_FP8 ? 1 : d->w_dtype == HPA_BF16 ? 2 : 4;
+}
+
+/* packed weights at element offset off (fp32, bf16 or fp8 pack) */
 static const float* wpack_at(const GPT2Decode* d, size_t off) {
-    return d->w_bf16 ? (const float*)((const unsigned short*)d->d_wpack + off) : d->d_wpack + off;
+    return (const float*)((const char*)d->d_wpack + off * wpack_elem_bytes(d));
+}
+
+/* fp8 weights: the scales of wte's rows (else NULL) */
+static const float* wte_scale(const GPT2Decode* d, const GPT2Config* c) {
+    return d->d_wscale ? d->d_wscale + (size_t)c->num_layers * 9 * c->channels : NULL;
 }
 
 /* layer l's operands: where dec_init_weights packs them and every launch
@@ -1005,6 +1019,7 @@ static const float* wpack_at(const GPT2Decode* d, size_t off) {
 #define DEC_FOLD_C 14 /* 3 + 3 + 4 + 4 */
 typedef struct {
     const float *w_qkv, *w_ap, *w_fc, *w_fp;
+    const float *s_qkv, *s_ap, *s_fc, *s_fp; /* fp8 weights: their per-channel scales, else NULL */
     const float *qkv_c1, *qkv_c2, *fc_c1, *fc_c2;
     const float *b_qkv, *b_ap, *b_fc, *b_fp; /* checkpoint biases */
     const float *ln1_w, *ln1_b, *ln2_w, *ln2_b;
@@ -1019,6 +1034,11 @@ static DecLayerOps dec_layer_ops(const GPT2* model, const GPT2Decode* d, int l) 
     o.w_ap = wpack_at(d, d->wpack_layer * l + d->wpack_off[1]);
     o.w_fc = wpack_at(d, d->wpack_layer * l + d->wpack_off[2]);
     o.w_fp = wpack_at(d, d->wpack_layer * l + d->wpack_off[3]);
+    const float* sl = d->d_wscale ? d->d_wscale + 9 * lc : NULL;
+    o.s_qkv = sl;
+    o.s_ap = sl ? sl + 3 * C : NULL;
+    o.s_fc = sl ? sl + 4 * C : NULL;
+    o.s_fp = sl ? sl + 8 * C : NULL;
     o.qkv_c1 = fl;
     o.qkv_c2 = fl ? fl + 3 * C : NULL;
     o.fc_c1 = fl ? fl + 6 * C : NULL;
@@ -1050,9 +1070,28 @@ static int dec_init_weights(GPT2* model, GPT2Decode* d) {
     d->wpack_off[3] = e_qkv + e_ap + e_fc;
     d->wpack_off[4] = e_layer * L; /* wte */
     const size_t total = d->wpack_off[4] + hpa_frag_elems(V, C);
-    d->d_wpack = (float*)hpa_malloc(total * (d->w_bf16 ? 2 : 4));
+    d->d_wpack = (float*)hpa_malloc(total * wpack_elem_bytes(d));
     if (!d->d_wpack) return 1;
-    if (d->w_bf16) { /* bf16 weights: same element offsets, 2 bytes each; LN on the operand path */
+    if (d->w_dtype == HPA_FP8) { /* fp8 weights: same element offsets, 1 byte each, and one scale per
+                                  * output channel; LN on the operand path; the embedding gather
+                                  * keeps reading the fp32 checkpoint wte */
+        d->d_wscale = (float*)hpa_malloc(((size_t)L * 9 * C + (size_t)(V + 15) / 16 * 16) * sizeof(float));
+        if (!d->d_wscale) return 1;
+        for (int l = 0; l < L; l++) {
+            const DecLayerOps o = dec_layer_ops(model, d, l);
+            const size_t lc = (size_t)l * C;
+            if (hpa_pack_frag_fp8(w->qkvw + lc * 3 * C, 3 * C, C, C, (unsigned char*)o.w_qkv, (float*)o.s_qkv) ||
+                hpa_pack_frag_fp8(w->attprojw + lc * C, C, C, C, (unsigned char*)o.w_ap, (float*)o.s_ap) ||
+                hpa_pack_frag_fp8(w->fcw + lc * 4 * C, 4 * C, C, C, (unsigned char*)o.w_fc, (float*)o.s_fc) ||
+                hpa_pack_frag_fp8(w->fcprojw + lc * 4 * C, C, 4 * C, 4 * C, (unsigned char*)o.w_fp, (float*)o.s_fp))
+                return 1;
+        }
+        if (hpa_pack_frag_fp8(w->wte, V, C, C, (unsigned char*)wpack_at(d, d->wpack_off[4]), (float*)wte_scale(d, &c)))
+            return 1;
+        for (int i = 0; i < 5; i++) d->fwaves[i] = d->frb[i] = d->fct[i] = 0; /* hpa_fused_pick_fp8 in the library */
+        return 0;
+    }
+    if (d->w_dtype == HPA_BF16) { /* bf16 weights: same element offsets, 2 bytes each; LN on the operand path */
         for (int l = 0; l < L; l++) {
             const DecLayerOps o = dec_layer_ops(model, d, l);
             const size_t lc = (size_t)l * C;
@@ -1102,7 +1141,7 @@ static int dec_init_weights(GPT2* model, GPT2Decode* d) {
  * engine's own B (a shard then computes what a single-GPU engine of its rows
  * computes) */
 static int dec_pick_B(const GPT2Decode* d) {
-    const int lim = d->w_bf16 ? 256 : 64;
+    const int lim = d->w_dtype == HPA_BF16 ? 256 : 64;
     return d->pl_global_B > 0 && d->pl_global_B <= lim ? d->pl_global_B : d->B;
 }
 
@@ -1184,6 +1223,9 @@ static int dec_set_splits(GPT2Decode* d, int splits) {
 static DecPlan dec_plan(int want, int B, int pick_B, int C, int num_heads, int max_ctx, int kv_dtype, int w_bf16,
                         int have_fold, int num_cus, int ab_build, int full_splits) {
     const DecPlan five = {0, 0, 1, 0, 0};
+    /* fp8 weights (w_bf16 = 2) live in the GEMM launches only: five launches
+     * per layer for every request; the chains know fp32 and bf16 packs */
+    if (w_bf16 == 2) return five;
     /* an fp8 pool's K/V are appended by chain form 6 (with the step's first
      * launch) and by the GEMM launches' shared epilogue only: auto and form 5
      * give chain form 6 where it applies, every other pick -- the bf16 chain
@@ -1238,7 +1280,7 @@ int gpt2_decode_layer_plan(int request, int B, int pick_B, int C, int num_heads,
                            int w_bf16, int num_cus, int out5[5]) {
     if (!out5) return 1;
     const DecPlan p = dec_plan(request < 0 ? 0 : request > 7 ? 7 : request, B, pick_B, C, num_heads, max_ctx,
-                               kv_dtype, w_bf16, !w_bf16, num_cus, hpa_build_flags() & 1, 0);
+                               kv_dtype, w_bf16 == 2 ? 2 : !!w_bf16, !w_bf16, num_cus, hpa_build_flags() & 1, 0);
     out5[0] = p.form; out5[1] = p.chain; out5[2] = p.splits; out5[3] = p.first; out5[4] = p.attn_launch;
     return 0;
 }
@@ -1320,7 +1362,7 @@ static int dec_layer_setup(GPT2* model, GPT2Decode* d) {
     if (env) full_splits = atoi(env);
 #endif
     const DecPlan p = dec_plan(d->pl_want, d->B, dec_pick_B(d), c.channels, c.num_heads, d->max_ctx, d->pool.dtype,
-                               d->w_bf16, d->d_fold != NULL, ncu, hpa_build_flags() & 1, full_splits);
+                               d->w_dtype, d->d_fold != NULL, ncu, hpa_build_flags() & 1, full_splits);
     d->plan = five;
     if (dec_layer_workspace(model, d, &p)) return 1;
     d->plan = p;
@@ -1443,8 +1485,8 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
         fprintf(stderr, "[paged_infer] kv dtype must be HPA_F32, HPA_BF16 or HPA_FP8\n");
         return 1;
     }
-    if (w_dtype != HPA_F32 && w_dtype != HPA_BF16) {
-        fprintf(stderr, "[paged_infer] weight dtype must be HPA_F32 or HPA_BF16\n");
+    if (w_dtype != HPA_F32 && w_dtype != HPA_BF16 && w_dtype != HPA_FP8) {
+        fprintf(stderr, "[paged_infer] weight dtype must be HPA_F32, HPA_BF16 or HPA_FP8\n");
         return 1;
     }
     if (!model->params_memory) { fprintf(stderr, "[paged_infer] model not built\n"); return 1; }
@@ -1573,7 +1615,7 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
     /* logits GEMM: the activation-resident kernel where it applies (C = 768,
      * B <= 64); stream-K where its shape limits allow (XL at B <= 64), which
      * needs a slab and zeroed counters; else the looped kernel */
-    if (ok && w_dtype != HPA_BF16 && hpa_logits_kernel(B, V, C) == 6) {
+    if (ok && w_dtype == HPA_F32 && hpa_logits_kernel(B, V, C) == 6) {
         size_t nf = 0, nc = 0;
         ok = hpa_gemm_sk_workspace(V, &nf, &nc) == 0;
         if (ok) {
@@ -1585,7 +1627,7 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
     }
     /* the ring qkv / fc of wide layers (dec_gemm): K split in DEC_RING_QKV_PARTS /
      * DEC_RING_FC_PARTS parts over workgroups, one slab + counters for both */
-    if (ok && w_dtype != HPA_BF16 && C >= 1024 && dec_ring_allowed() == 2) {
+    if (ok && w_dtype == HPA_F32 && C >= 1024 && dec_ring_allowed() == 2) {
         size_t f1 = 0, c1 = 0, f2 = 0, c2 = 0;
         ok = hpa_gemm_ring_workspace(3 * C, DEC_RING_QKV_PARTS, &f1, &c1) == 0 &&
              hpa_gemm_ring_workspace(4 * C, DEC_RING_FC_PARTS, &f2, &c2) == 0;
@@ -1612,7 +1654,7 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
         dec_free(d);
         return 1;
     }
-    d->w_bf16 = w_dtype == HPA_BF16;
+    d->w_dtype = w_dtype;
     int ncu = 0;
     hpa_device_info(NULL, 0, &ncu, NULL);
     if (dec_init_weights(model, d) || dec_set_splits(d, dec_pick_splits(d, B, ncu))) {
@@ -1760,7 +1802,7 @@ static void dec_gemm_desc(GPT2* model, int l, int which, HpaFusedGemm* g) {
     const DecLayerOps o = dec_layer_ops(model, d, l);
     memset(g, 0, sizeof(*g));
     g->M = d->B;
-    g->w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
+    g->w_dtype = d->w_dtype;
     g->epilogue = which == G_QKV ? HPA_FEPI_QKV : which == G_FC ? HPA_FEPI_GELU
                 : which == G_LOGITS ? HPA_FEPI_LOGITS : HPA_FEPI_RESID;
     g->waves = d->fwaves[which];
@@ -1774,32 +1816,34 @@ static void dec_gemm_desc(GPT2* model, int l, int which, HpaFusedGemm* g) {
     switch (which) {
         case G_QKV: /* LN1 (stats: embedding's 1 tile at layer 0, fcproj's C/16 after) */
             g->x = d->res; g->K = C; g->ln_stats = d->st1; g->ln_ntiles = l == 0 ? 1 : ct;
-            g->ln_w = o.ln1_w; g->ln_b = o.ln1_b; g->w = o.w_qkv;
+            g->ln_w = o.ln1_w; g->ln_b = o.ln1_b; g->w = o.w_qkv; g->w_scale = o.s_qkv;
             g->N = 3 * C; g->bias = o.b_qkv; g->out = d->d_q;
             if (d->d_fold) { g->ln_fold_c1 = o.qkv_c1; g->bias = o.qkv_c2; }
             break;
         case G_ATTPROJ: /* res2 = res + att . Wap^T + b (LN2 statistics only when fc needs them) */
-            g->x = d->att; g->K = C; g->w = o.w_ap; g->N = C;
+            g->x = d->att; g->K = C; g->w = o.w_ap; g->w_scale = o.s_ap; g->N = C;
             g->bias = o.b_ap; g->out = d->res2; g->res_in = d->res; g->stats_out = d->d_fold ? NULL : d->st2;
             break;
         case G_FC: /* gelu(LN2(res2) . Wfc^T + b) */
             g->x = d->res2; g->K = C; g->ln_stats = d->st2; g->ln_ntiles = ct; g->ln_w = o.ln2_w;
-            g->ln_b = o.ln2_b; g->w = o.w_fc; g->N = 4 * C;
+            g->ln_b = o.ln2_b; g->w = o.w_fc; g->w_scale = o.s_fc; g->N = 4 * C;
             g->bias = o.b_fc; g->out = d->fch;
             if (d->d_fold) { g->ln_fold_c1 = o.fc_c1; g->bias = o.fc_c2; }
             break;
         case G_FCPROJ: /* res = res2 + fch . Wfp^T + b, next-LN statistics */
-            g->x = d->fch; g->K = 4 * C; g->w = o.w_fp; g->N = C;
+            g->x = d->fch; g->K = 4 * C; g->w = o.w_fp; g->w_scale = o.s_fp; g->N = C;
             g->bias = o.b_fp; g->out = d->res; g->res_in = d->res2;
             g->stats_out = d->d_fold && l + 1 < c.num_layers ? NULL : d->st1; /* LNf of logits: last layer */
             break;
         default: /* logits = LNf(res) . wte^T, argmax partials */
             g->x = d->res; g->K = C; g->ln_stats = d->st1; g->ln_ntiles = ct;
             g->ln_w = w->lnfw; g->ln_b = w->lnfb; g->w = wpack_at(d, d->wpack_off[4]); g->N = V;
+            g->w_scale = wte_scale(d, &c);
             g->out = d->d_logits; g->part_out = d->part; g->layer = 0;
+            if (d->w_dtype == HPA_FP8) break; /* the fp8-weight kernel, shapes by hpa_fused_pick_fp8 */
             g->variant = 4; /* activation-resident kernel where the shape allows (hpa_logits.hip), */
             g->sk_slab = d->sk_slab; g->sk_count = d->sk_cnt; /* else stream-K with this workspace */
-            if (!d->w_bf16 && hpa_logits_kernel(d->B, V, C) == 4) { /* its form by the GLOBAL batch: a */
+            if (d->w_dtype == HPA_F32 && hpa_logits_kernel(d->B, V, C) == 4) { /* its form by the GLOBAL batch: a */
                 const int Bg = dec_pick_B(d); /* row's sum order (global picks: sharded = */
                 g->waves = Bg > 32 ? 12 : 16;                             /* unsharded bit for bit) */
             }
@@ -1832,7 +1876,7 @@ static int dec_gemm(GPT2* model, int l, int which) {
         GPT2Decode* d = model->decode;
         const int Bg = dec_pick_B(d);
         const int ring = dec_ring_allowed();
-        if ((which == G_QKV || which == G_FC) && !d->w_bf16 && d->d_fold && model->config.channels >= 1024 &&
+        if ((which == G_QKV || which == G_FC) && d->w_dtype == HPA_F32 && d->d_fold && model->config.channels >= 1024 &&
             Bg > 48 && d->B <= 64 && ring) {
             g.variant = 3;
             /* HPA_GEMM_RING=2: K split over workgroups so all CUs compute (qkv
@@ -2735,12 +2779,13 @@ static int prefill_gemm(GPT2* model, int l, int which, int R) {
     HpaFusedGemm g;
     memset(&g, 0, sizeof(g));
     g.M = R;
-    g.w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
+    g.w_dtype = d->w_dtype;
     /* many rows: reuse every activation fragment over 2 weight tiles and every
      * weight fragment over 4 row blocks (MFMA-bound at this M) */
-    g.waves = d->w_bf16 ? 0 : 8; /* bf16 weights: the library's shapes by (M, N, K) */
-    g.row_blocks = d->w_bf16 ? 0 : 4;
-    g.col_tiles = d->w_bf16 ? 0 : 2;
+    const int lib_shape = d->w_dtype != HPA_F32; /* bf16 / fp8 weights: the library's shapes by (M, N, K) */
+    g.waves = lib_shape ? 0 : 8;
+    g.row_blocks = lib_shape ? 0 : 4;
+    g.col_tiles = lib_shape ? 0 : 2;
     g.pool = &d->pool;
     g.layer = l;
     g.block_table = d->d_bt;
@@ -2751,23 +2796,23 @@ static int prefill_gemm(GPT2* model, int l, int which, int R) {
         case G_QKV:
             g.epilogue = HPA_FEPI_QKV; g.x = d->pf_res; g.K = C; g.ln_stats = d->pf_st1;
             g.ln_ntiles = l == 0 ? 1 : ct; g.ln_w = o.ln1_w; g.ln_b = o.ln1_b;
-            g.w = o.w_qkv; g.N = 3 * C; g.bias = o.b_qkv; g.out = d->pf_q;
+            g.w = o.w_qkv; g.w_scale = o.s_qkv; g.N = 3 * C; g.bias = o.b_qkv; g.out = d->pf_q;
             if (d->pf_slot) g.pos = d->pf_slot; /* a tree pass appends node i at start + i, whatever its depth */
             if (d->d_fold) { g.ln_fold_c1 = o.qkv_c1; g.bias = o.qkv_c2; }
             break;
         case G_ATTPROJ:
-            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_att; g.K = C; g.w = o.w_ap;
+            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_att; g.K = C; g.w = o.w_ap; g.w_scale = o.s_ap;
             g.N = C; g.bias = o.b_ap; g.out = d->pf_res2; g.res_in = d->pf_res;
             g.stats_out = d->d_fold ? NULL : d->pf_st2;
             break;
         case G_FC:
             g.epilogue = HPA_FEPI_GELU; g.x = d->pf_res2; g.K = C; g.ln_stats = d->pf_st2; g.ln_ntiles = ct;
-            g.ln_w = o.ln2_w; g.ln_b = o.ln2_b; g.w = o.w_fc;
+            g.ln_w = o.ln2_w; g.ln_b = o.ln2_b; g.w = o.w_fc; g.w_scale = o.s_fc;
             g.N = 4 * C; g.bias = o.b_fc; g.out = d->pf_fch;
             if (d->d_fold) { g.ln_fold_c1 = o.fc_c1; g.bias = o.fc_c2; }
             break;
         default: /* G_FCPROJ */
-            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_fch; g.K = 4 * C; g.w = o.w_fp;
+            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_fch; g.K = 4 * C; g.w = o.w_fp; g.w_scale = o.s_fp;
             g.N = C; g.bias = o.b_fp; g.out = d->pf_res; g.res_in = d->pf_res2;
             g.stats_out = d->d_fold && l + 1 < c.num_layers ? NULL : d->pf_st1;
             break;
@@ -2789,7 +2834,7 @@ static int prefill_all_logits(GPT2* model, int R, float* rows_out, const int* ou
     HpaFusedGemm g;
     memset(&g, 0, sizeof(g));
     g.M = R;
-    g.w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
+    g.w_dtype = d->w_dtype;
     g.epilogue = HPA_FEPI_LOGITS;
     g.x = d->pf_res;
     g.K = C;
@@ -2798,6 +2843,7 @@ static int prefill_all_logits(GPT2* model, int R, float* rows_out, const int* ou
     g.ln_w = model->params.lnfw;
     g.ln_b = model->params.lnfb;
     g.w = wpack_at(d, d->wpack_off[4]);
+    g.w_scale = wte_scale(d, &model->config);
     g.N = V;
     g.out = rows_out;
     g.row_seq = out_rows; /* LOGITS: GEMM row -> row of rows_out (NULL: the same) */
@@ -2878,7 +2924,7 @@ static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
         HpaFusedGemm g;
         memset(&g, 0, sizeof(g));
         g.M = n;
-        g.w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
+        g.w_dtype = d->w_dtype;
         g.epilogue = HPA_FEPI_SCORE;
         g.x = d->sc_x;
         g.K = C;
@@ -2887,6 +2933,7 @@ static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
         g.ln_w = model->params.lnfw;
         g.ln_b = model->params.lnfb;
         g.w = wpack_at(d, d->wpack_off[4]);
+        g.w_scale = wte_scale(d, &model->config);
         g.N = V;
         g.score_target = d->sc_tgt;
         g.score_part = d->sc_part;
@@ -2956,7 +3003,7 @@ static int dec_score_top_rows(GPT2* model, int R, const DecScore* sc) {
         HpaFusedGemm g;
         memset(&g, 0, sizeof(g));
         g.M = n;
-        g.w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
+        g.w_dtype = d->w_dtype;
         g.epilogue = HPA_FEPI_LOGITS;
         g.x = d->sc_x;
         g.K = C;
@@ -2965,6 +3012,7 @@ static int dec_score_top_rows(GPT2* model, int R, const DecScore* sc) {
         g.ln_w = model->params.lnfw;
         g.ln_b = model->params.lnfb;
         g.w = wpack_at(d, d->wpack_off[4]);
+        g.w_scale = wte_scale(d, &model->config);
         g.N = V;
         g.out = d->st_logits;
         g.part_out = d->sc_part; /* (V + 15) / 16 * np * 2 floats: half the SCORE partials' room */
@@ -3225,7 +3273,7 @@ static int dec_spec_dense(GPT2* model, int R, int ND, const int* hrows, const in
         HpaFusedGemm g;
         memset(&g, 0, sizeof(g));
         g.M = n;
-        g.w_dtype = d->w_bf16 ? HPA_BF16 : HPA_F32;
+        g.w_dtype = d->w_dtype;
         g.epilogue = HPA_FEPI_LOGITS;
         g.x = d->sc_x;
         g.K = C;
@@ -3234,6 +3282,7 @@ static int dec_spec_dense(GPT2* model, int R, int ND, const int* hrows, const in
         g.ln_w = model->params.lnfw;
         g.ln_b = model->params.lnfb;
         g.w = wpack_at(d, d->wpack_off[4]);
+        g.w_scale = wte_scale(d, &model->config);
         g.N = V;
         g.out = d->st_logits;
         g.part_out = d->sc_part; /* not read (dec_score_top_rows) */
@@ -3988,6 +4037,17 @@ int gpt2_decode_set_kv_scales(GPT2* model, const float* k_scale, const float* v_
     return 0;
 }
 
+int gpt2_decode_weight_scales(GPT2* model, float* out) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d || !d->d_wscale || !out) {
+        fprintf(stderr, "[paged_infer] gpt2_decode_weight_scales: needs an fp8-weight engine (gpt2_decode_init_w)\n");
+        return 1;
+    }
+    const GPT2Config c = model->config;
+    const size_t n = (size_t)c.num_layers * 9 * c.channels + c.vocab_size;
+    return hpa_synchronize() || hpa_memcpy(out, d->d_wscale, n * sizeof(float));
+}
+
 int gpt2_decode_kv_scales(GPT2* model, float* k_scale, float* v_scale) {
     GPT2Decode* d = model ? model->decode : NULL;
     if (!d || d->pool.dtype != HPA_FP8) return 1;
@@ -4191,8 +4251,9 @@ double gpt2_decode_step_bytes(GPT2* model, double* attn_bytes) {
     const GPT2Config c = model->config;
     const double C = c.channels, L = c.num_layers, V = c.vocab_size, w = 4.0;
     const double wkv = (double)d->pool.elem_bytes; /* fp32, bf16 or fp8 KV storage */
-    const double wm = d->w_bf16 ? 2.0 : 4.0; /* GEMM weight matrices: bf16 or fp32 */
-    const double weights = (L * 12 * C * C + V * C) * wm + (L * 13 * C + 2 * C) * w;
+    const double wm = (double)wpack_elem_bytes(d); /* GEMM weight matrices: fp32, bf16 or fp8 */
+    const double wsc = d->w_dtype == HPA_FP8 ? (L * 9 * C + V) * w : 0.0; /* fp8: one scale per output channel */
+    const double weights = (L * 12 * C * C + V * C) * wm + wsc + (L * 13 * C + 2 * C) * w;
     double kv = 0.0;
     for (int b = 0; b < d->B; b++) kv += 2.0 * L * (d->h_pos[b] + 1) * C * wkv;
     const double append = 2.0 * L * d->B * C * wkv;

@@ -60,7 +60,7 @@ class HpaFusedGemm(ctypes.Structure):
                 ("row_blocks", ctypes.c_int), ("variant", ctypes.c_int), ("col_tiles", ctypes.c_int),
                 ("row_seq", _V), ("ln_fold_c1", _V), ("sk_slab", _V), ("sk_count", _V),
                 ("w_dtype", ctypes.c_int), ("pick_next", _V), ("pick_tokens", _V), ("pick_pos", _V),
-                ("pick_count", _V), ("score_target", _V), ("score_part", _V)]
+                ("pick_count", _V), ("score_target", _V), ("score_part", _V), ("w_scale", _V)]
 
 
 class HpaChainB16Args(ctypes.Structure):
@@ -122,6 +122,22 @@ def from_frag_bf16(bits_u16, rows, K):
     """bf16 frag layout (hpa_pack_frag_bf16, the chain's fch) -> [rows][K] bf16 bit patterns"""
     m, k = np.meshgrid(np.arange(rows), np.arange(K), indexing="ij")
     return np.asarray(bits_u16, np.uint16)[frag_bf16_index(m, k, K)]
+
+
+def frag_fp8_index(m, k, K):
+    """byte of code (m, k) of a [rows][K] matrix in the fp8 frag layout (hip_paged_attn.h;
+    vectorised over m, k): the 16 bytes of lane m % 16 + 16 * ((k % 16) / 4) of (row block
+    m / 16, 64-deep step k / 64), dword (k % 64) / 16 of them"""
+    m = np.asarray(m)
+    k = np.asarray(k)
+    return ((((m >> 4) * (K >> 6) + (k >> 6)) * 64 + ((m & 15) + 16 * ((k >> 2) & 3))) << 4) + \
+        4 * ((k >> 4) & 3) + (k & 3)
+
+
+def from_frag_fp8(codes_u8, rows, K):
+    """fp8 frag layout (hpa_pack_frag_fp8) -> [rows][K] e4m3fn codes"""
+    m, k = np.meshgrid(np.arange(rows), np.arange(K), indexing="ij")
+    return np.asarray(codes_u8, np.uint8)[frag_fp8_index(m, k, K)]
 
 
 GPT2_124M = dict(maxT=1024, V=50257, L=12, NH=12, C=768)
@@ -292,6 +308,9 @@ def lib():
     _sig(L, "gpt2_decode_init_w", i, [v, i, i, i, i, i])
     _sig(L, "hpa_pack_frag_bf16", i, [v, i, i, i, v])
     _sig(L, "hpa_frag_bf16_elems", ctypes.c_size_t, [i, i])
+    _sig(L, "hpa_pack_frag_fp8", i, [v, i, i, i, v, v])
+    _sig(L, "hpa_frag_fp8_bytes", ctypes.c_size_t, [i, i])
+    _sig(L, "hpa_fused_pick_fp8", None, [i, i, i, _I])
     _sig(L, "gpt2_decode_prefill", i, [v, _I, i, _I])
     _sig(L, "gpt2_decode_prefill_ragged", i, [v, _I, _I, _I])
     _sig(L, "gpt2_decode_score", i, [v, _I, _I, _I, _F, _I, _I])
@@ -395,6 +414,7 @@ def lib():
     _sig(L, "gpt2_decode_read_kv", i, [v, i, i, i, _F, _F])
     _sig(L, "gpt2_decode_set_kv_scales", i, [v, _F, _F])
     _sig(L, "gpt2_decode_kv_scales", i, [v, _F, _F])
+    _sig(L, "gpt2_decode_weight_scales", i, [v, _F])
     _sig(L, "gpt2_decode_batch", i, [v])
     _sig(L, "gpt2_decode_shard", i, [v, _I, i])
     _sig(L, "gpt2_decode_gather", i, [v, i])
@@ -476,10 +496,11 @@ def layer_plan(request, B, C, num_heads, max_ctx, kv_dtype=0, w_bf16=False, num_
     """what the engine makes of set_layer_kernel(request) for these shapes on a
     device of num_cus CUs (gpt2_decode_layer_plan: the one place that decides
     it; pure, needs no GPU): a dict of PLAN_FIELDS.  pick_B: the global batch
-    of a shard (default: B)."""
+    of a shard (default: B).  w_bf16: False / 0 fp32 weights, True / 1 bf16, 2 fp8
+    (five launches per layer for every request)."""
     out = (ctypes.c_int * 5)()
     check(lib().gpt2_decode_layer_plan(int(request), int(B), int(B if pick_B is None else pick_B), int(C),
-                                       int(num_heads), int(max_ctx), int(kv_dtype), int(bool(w_bf16)),
+                                       int(num_heads), int(max_ctx), int(kv_dtype), 2 if int(w_bf16) == 2 else int(bool(w_bf16)),
                                        int(num_cus), out), "layer_plan")
     return dict(zip(PLAN_FIELDS, out))
 
@@ -691,6 +712,22 @@ def round_fp8(a, scale=1.0):
     inv = (np.float32(1.0) / scale).astype(np.float32)
     a = np.asarray(a, np.float32)
     return (from_fp8_bits(to_fp8_bits((a * inv).astype(np.float32))) * scale).astype(np.float32)
+
+
+def quantize_fp8_rows(W):
+    """weight-only fp8 quantisation of W [N][K], one power-of-two scale per row
+    (hpa_pack_frag_fp8's rule, restated): s_n = the smallest power of two with
+    absmax_n / s_n <= 448, from absmax_n's exponent and mantissa (absmax = m 2^e with
+    m in [0.5, 1): 2^(e - 9) for m <= 0.875, else 2^(e - 8)); exponent clamped to
+    [-64, 64]; 1 for an all-zero row.  Returns (codes uint8 [N][K], scales fp32 [N],
+    W' = decode(codes) * scales, exactly bf16 values)."""
+    W = np.ascontiguousarray(W, np.float32)
+    m, e = np.frexp(np.abs(W).max(axis=1))
+    t = np.clip(np.where(m <= 0.875, e - 9, e - 8), -64, 64)
+    t = np.where(m == 0, 0, t).astype(np.int32)
+    scales = np.ldexp(np.float32(1.0), t).astype(np.float32)
+    codes = to_fp8_bits(np.ldexp(W, -t[:, None]).astype(np.float32))
+    return codes, scales, (from_fp8_bits(codes) * scales[:, None]).astype(np.float32)
 
 
 HPA_F32, HPA_BF16, HPA_FP8 = 0, 1, 2
@@ -1187,6 +1224,13 @@ class Model:
         k, v = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
         check(lib().gpt2_decode_kv_scales(self.h, k.ctypes.data_as(_F), v.ctypes.data_as(_F)), "kv_scales")
         return k, v
+
+    def weight_scales(self):
+        """fp8 weights: the scale of every output channel, [L * 9C + V]: per layer qkvw [3C],
+        attprojw [C], fcw [4C], fcprojw [C], then wte [V] (gpt2_decode_weight_scales)"""
+        out = np.zeros(self.cfg.num_layers * 9 * self.cfg.channels + self.cfg.vocab_size, np.float32)
+        check(lib().gpt2_decode_weight_scales(self.h, out.ctypes.data_as(_F)), "weight_scales")
+        return out
 
     def shard(self, rows_per_rank, root=0):
         """sequence-sharded decode: this rank's row count among rows_per_rank
