@@ -135,7 +135,7 @@ typedef struct HpaKVPool {
     int    managed;
     float* scales;        /* fp8 pools: device [num_layers][2][num_heads][2] (scale, inv); else NULL */
 } HpaKVPool;
-enum { HPA_F32 = 0, HPA_BF16 = 1, HPA_FP8 = 2 };
+enum { HPA_F32 = 0, HPA_BF16 = 1, HPA_FP8 = 2, HPA_FP4 = 3 }; /* HPA_FP4: weights only (hpa_pack_frag_fp4); no pool */
 int  hpa_pool_create(HpaKVPool* pool, int num_layers, int num_heads, int head_size, int page_size,
                      int num_pages, int dtype, int managed);
 void hpa_pool_destroy(HpaKVPool* pool);
@@ -311,6 +311,34 @@ int hpa_pack_frag_bf16(const float* src, int rows, int K, int ld, void* dst);
  * ((N + 15) / 16 * 16) floats.  Padded rows get code 0 and scale 1. */
 size_t hpa_frag_fp8_bytes(int rows, int K);
 int hpa_pack_frag_fp8(const float* W, int N, int K, int ld, unsigned char* dst_frag, float* scale);
+/* fp4 weights (w_dtype = HPA_FP4): weight-only MXFP4 (OCP microscaling) of W
+ * [N][K], K % 64 == 0: e2m1 codes with one e8m0 power-of-two scale per row and
+ * group of 32 consecutive k.  t = the smallest integer with absmax_g / 2^t <= 6,
+ * from the fp32 fields of absmax_g (= m 2^e, m in [0.5, 1): e - 3 for m <= 0.75,
+ * else e - 2), clamped to [-64, 64], 0 for an all-zero group; stored as the byte
+ * t + 127.  code = e2m1_rne(clamp(w 2^-t, -6, 6)): magnitudes 0, 0.5, 1, 1.5, 2,
+ * 3, 4, 6 in bits 0..2, ties to the code with mantissa bit 0, bit 3 = (w < 0).
+ * decode(code) 2^t is exactly a bf16 value.
+ * fp4 frag layout (rows padded to 16): the unit of (16-row block, 64-deep step
+ * s) is 512 B contiguous, 8 bytes per lane; lane l = (m % 16) + 16*g holds in
+ * dword h (0, 1) the codes of k = 64s + 32h + {4g..4g+3, 16+4g..16+4g+3}, four
+ * bits each from bit 0 up (two codes a byte, the lower k in the low nibble): the
+ * eight k of the lane's two float4 in the fp32 frag layout at k16-steps 4s + 2h
+ * and 4s + 2h + 1, i.e. the B fragment of one v_mfma_f32_16x16x32_bf16 k-step
+ * after four v_cvt_scalef32_pk_bf16_fp4.  Code (m, k): nibble (k % 4) + 4*((k %
+ * 32) / 16) of dword (k % 64) / 32 of lane m % 16 + 16*((k % 16) / 4) of unit
+ * (m / 16) * K/64 + k / 64.
+ * Scales: each MFMA k-step is one group per row; the two bytes of (row, step s)
+ * sit together in unit order, [row block][s][16 rows][2], 32 B per unit: byte
+ * (m, k) at (((m/16) * K/64 + k/64) * 16 + m%16) * 2 + (k%64)/32.  The float
+ * scale is (unsigned)byte << 23.
+ * hpa_pack_frag_fp4 (device -> device, deterministic): W row-major, leading
+ * dimension ld, 16-byte aligned; dst_codes hpa_frag_fp4_bytes(N, K) bytes,
+ * 8-byte aligned; dst_scales hpa_frag_mx_scale_bytes(N, K) bytes, 2-byte
+ * aligned.  Padded rows get code 0 and scale byte 127. */
+size_t hpa_frag_fp4_bytes(int rows, int K);
+size_t hpa_frag_mx_scale_bytes(int rows, int K);
+int hpa_pack_frag_fp4(const float* W, int N, int K, int ld, unsigned char* dst_codes, unsigned char* dst_scales);
 
 /* per-row LayerNorm statistics travel between kernels as partial sums
  * (sum x, sum x^2) over 16-column tiles: stats[tile][Mp][2]; a consumer sums
@@ -404,7 +432,16 @@ typedef struct {
                              multiplied by w_scale[n] once, before the bias: the bf16-weight
                              numerics on W' = decode(code) * scale.  Variant 0 / 1 only
                              (5 and the fp32-only variants are refused); ln_fold_c1 must be
-                             NULL; waves 4/8, the bf16 kernel's (row_blocks, col_tiles). */
+                             NULL; waves 4/8, the bf16 kernel's (row_blocks, col_tiles).
+                             HPA_FP4: w points at e2m1 codes in the fp4 frag layout
+                             (hpa_pack_frag_fp4), K % 64 == 0, w_gscale their e8m0 group
+                             scales.  The bf16-weight numerics on W' = decode(code) * 2^t:
+                             the scale is applied at decode, nothing after the fold.
+                             Epilogues QKV, RESID, GELU (LOGITS / SCORE are refused: wte is
+                             fp8 on an fp4 engine).  Variant 0 (hpa_fused_pick_fp4), 1 (looped;
+                             waves 4/8, the bf16 kernel's (row_blocks, col_tiles)) or 5
+                             (A-resident; waves 4/8, row_blocks * K <= 3200, col_tiles =
+                             rounds, 0 = auto); ln_fold_c1 must be NULL. */
     /* LOGITS on the activation-resident kernel (variant 4, fp32) only: non-NULL
      * pick_next makes the launch's last workgroup to finish (an arrival ticket on
      * pick_count: one int, zero before the first launch, left zero) reduce the
@@ -430,6 +467,8 @@ typedef struct {
     float* score_part;
     const float* w_scale; /* w_dtype = HPA_FP8 only: device [N], the weight's scale per output
                              column (hpa_pack_frag_fp8 writes it); else not read */
+    const unsigned char* w_gscale; /* w_dtype = HPA_FP4 only: device, the weight's e8m0 group
+                             scales in unit order (hpa_pack_frag_fp4 writes them); else not read */
 } HpaFusedGemm;
 /* LayerNorm folding for hpa_gemm_fused (layernorm_forward :49-89 followed by
  * matmul_forward :92-114, restated): for W [N][K] row-major (device), writes
@@ -466,6 +505,12 @@ void hpa_fused_pick_bf16(int M, int N, int K, int* out3);
 /* the launch shape of an fp8-weight GEMM (w_dtype = HPA_FP8): waves by K alone
  * (8 from K = 2048, else 4), row blocks and column tiles as the bf16 table */
 void hpa_fused_pick_fp8(int M, int N, int K, int* out3);
+/* an fp4-weight GEMM (w_dtype = HPA_FP4) at variant 0: out4 = {variant (1
+ * looped, 5 A-resident), waves, row_blocks, col_tiles (looped) or rounds
+ * (A-resident)}.  The table follows profiles/r20/w_fp4.txt: the A-resident form
+ * is a default only where it beat the looped form by more than the larger of
+ * the two spreads */
+void hpa_fused_pick_fp4(int M, int N, int K, int* out4);
 /* bf16 weights, A-resident kernel (variant 5: the workgroup's rows of A
  * LayerNorm'ed and rounded into LDS once, waves walking waves*rounds column
  * tiles over the whole K; col_tiles = rounds for this variant):

@@ -174,7 +174,12 @@ int  gpt2_decode_init_ex(GPT2* model, int B, int page_size, int max_ctx, int kv_
  * checkpoint; the bf16 mode's arithmetic on the dequantised weights
  * decode(code) * scale, which are exactly bf16 values.  The embedding gather
  * keeps reading the fp32 wte.  Five launches per layer for every layer-kernel
- * request: the persistent chains take fp32 and bf16 packs only) */
+ * request: the persistent chains take fp32 and bf16 packs only) or HPA_FP4
+ * (3: weight-only MXFP4 -- the four layer matrices as e2m1 codes, half a byte
+ * each, with one e8m0 power-of-two scale per 32 consecutive k of a row
+ * (hpa_pack_frag_fp4); wte is stored and multiplied exactly as on an HPA_FP8
+ * engine; otherwise as HPA_FP8: the bf16 mode's arithmetic on decode(code) *
+ * 2^t, five launches per layer).  kv_dtype 3 is refused: fp4 is a weight format */
 int  gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dtype, int w_dtype);
 /* one decode step for every sequence: tokens[b] (host) at position pos[b];
  * tokens == NULL feeds back the previous step's greedy ids (device-resident).
@@ -731,8 +736,15 @@ int    gpt2_decode_kv_scales(GPT2* model, float* k_scale, float* v_scale);
 /* fp8 weights (gpt2_decode_init_w with w_dtype = HPA_FP8): the power-of-two
  * scale of every output channel (hip_paged_attn.h, hpa_pack_frag_fp8), into
  * out [L * 9C + V]: per layer qkvw [3C], attprojw [C], fcw [4C], fcprojw [C],
- * then wte [V].  Nonzero on an engine with fp32 / bf16 weights. */
+ * then wte [V].  On an fp4-weight engine the layer entries are 1.0 (their scales
+ * are per group, below) and wte's are its fp8 scales.  Nonzero on an engine with
+ * fp32 / bf16 weights. */
 int    gpt2_decode_weight_scales(GPT2* model, float* out);
+/* fp4 weights (w_dtype = HPA_FP4): the e8m0 group-scale bytes of the layer
+ * matrices as the engine holds them, n = L * 12 C^2 / 32 bytes: per layer qkvw,
+ * attprojw, fcw, fcprojw, each in the unit order of hpa_pack_frag_fp4
+ * ([row block][64-deep step][16 rows][2]).  Nonzero on any other engine or n. */
+int    gpt2_decode_weight_group_scales(GPT2* model, unsigned char* out, size_t n);
 /* K/V of positions [0, n) of sequence b at layer l, token-major [n][C] host
  * arrays (the reference page layout, block_manager.c:145-146); bf16 / fp8
  * pools: the values the stored codes stand for (fp8: decode(code) * scale) */

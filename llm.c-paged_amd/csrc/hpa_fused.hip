@@ -873,7 +873,34 @@ static int gemm_fused_launch(const HpaFusedGemm* g, FG& p) {
         if (ntw == 2 && mt == 1) ntw = 1;
         return launch_f8w(p, g->w_scale, g->epilogue, nw, mt, ntw);
     }
-    HPA_REQUIRE(g->w_dtype == HPA_F32, "gemm_fused: w_dtype must be HPA_F32, HPA_BF16 or HPA_FP8");
+    if (g->w_dtype == HPA_FP4) {  // MXFP4 weights: hpa_gemm_fp4w.hip
+        HPA_REQUIRE(g->epilogue == HPA_FEPI_QKV || g->epilogue == HPA_FEPI_RESID || g->epilogue == HPA_FEPI_GELU,
+                    "gemm_fused fp4 weights: epilogue QKV, RESID or GELU (the layer matrices); LOGITS and SCORE "
+                    "multiply wte, which is fp8 on an fp4 engine");
+        HPA_REQUIRE(g->variant == 0 || g->variant == 1 || g->variant == 5,
+                    "gemm_fused fp4 weights: variant 0, 1 (looped) or 5 (A-resident); not an fp32-only variant "
+                    "(2, 3, 4, 6)");
+        HPA_REQUIRE(!g->ln_fold_c1, "gemm_fused fp4 weights: ln_fold_c1 must be NULL (LN on the operand path)");
+        HPA_REQUIRE(g->w_gscale, "gemm_fused fp4 weights: w_gscale is NULL");
+        HPA_REQUIRE(g->K % 64 == 0, "gemm_fused fp4 weights: K % 64 != 0");
+        int pk[4];
+        hpa_fused_pick_fp4(g->M, g->N, g->K, pk);
+        const int variant = g->variant ? g->variant : pk[0];
+        nw = g->waves ? g->waves : pk[1];
+        if (variant == 5) {
+            mt = g->row_blocks ? g->row_blocks : pk[0] == 5 ? pk[2] : g->K <= 768 ? 4 : g->K <= 1600 ? 2 : 1;
+            HPA_REQUIRE(mt * g->K <= 3200 && g->K <= 3200,
+                        "gemm_fused fp4 A-resident: row_blocks * K <= 3200 (4: K <= 768, 2: 1600, 1: 3200)");
+            while (mt > 1 && (p.Mp / 16) % mt) mt >>= 1;  // row blocks of this M
+            return launch_f4w_ares(p, g->w_gscale, g->epilogue, nw, mt, g->variant == 5 ? g->col_tiles : 0);
+        }
+        mt = g->row_blocks ? g->row_blocks : pk[2];
+        ntw = g->col_tiles ? g->col_tiles : pk[3];
+        while (mt > 1 && (p.Mp / 16) % mt) mt >>= 1;  // row blocks of this M
+        if (ntw == 2 && mt == 1) ntw = 1;
+        return launch_f4w(p, g->w_gscale, g->epilogue, nw, mt, ntw);
+    }
+    HPA_REQUIRE(g->w_dtype == HPA_F32, "gemm_fused: w_dtype must be HPA_F32, HPA_BF16, HPA_FP8 or HPA_FP4");
     if (g->variant == 6) return launch_sk(p, g->epilogue);  // stream-K (hpa_gemm_sk.hip)
     HPA_REQUIRE(g->row_blocks == 0 || g->row_blocks == 1 || g->row_blocks == 2 || g->row_blocks == 4,
                 "gemm_fused: row_blocks must be 1, 2 or 4");

@@ -709,6 +709,11 @@ int launch_b16(const FG& p, int epi, int nw, int mt, int ntw);
 // fp8-weight GEMM launch (hpa_gemm_fp8w.hip): e4m3 codes in the fp8 frag
 // layout, w_scale [N] per output column; the shapes of launch_b16
 int launch_f8w(const FG& p, const float* w_scale, int epi, int nw, int mt, int ntw);
+// fp4-weight GEMM launches (hpa_gemm_fp4w.hip): e2m1 codes in the fp4 frag
+// layout, gscale their e8m0 group scales in unit order; QKV / RESID / GELU.
+// Looped: the shapes of launch_b16; A-resident: those of launch_b16_ares
+int launch_f4w(const FG& p, const unsigned char* gscale, int epi, int nw, int mt, int ntw);
+int launch_f4w_ares(const FG& p, const unsigned char* gscale, int epi, int nw, int mt, int rounds);
 // A-resident bf16 variant (variant 5): waves 4/8, row_blocks (mt) 1/2/4 with
 // mt*K <= 3200; each workgroup takes waves*rounds column tiles
 int launch_b16_ares(const FG& p, int epi, int nw, int mt, int rounds);

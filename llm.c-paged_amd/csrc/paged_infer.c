@@ -652,10 +652,14 @@ struct GPT2Decode {
     int* ring_cnt;
     size_t ring_cnt_n;
     float* d_wpack;   /* packed qkvw, attprojw, fcw, fcprojw of every layer, then wte */
-    int w_dtype;      /* HPA_F32, HPA_BF16 (hpa_pack_frag_bf16) or HPA_FP8 (hpa_pack_frag_fp8): the
-                         packs' storage; offsets in elements of it */
+    int w_dtype;      /* HPA_F32, HPA_BF16 (hpa_pack_frag_bf16), HPA_FP8 (hpa_pack_frag_fp8) or HPA_FP4
+                         (hpa_pack_frag_fp4: the layer packs at half a byte per element, the wte pack
+                         fp8 behind them): the packs' storage; offsets in elements of it */
     float* d_wscale;  /* fp8 weights: the scale of every output channel -- per layer qkv [3C],
-                         attproj [C], fc [4C], fcproj [C], then wte [V padded to 16]; else NULL */
+                         attproj [C], fc [4C], fcproj [C], then wte [V padded to 16]; fp4 weights: wte's
+                         alone; else NULL */
+    unsigned char* d_wgscale; /* fp4 weights: the layer packs' e8m0 group scales, one byte per 32
+                         elements at the packs' element offsets / 32; else NULL */
     size_t wpack_off[5]; /* per-layer offsets (0..3) and wte offset (4) */
     size_t wpack_layer;  /* elements of one layer's four packs */
     float* d_fold;    /* LN folded into qkvw / fcw (hpa_ln_fold_pack): per layer c1, c2 of
@@ -966,6 +970,7 @@ static void dec_free(GPT2Decode* d) {
     hpa_free(d->ring_slab); hpa_free(d->ring_cnt);
     hpa_free(d->d_wpack);
     hpa_free(d->d_wscale);
+    hpa_free(d->d_wgscale);
     hpa_free(d->d_fold);
     hpa_free(d->d_attn_ws);
     hpa_free(d->d_sh); hpa_free(d->d_sh_ws);
@@ -996,18 +1001,25 @@ void gpt2_decode_free(GPT2* model) {
     }
 }
 
-/* bytes per packed weight element */
-static size_t wpack_elem_bytes(const GPT2Decode* d) {
-    return d->w_dtype == HPA_FP8 ? 1 : d->w_dtype == HPA_BF16 ? 2 : 4;
+/* half-bytes per packed element of the layer matrices */
+static size_t wpack_elem_nibbles(const GPT2Decode* d) {
+    return d->w_dtype == HPA_FP4 ? 1 : d->w_dtype == HPA_FP8 ? 2 : d->w_dtype == HPA_BF16 ? 4 : 8;
 }
 
-/* packed weights at element offset off (fp32, bf16 or fp8 pack) */
+/* the dtype of the wte pack: an fp4 engine keeps wte fp8 (only the layer matrices go to fp4) */
+static int wte_dtype(const GPT2Decode* d) { return d->w_dtype == HPA_FP4 ? HPA_FP8 : d->w_dtype; }
+
+/* packed layer weights at element offset off (fp32, bf16, fp8 or fp4 pack; every offset is even) */
 static const float* wpack_at(const GPT2Decode* d, size_t off) {
-    return (const float*)((const char*)d->d_wpack + off * wpack_elem_bytes(d));
+    return (const float*)((const char*)d->d_wpack + off * wpack_elem_nibbles(d) / 2);
 }
 
-/* fp8 weights: the scales of wte's rows (else NULL) */
+/* the wte pack: behind the layer packs, in wte_dtype's storage */
+static const float* wte_pack(const GPT2Decode* d) { return wpack_at(d, d->wpack_off[4]); }
+
+/* fp8 and fp4 weights: the scales of wte's rows (else NULL) */
 static const float* wte_scale(const GPT2Decode* d, const GPT2Config* c) {
+    if (d->w_dtype == HPA_FP4) return d->d_wscale;
     return d->d_wscale ? d->d_wscale + (size_t)c->num_layers * 9 * c->channels : NULL;
 }
 
@@ -1020,6 +1032,7 @@ static const float* wte_scale(const GPT2Decode* d, const GPT2Config* c) {
 typedef struct {
     const float *w_qkv, *w_ap, *w_fc, *w_fp;
     const float *s_qkv, *s_ap, *s_fc, *s_fp; /* fp8 weights: their per-channel scales, else NULL */
+    const unsigned char *g_qkv, *g_ap, *g_fc, *g_fp; /* fp4 weights: their group scales, else NULL */
     const float *qkv_c1, *qkv_c2, *fc_c1, *fc_c2;
     const float *b_qkv, *b_ap, *b_fc, *b_fp; /* checkpoint biases */
     const float *ln1_w, *ln1_b, *ln2_w, *ln2_b;
@@ -1034,7 +1047,12 @@ static DecLayerOps dec_layer_ops(const GPT2* model, const GPT2Decode* d, int l) 
     o.w_ap = wpack_at(d, d->wpack_layer * l + d->wpack_off[1]);
     o.w_fc = wpack_at(d, d->wpack_layer * l + d->wpack_off[2]);
     o.w_fp = wpack_at(d, d->wpack_layer * l + d->wpack_off[3]);
-    const float* sl = d->d_wscale ? d->d_wscale + 9 * lc : NULL;
+    const float* sl = d->w_dtype == HPA_FP8 && d->d_wscale ? d->d_wscale + 9 * lc : NULL;
+    const unsigned char* gl = d->d_wgscale ? d->d_wgscale + d->wpack_layer * l / 32 : NULL;
+    o.g_qkv = gl;
+    o.g_ap = gl ? gl + d->wpack_off[1] / 32 : NULL;
+    o.g_fc = gl ? gl + d->wpack_off[2] / 32 : NULL;
+    o.g_fp = gl ? gl + d->wpack_off[3] / 32 : NULL;
     o.s_qkv = sl;
     o.s_ap = sl ? sl + 3 * C : NULL;
     o.s_fc = sl ? sl + 4 * C : NULL;
@@ -1069,9 +1087,28 @@ static int dec_init_weights(GPT2* model, GPT2Decode* d) {
     d->wpack_off[2] = e_qkv + e_ap;
     d->wpack_off[3] = e_qkv + e_ap + e_fc;
     d->wpack_off[4] = e_layer * L; /* wte */
-    const size_t total = d->wpack_off[4] + hpa_frag_elems(V, C);
-    d->d_wpack = (float*)hpa_malloc(total * wpack_elem_bytes(d));
+    const size_t wte_bytes = hpa_frag_elems(V, C) * (wte_dtype(d) == HPA_FP8 ? 1 : wte_dtype(d) == HPA_BF16 ? 2 : 4);
+    d->d_wpack = (float*)hpa_malloc(d->wpack_off[4] * wpack_elem_nibbles(d) / 2 + wte_bytes);
     if (!d->d_wpack) return 1;
+    if (d->w_dtype == HPA_FP4) { /* fp4 weights: the layer packs at the same element offsets, half a
+                                  * byte each, their group scales at offset / 32; wte as on an fp8
+                                  * engine; LN on the operand path */
+        d->d_wscale = (float*)hpa_malloc((size_t)(V + 15) / 16 * 16 * sizeof(float));
+        d->d_wgscale = (unsigned char*)hpa_malloc(d->wpack_off[4] / 32);
+        if (!d->d_wscale || !d->d_wgscale) return 1;
+        for (int l = 0; l < L; l++) {
+            const DecLayerOps o = dec_layer_ops(model, d, l);
+            const size_t lc = (size_t)l * C;
+            if (hpa_pack_frag_fp4(w->qkvw + lc * 3 * C, 3 * C, C, C, (unsigned char*)o.w_qkv, (unsigned char*)o.g_qkv) ||
+                hpa_pack_frag_fp4(w->attprojw + lc * C, C, C, C, (unsigned char*)o.w_ap, (unsigned char*)o.g_ap) ||
+                hpa_pack_frag_fp4(w->fcw + lc * 4 * C, 4 * C, C, C, (unsigned char*)o.w_fc, (unsigned char*)o.g_fc) ||
+                hpa_pack_frag_fp4(w->fcprojw + lc * 4 * C, C, 4 * C, 4 * C, (unsigned char*)o.w_fp, (unsigned char*)o.g_fp))
+                return 1;
+        }
+        if (hpa_pack_frag_fp8(w->wte, V, C, C, (unsigned char*)wte_pack(d), (float*)wte_scale(d, &c))) return 1;
+        for (int i = 0; i < 5; i++) d->fwaves[i] = d->frb[i] = d->fct[i] = 0; /* hpa_fused_pick_fp4 / _fp8 */
+        return 0;
+    }
     if (d->w_dtype == HPA_FP8) { /* fp8 weights: same element offsets, 1 byte each, and one scale per
                                   * output channel; LN on the operand path; the embedding gather
                                   * keeps reading the fp32 checkpoint wte */
@@ -1225,7 +1262,7 @@ static DecPlan dec_plan(int want, int B, int pick_B, int C, int num_heads, int m
     const DecPlan five = {0, 0, 1, 0, 0};
     /* fp8 weights (w_bf16 = 2) live in the GEMM launches only: five launches
      * per layer for every request; the chains know fp32 and bf16 packs */
-    if (w_bf16 == 2) return five;
+    if (w_bf16 >= 2) return five; /* HPA_FP8, HPA_FP4 */
     /* an fp8 pool's K/V are appended by chain form 6 (with the step's first
      * launch) and by the GEMM launches' shared epilogue only: auto and form 5
      * give chain form 6 where it applies, every other pick -- the bf16 chain
@@ -1482,11 +1519,11 @@ int gpt2_decode_init_ex(GPT2* model, int B, int page_size, int max_ctx, int kv_d
 int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dtype, int w_dtype) {
     ensure_device();
     if (kv_dtype != HPA_F32 && kv_dtype != HPA_BF16 && kv_dtype != HPA_FP8) {
-        fprintf(stderr, "[paged_infer] kv dtype must be HPA_F32, HPA_BF16 or HPA_FP8\n");
+        fprintf(stderr, "[paged_infer] kv dtype must be HPA_F32, HPA_BF16 or HPA_FP8 (HPA_FP4 is a weight format)\n");
         return 1;
     }
-    if (w_dtype != HPA_F32 && w_dtype != HPA_BF16 && w_dtype != HPA_FP8) {
-        fprintf(stderr, "[paged_infer] weight dtype must be HPA_F32, HPA_BF16 or HPA_FP8\n");
+    if (w_dtype != HPA_F32 && w_dtype != HPA_BF16 && w_dtype != HPA_FP8 && w_dtype != HPA_FP4) {
+        fprintf(stderr, "[paged_infer] weight dtype must be HPA_F32, HPA_BF16, HPA_FP8 or HPA_FP4\n");
         return 1;
     }
     if (!model->params_memory) { fprintf(stderr, "[paged_infer] model not built\n"); return 1; }
@@ -1816,31 +1853,31 @@ static void dec_gemm_desc(GPT2* model, int l, int which, HpaFusedGemm* g) {
     switch (which) {
         case G_QKV: /* LN1 (stats: embedding's 1 tile at layer 0, fcproj's C/16 after) */
             g->x = d->res; g->K = C; g->ln_stats = d->st1; g->ln_ntiles = l == 0 ? 1 : ct;
-            g->ln_w = o.ln1_w; g->ln_b = o.ln1_b; g->w = o.w_qkv; g->w_scale = o.s_qkv;
+            g->ln_w = o.ln1_w; g->ln_b = o.ln1_b; g->w = o.w_qkv; g->w_scale = o.s_qkv; g->w_gscale = o.g_qkv;
             g->N = 3 * C; g->bias = o.b_qkv; g->out = d->d_q;
             if (d->d_fold) { g->ln_fold_c1 = o.qkv_c1; g->bias = o.qkv_c2; }
             break;
         case G_ATTPROJ: /* res2 = res + att . Wap^T + b (LN2 statistics only when fc needs them) */
-            g->x = d->att; g->K = C; g->w = o.w_ap; g->w_scale = o.s_ap; g->N = C;
+            g->x = d->att; g->K = C; g->w = o.w_ap; g->w_scale = o.s_ap; g->w_gscale = o.g_ap; g->N = C;
             g->bias = o.b_ap; g->out = d->res2; g->res_in = d->res; g->stats_out = d->d_fold ? NULL : d->st2;
             break;
         case G_FC: /* gelu(LN2(res2) . Wfc^T + b) */
             g->x = d->res2; g->K = C; g->ln_stats = d->st2; g->ln_ntiles = ct; g->ln_w = o.ln2_w;
-            g->ln_b = o.ln2_b; g->w = o.w_fc; g->w_scale = o.s_fc; g->N = 4 * C;
+            g->ln_b = o.ln2_b; g->w = o.w_fc; g->w_scale = o.s_fc; g->w_gscale = o.g_fc; g->N = 4 * C;
             g->bias = o.b_fc; g->out = d->fch;
             if (d->d_fold) { g->ln_fold_c1 = o.fc_c1; g->bias = o.fc_c2; }
             break;
         case G_FCPROJ: /* res = res2 + fch . Wfp^T + b, next-LN statistics */
-            g->x = d->fch; g->K = 4 * C; g->w = o.w_fp; g->w_scale = o.s_fp; g->N = C;
+            g->x = d->fch; g->K = 4 * C; g->w = o.w_fp; g->w_scale = o.s_fp; g->w_gscale = o.g_fp; g->N = C;
             g->bias = o.b_fp; g->out = d->res; g->res_in = d->res2;
             g->stats_out = d->d_fold && l + 1 < c.num_layers ? NULL : d->st1; /* LNf of logits: last layer */
             break;
         default: /* logits = LNf(res) . wte^T, argmax partials */
             g->x = d->res; g->K = C; g->ln_stats = d->st1; g->ln_ntiles = ct;
-            g->ln_w = w->lnfw; g->ln_b = w->lnfb; g->w = wpack_at(d, d->wpack_off[4]); g->N = V;
-            g->w_scale = wte_scale(d, &c);
+            g->ln_w = w->lnfw; g->ln_b = w->lnfb; g->w = wte_pack(d); g->N = V;
+            g->w_scale = wte_scale(d, &c); g->w_dtype = wte_dtype(d);
             g->out = d->d_logits; g->part_out = d->part; g->layer = 0;
-            if (d->w_dtype == HPA_FP8) break; /* the fp8-weight kernel, shapes by hpa_fused_pick_fp8 */
+            if (g->w_dtype == HPA_FP8) break; /* the fp8-weight kernel, shapes by hpa_fused_pick_fp8 */
             g->variant = 4; /* activation-resident kernel where the shape allows (hpa_logits.hip), */
             g->sk_slab = d->sk_slab; g->sk_count = d->sk_cnt; /* else stream-K with this workspace */
             if (d->w_dtype == HPA_F32 && hpa_logits_kernel(d->B, V, C) == 4) { /* its form by the GLOBAL batch: a */
@@ -2796,23 +2833,23 @@ static int prefill_gemm(GPT2* model, int l, int which, int R) {
         case G_QKV:
             g.epilogue = HPA_FEPI_QKV; g.x = d->pf_res; g.K = C; g.ln_stats = d->pf_st1;
             g.ln_ntiles = l == 0 ? 1 : ct; g.ln_w = o.ln1_w; g.ln_b = o.ln1_b;
-            g.w = o.w_qkv; g.w_scale = o.s_qkv; g.N = 3 * C; g.bias = o.b_qkv; g.out = d->pf_q;
+            g.w = o.w_qkv; g.w_scale = o.s_qkv; g.w_gscale = o.g_qkv; g.N = 3 * C; g.bias = o.b_qkv; g.out = d->pf_q;
             if (d->pf_slot) g.pos = d->pf_slot; /* a tree pass appends node i at start + i, whatever its depth */
             if (d->d_fold) { g.ln_fold_c1 = o.qkv_c1; g.bias = o.qkv_c2; }
             break;
         case G_ATTPROJ:
-            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_att; g.K = C; g.w = o.w_ap; g.w_scale = o.s_ap;
+            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_att; g.K = C; g.w = o.w_ap; g.w_scale = o.s_ap; g.w_gscale = o.g_ap;
             g.N = C; g.bias = o.b_ap; g.out = d->pf_res2; g.res_in = d->pf_res;
             g.stats_out = d->d_fold ? NULL : d->pf_st2;
             break;
         case G_FC:
             g.epilogue = HPA_FEPI_GELU; g.x = d->pf_res2; g.K = C; g.ln_stats = d->pf_st2; g.ln_ntiles = ct;
-            g.ln_w = o.ln2_w; g.ln_b = o.ln2_b; g.w = o.w_fc; g.w_scale = o.s_fc;
+            g.ln_w = o.ln2_w; g.ln_b = o.ln2_b; g.w = o.w_fc; g.w_scale = o.s_fc; g.w_gscale = o.g_fc;
             g.N = 4 * C; g.bias = o.b_fc; g.out = d->pf_fch;
             if (d->d_fold) { g.ln_fold_c1 = o.fc_c1; g.bias = o.fc_c2; }
             break;
         default: /* G_FCPROJ */
-            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_fch; g.K = 4 * C; g.w = o.w_fp; g.w_scale = o.s_fp;
+            g.epilogue = HPA_FEPI_RESID; g.x = d->pf_fch; g.K = 4 * C; g.w = o.w_fp; g.w_scale = o.s_fp; g.w_gscale = o.g_fp;
             g.N = C; g.bias = o.b_fp; g.out = d->pf_res; g.res_in = d->pf_res2;
             g.stats_out = d->d_fold && l + 1 < c.num_layers ? NULL : d->pf_st1;
             break;
@@ -2834,7 +2871,7 @@ static int prefill_all_logits(GPT2* model, int R, float* rows_out, const int* ou
     HpaFusedGemm g;
     memset(&g, 0, sizeof(g));
     g.M = R;
-    g.w_dtype = d->w_dtype;
+    g.w_dtype = wte_dtype(d);
     g.epilogue = HPA_FEPI_LOGITS;
     g.x = d->pf_res;
     g.K = C;
@@ -2842,7 +2879,7 @@ static int prefill_all_logits(GPT2* model, int R, float* rows_out, const int* ou
     g.ln_ntiles = C / 16;
     g.ln_w = model->params.lnfw;
     g.ln_b = model->params.lnfb;
-    g.w = wpack_at(d, d->wpack_off[4]);
+    g.w = wte_pack(d);
     g.w_scale = wte_scale(d, &model->config);
     g.N = V;
     g.out = rows_out;
@@ -2924,7 +2961,7 @@ static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
         HpaFusedGemm g;
         memset(&g, 0, sizeof(g));
         g.M = n;
-        g.w_dtype = d->w_dtype;
+        g.w_dtype = wte_dtype(d);
         g.epilogue = HPA_FEPI_SCORE;
         g.x = d->sc_x;
         g.K = C;
@@ -2932,7 +2969,7 @@ static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
         g.ln_ntiles = C / 16;
         g.ln_w = model->params.lnfw;
         g.ln_b = model->params.lnfb;
-        g.w = wpack_at(d, d->wpack_off[4]);
+        g.w = wte_pack(d);
         g.w_scale = wte_scale(d, &model->config);
         g.N = V;
         g.score_target = d->sc_tgt;
@@ -3003,7 +3040,7 @@ static int dec_score_top_rows(GPT2* model, int R, const DecScore* sc) {
         HpaFusedGemm g;
         memset(&g, 0, sizeof(g));
         g.M = n;
-        g.w_dtype = d->w_dtype;
+        g.w_dtype = wte_dtype(d);
         g.epilogue = HPA_FEPI_LOGITS;
         g.x = d->sc_x;
         g.K = C;
@@ -3011,7 +3048,7 @@ static int dec_score_top_rows(GPT2* model, int R, const DecScore* sc) {
         g.ln_ntiles = C / 16;
         g.ln_w = model->params.lnfw;
         g.ln_b = model->params.lnfb;
-        g.w = wpack_at(d, d->wpack_off[4]);
+        g.w = wte_pack(d);
         g.w_scale = wte_scale(d, &model->config);
         g.N = V;
         g.out = d->st_logits;
@@ -3273,7 +3310,7 @@ static int dec_spec_dense(GPT2* model, int R, int ND, const int* hrows, const in
         HpaFusedGemm g;
         memset(&g, 0, sizeof(g));
         g.M = n;
-        g.w_dtype = d->w_dtype;
+        g.w_dtype = wte_dtype(d);
         g.epilogue = HPA_FEPI_LOGITS;
         g.x = d->sc_x;
         g.K = C;
@@ -3281,7 +3318,7 @@ static int dec_spec_dense(GPT2* model, int R, int ND, const int* hrows, const in
         g.ln_ntiles = C / 16;
         g.ln_w = model->params.lnfw;
         g.ln_b = model->params.lnfb;
-        g.w = wpack_at(d, d->wpack_off[4]);
+        g.w = wte_pack(d);
         g.w_scale = wte_scale(d, &model->config);
         g.N = V;
         g.out = d->st_logits;
@@ -4040,12 +4077,26 @@ int gpt2_decode_set_kv_scales(GPT2* model, const float* k_scale, const float* v_
 int gpt2_decode_weight_scales(GPT2* model, float* out) {
     GPT2Decode* d = model ? model->decode : NULL;
     if (!d || !d->d_wscale || !out) {
-        fprintf(stderr, "[paged_infer] gpt2_decode_weight_scales: needs an fp8-weight engine (gpt2_decode_init_w)\n");
+        fprintf(stderr, "[paged_infer] gpt2_decode_weight_scales: needs an fp8- or fp4-weight engine (gpt2_decode_init_w)\n");
         return 1;
     }
     const GPT2Config c = model->config;
-    const size_t n = (size_t)c.num_layers * 9 * c.channels + c.vocab_size;
+    const size_t nl = (size_t)c.num_layers * 9 * c.channels, n = nl + c.vocab_size;
+    if (d->w_dtype == HPA_FP4) { /* the layer matrices carry group scales (gpt2_decode_weight_group_scales) */
+        for (size_t i = 0; i < nl; i++) out[i] = 1.0f;
+        return hpa_synchronize() || hpa_memcpy(out + nl, d->d_wscale, (size_t)c.vocab_size * sizeof(float));
+    }
     return hpa_synchronize() || hpa_memcpy(out, d->d_wscale, n * sizeof(float));
+}
+
+int gpt2_decode_weight_group_scales(GPT2* model, unsigned char* out, size_t n) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    const size_t have = d && d->d_wgscale ? d->wpack_off[4] / 32 : 0;
+    if (!have || !out || n != have) {
+        fprintf(stderr, "[paged_infer] gpt2_decode_weight_group_scales: needs an fp4-weight engine and n = L * 12 C^2 / 32\n");
+        return 1;
+    }
+    return hpa_synchronize() || hpa_memcpy(out, d->d_wgscale, n);
 }
 
 int gpt2_decode_kv_scales(GPT2* model, float* k_scale, float* v_scale) {
@@ -4251,9 +4302,11 @@ double gpt2_decode_step_bytes(GPT2* model, double* attn_bytes) {
     const GPT2Config c = model->config;
     const double C = c.channels, L = c.num_layers, V = c.vocab_size, w = 4.0;
     const double wkv = (double)d->pool.elem_bytes; /* fp32, bf16 or fp8 KV storage */
-    const double wm = (double)wpack_elem_bytes(d); /* GEMM weight matrices: fp32, bf16 or fp8 */
-    const double wsc = d->w_dtype == HPA_FP8 ? (L * 9 * C + V) * w : 0.0; /* fp8: one scale per output channel */
-    const double weights = (L * 12 * C * C + V * C) * wm + wsc + (L * 13 * C + 2 * C) * w;
+    const double wm = (double)wpack_elem_nibbles(d) / 2; /* layer matrices: fp32, bf16, fp8 or fp4 */
+    const double wt = wte_dtype(d) == HPA_FP8 ? 1.0 : wte_dtype(d) == HPA_BF16 ? 2.0 : 4.0; /* wte (fp4 engine: fp8) */
+    /* fp8: one scale per output channel; fp4: one byte per 32 layer weights, and wte's fp8 scales */
+    const double wsc = d->w_dtype == HPA_FP8 ? (L * 9 * C + V) * w : d->w_dtype == HPA_FP4 ? L * 12 * C * C / 32 + V * w : 0.0;
+    const double weights = L * 12 * C * C * wm + V * C * wt + wsc + (L * 13 * C + 2 * C) * w;
     double kv = 0.0;
     for (int b = 0; b < d->B; b++) kv += 2.0 * L * (d->h_pos[b] + 1) * C * wkv;
     const double append = 2.0 * L * d->B * C * wkv;

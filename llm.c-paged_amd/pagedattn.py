@@ -60,7 +60,7 @@ class HpaFusedGemm(ctypes.Structure):
                 ("row_blocks", ctypes.c_int), ("variant", ctypes.c_int), ("col_tiles", ctypes.c_int),
                 ("row_seq", _V), ("ln_fold_c1", _V), ("sk_slab", _V), ("sk_count", _V),
                 ("w_dtype", ctypes.c_int), ("pick_next", _V), ("pick_tokens", _V), ("pick_pos", _V),
-                ("pick_count", _V), ("score_target", _V), ("score_part", _V), ("w_scale", _V)]
+                ("pick_count", _V), ("score_target", _V), ("score_part", _V), ("w_scale", _V), ("w_gscale", _V)]
 
 
 class HpaChainB16Args(ctypes.Structure):
@@ -138,6 +138,31 @@ def from_frag_fp8(codes_u8, rows, K):
     """fp8 frag layout (hpa_pack_frag_fp8) -> [rows][K] e4m3fn codes"""
     m, k = np.meshgrid(np.arange(rows), np.arange(K), indexing="ij")
     return np.asarray(codes_u8, np.uint8)[frag_fp8_index(m, k, K)]
+
+
+def frag_fp4_index(m, k, K):
+    """(byte, shift) of code (m, k) of a [rows][K] matrix in the fp4 frag layout (hip_paged_attn.h;
+    vectorised over m, k): the 8 bytes of lane m % 16 + 16 * ((k % 16) / 4) of (row block m / 16,
+    64-deep step k / 64), dword (k % 64) / 32 of them, nibble k % 4 + 4 * ((k % 32) / 16)"""
+    m = np.asarray(m)
+    k = np.asarray(k)
+    nib = (k & 3) + 4 * ((k >> 4) & 1)
+    byte = ((((m >> 4) * (K >> 6) + (k >> 6)) * 64 + ((m & 15) + 16 * ((k >> 2) & 3))) << 3) + \
+        4 * ((k >> 5) & 1) + (nib >> 1)
+    return byte, 4 * (nib & 1)
+
+
+def from_frag_fp4(codes_u8, rows, K):
+    """fp4 frag layout (hpa_pack_frag_fp4) -> [rows][K] e2m1 codes, one per element"""
+    m, k = np.meshgrid(np.arange(rows), np.arange(K), indexing="ij")
+    byte, shift = frag_fp4_index(m, k, K)
+    return (np.asarray(codes_u8, np.uint8)[byte] >> shift) & 15
+
+
+def from_frag_mx_scales(scales_u8, rows, K):
+    """the group scales' unit order ([row block][64-deep step][16 rows][2]) -> [rows][K / 32] bytes"""
+    m, g = np.meshgrid(np.arange(rows), np.arange(K // 32), indexing="ij")
+    return np.asarray(scales_u8, np.uint8)[(((m >> 4) * (K >> 6) + (g >> 1)) * 16 + (m & 15)) * 2 + (g & 1)]
 
 
 GPT2_124M = dict(maxT=1024, V=50257, L=12, NH=12, C=768)
@@ -311,6 +336,10 @@ def lib():
     _sig(L, "hpa_pack_frag_fp8", i, [v, i, i, i, v, v])
     _sig(L, "hpa_frag_fp8_bytes", ctypes.c_size_t, [i, i])
     _sig(L, "hpa_fused_pick_fp8", None, [i, i, i, _I])
+    _sig(L, "hpa_pack_frag_fp4", i, [v, i, i, i, v, v])
+    _sig(L, "hpa_frag_fp4_bytes", ctypes.c_size_t, [i, i])
+    _sig(L, "hpa_frag_mx_scale_bytes", ctypes.c_size_t, [i, i])
+    _sig(L, "hpa_fused_pick_fp4", None, [i, i, i, _I])
     _sig(L, "gpt2_decode_prefill", i, [v, _I, i, _I])
     _sig(L, "gpt2_decode_prefill_ragged", i, [v, _I, _I, _I])
     _sig(L, "gpt2_decode_score", i, [v, _I, _I, _I, _F, _I, _I])
@@ -415,6 +444,7 @@ def lib():
     _sig(L, "gpt2_decode_set_kv_scales", i, [v, _F, _F])
     _sig(L, "gpt2_decode_kv_scales", i, [v, _F, _F])
     _sig(L, "gpt2_decode_weight_scales", i, [v, _F])
+    _sig(L, "gpt2_decode_weight_group_scales", i, [v, v, ctypes.c_size_t])
     _sig(L, "gpt2_decode_batch", i, [v])
     _sig(L, "gpt2_decode_shard", i, [v, _I, i])
     _sig(L, "gpt2_decode_gather", i, [v, i])
@@ -730,7 +760,33 @@ def quantize_fp8_rows(W):
     return codes, scales, (from_fp8_bits(codes) * scales[:, None]).astype(np.float32)
 
 
-HPA_F32, HPA_BF16, HPA_FP8 = 0, 1, 2
+E2M1 = np.array([0, 0.5, 1, 1.5, 2, 3, 4, 6], np.float32)  # magnitude of code bits 0..2; bit 3 = sign
+
+
+def quantize_mxfp4_rows(W):
+    """weight-only MXFP4 quantisation of W [N][K] (hpa_pack_frag_fp4's rule, restated): per row
+    and group of 32 consecutive k, t = the smallest integer with absmax / 2^t <= 6 (absmax = m 2^e
+    with m in [0.5, 1): e - 3 for m <= 0.75, else e - 2), clamped to [-64, 64], 0 for an all-zero
+    group; code = e2m1_rne(clamp(w 2^-t, -6, 6)), ties to the even mantissa, bit 3 = (w < 0).
+    Returns (codes uint8 [N][K], one per element; e8m0 bytes t + 127 [N][K / 32];
+    W' = decode(codes) * 2^t, exactly bf16 values)."""
+    W = np.ascontiguousarray(W, np.float32)
+    N, K = W.shape
+    G = W.reshape(N, K // 32, 32)
+    m, e = np.frexp(np.abs(G).max(axis=2))
+    t = np.clip(np.where(m <= 0.75, e - 3, e - 2), -64, 64)
+    t = np.where(m == 0, 0, t).astype(np.int32)
+    x = np.ldexp(np.abs(G), -t[:, :, None]).astype(np.float32)
+    # the boundary between codes c and c + 1; a tie goes to the code with mantissa bit 0
+    mag = np.zeros(x.shape, np.uint8)
+    for c, (mid, up) in enumerate(zip((0.25, 0.75, 1.25, 1.75, 2.5, 3.5, 5.0), (False, True) * 4)):
+        mag[(x >= mid) if up else (x > mid)] = c + 1
+    codes = (mag | ((G < 0).astype(np.uint8) << 3)).reshape(N, K)
+    deq = np.ldexp(np.where(G < 0, -E2M1[mag], E2M1[mag]), t[:, :, None]).astype(np.float32).reshape(N, K)
+    return codes, (t + 127).astype(np.uint8), deq
+
+
+HPA_F32, HPA_BF16, HPA_FP8, HPA_FP4 = 0, 1, 2, 3
 
 
 class Pool:
@@ -1230,6 +1286,21 @@ class Model:
         attprojw [C], fcw [4C], fcprojw [C], then wte [V] (gpt2_decode_weight_scales)"""
         out = np.zeros(self.cfg.num_layers * 9 * self.cfg.channels + self.cfg.vocab_size, np.float32)
         check(lib().gpt2_decode_weight_scales(self.h, out.ctypes.data_as(_F)), "weight_scales")
+        return out
+
+    def weight_group_scales(self):
+        """fp4 weights: the e8m0 group-scale bytes in natural order, per layer a list of qkvw
+        [3C][C/32], attprojw [C][C/32], fcw [4C][C/32], fcprojw [C][4C/32]
+        (gpt2_decode_weight_group_scales, un-permuted from the engine's unit order)"""
+        C, L = self.cfg.channels, self.cfg.num_layers
+        raw = np.zeros(L * 12 * C * C // 32, np.uint8)
+        check(lib().gpt2_decode_weight_group_scales(self.h, raw.ctypes.data, raw.size), "weight_group_scales")
+        out, at = [], 0
+        for _ in range(L):
+            out.append([])
+            for rows, K in ((3 * C, C), (C, C), (4 * C, C), (C, 4 * C)):
+                out[-1].append(from_frag_mx_scales(raw[at:at + rows * K // 32], rows, K))
+                at += rows * K // 32
         return out
 
     def shard(self, rows_per_rank, root=0):
