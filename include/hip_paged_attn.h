@@ -135,7 +135,8 @@ typedef struct HpaKVPool {
     int    managed;
     float* scales;        /* fp8 pools: device [num_layers][2][num_heads][2] (scale, inv); else NULL */
 } HpaKVPool;
-enum { HPA_F32 = 0, HPA_BF16 = 1, HPA_FP8 = 2, HPA_FP4 = 3 }; /* HPA_FP4: weights only (hpa_pack_frag_fp4); no pool */
+enum { HPA_F32 = 0, HPA_BF16 = 1, HPA_FP8 = 2, HPA_FP4 = 3, HPA_FP4A8 = 4 }; /* HPA_FP4: weights only
+    (hpa_pack_frag_fp4); HPA_FP4A8: weights only, W4A8 on the scaled MFMA (hpa_pack_frag_mx4); no pool */
 int  hpa_pool_create(HpaKVPool* pool, int num_layers, int num_heads, int head_size, int page_size,
                      int num_pages, int dtype, int managed);
 void hpa_pool_destroy(HpaKVPool* pool);
@@ -339,6 +340,41 @@ int hpa_pack_frag_fp8(const float* W, int N, int K, int ld, unsigned char* dst_f
 size_t hpa_frag_fp4_bytes(int rows, int K);
 size_t hpa_frag_mx_scale_bytes(int rows, int K);
 int hpa_pack_frag_fp4(const float* W, int N, int K, int ld, unsigned char* dst_codes, unsigned char* dst_scales);
+/* W4A8 (w_dtype = HPA_FP4A8): the same MXFP4 codes and e8m0 bytes as above, laid
+ * out for v_mfma_scale_f32_16x16x128_f8f6f4, against activations quantised once
+ * per GEMM to MXFP8 (hpa_quant_mxfp8_rows).  K % 32 == 0; Kp = K padded to a
+ * multiple of 128 (code 0, scale byte 127), S = Kp / 128 steps, S4 = ceil(S / 4).
+ * mx4 weight layout (rows padded to 16): the unit of (16-row block, 128-deep step
+ * s) is 1024 B contiguous, 16 bytes per lane; lane l = (m % 16) + 16 * g holds
+ * the 32 consecutive k = 128 s + 32 g + {0..31} of its row, two codes a byte, the
+ * lower k in the low nibble: the instruction's B operand as loaded.  Code (m, k):
+ * nibble k % 2 of byte (k % 32) / 2 of lane m % 16 + 16 * ((k % 128) / 32) of unit
+ * (m / 16) * S + k / 128.  Scales: [row block][S4][64 lanes] dwords, byte i of
+ * dword d the lane's group at step 4 d + i (the instruction's byte select);
+ * byte (m, k) at (((m / 16) * S4 + k / 512) * 64 + m % 16 + 16 * ((k % 128) / 32)) * 4
+ * + (k / 128) % 4.  hpa_pack_frag_mx4: as hpa_pack_frag_fp4, dst_codes
+ * hpa_frag_mx4_bytes(N, K) bytes, 16-byte aligned; dst_scales
+ * hpa_frag_mx4_scale_bytes(N, K) bytes, 4-byte aligned.
+ * Activations: for each row and group of 32 consecutive k, t = the smallest
+ * integer with absmax / 2^t <= 448, from the fp32 fields of absmax (= m 2^e, m in
+ * [0.5, 1): e - 9 for m <= 0.875, else e - 8), clamped to [-64, 64], 0 for an
+ * all-zero group, stored as the byte t + 127; code = e4m3fn_rne(a 2^-t), OCP
+ * e4m3fn with subnormals, ties to even, clamped at 448 (reached only where t was
+ * clamped).  hpa_quant_mxfp8_rows (one pass, deterministic) reads x_frag [M][K]
+ * in the fp32 frag layout, applies the one-pass LayerNorm of the fused GEMMs
+ * when ln_stats is non-NULL (partials [ln_ntiles][Mp][2], ln_w, ln_b [K]) and
+ * writes ws (hpa_mxfp8_workspace_bytes(M, K) bytes, 16-byte aligned): codes
+ * [row block][S][2 halves][64 lanes][16 B], lane l = (m % 16) + 16 * c, half h
+ * the k = 128 s + 64 h + 16 c + {0..15}, one byte each (the instruction's fp8
+ * operand: registers 4h .. 4h + 3 of lane l); then, at byte Mp * Kp, the scale
+ * dwords in the weights' order (by k alone: lane (m % 16) + 16 * ((k % 128) / 32)).
+ * Rows >= M and k >= K: code 0, byte 127. */
+size_t hpa_frag_mx4_bytes(int rows, int K);
+size_t hpa_frag_mx4_scale_bytes(int rows, int K);
+int hpa_pack_frag_mx4(const float* W, int N, int K, int ld, unsigned char* dst_codes, unsigned char* dst_scales);
+size_t hpa_mxfp8_workspace_bytes(int M, int K);
+int hpa_quant_mxfp8_rows(const float* x_frag, int M, int K, const float* ln_stats, int ln_ntiles, const float* ln_w,
+                         const float* ln_b, void* ws);
 
 /* per-row LayerNorm statistics travel between kernels as partial sums
  * (sum x, sum x^2) over 16-column tiles: stats[tile][Mp][2]; a consumer sums
@@ -441,7 +477,16 @@ typedef struct {
                              fp8 on an fp4 engine).  Variant 0 (hpa_fused_pick_fp4), 1 (looped;
                              waves 4/8, the bf16 kernel's (row_blocks, col_tiles)) or 5
                              (A-resident; waves 4/8, row_blocks * K <= 3200, col_tiles =
-                             rounds, 0 = auto); ln_fold_c1 must be NULL. */
+                             rounds, 0 = auto); ln_fold_c1 must be NULL.
+                             HPA_FP4A8: w points at e2m1 codes in the mx4 layout
+                             (hpa_pack_frag_mx4), K % 32 == 0, w_gscale their scale dwords,
+                             a_ws the activation workspace.  The call launches the
+                             activation quantiser (with the LN) and then the scaled-MFMA
+                             GEMM on the current stream: the fp32 sum of the exact products
+                             of the MXFP8 activations and the MXFP4 weights.  Epilogues
+                             QKV, RESID, GELU; variant 0 (hpa_fused_pick_mx48) or 1; waves
+                             4/8, the bf16 kernel's (row_blocks, col_tiles); ln_fold_c1
+                             must be NULL. */
     /* LOGITS on the activation-resident kernel (variant 4, fp32) only: non-NULL
      * pick_next makes the launch's last workgroup to finish (an arrival ticket on
      * pick_count: one int, zero before the first launch, left zero) reduce the
@@ -468,7 +513,11 @@ typedef struct {
     const float* w_scale; /* w_dtype = HPA_FP8 only: device [N], the weight's scale per output
                              column (hpa_pack_frag_fp8 writes it); else not read */
     const unsigned char* w_gscale; /* w_dtype = HPA_FP4 only: device, the weight's e8m0 group
-                             scales in unit order (hpa_pack_frag_fp4 writes them); else not read */
+                             scales in unit order (hpa_pack_frag_fp4 writes them); HPA_FP4A8:
+                             the scale dwords of hpa_pack_frag_mx4; else not read */
+    void* a_ws;           /* w_dtype = HPA_FP4A8 only: device workspace of
+                             hpa_mxfp8_workspace_bytes(M, K) bytes, 16-byte aligned, overwritten
+                             by every call; else not read */
 } HpaFusedGemm;
 /* LayerNorm folding for hpa_gemm_fused (layernorm_forward :49-89 followed by
  * matmul_forward :92-114, restated): for W [N][K] row-major (device), writes
@@ -511,6 +560,10 @@ void hpa_fused_pick_fp8(int M, int N, int K, int* out3);
  * is a default only where it beat the looped form by more than the larger of
  * the two spreads */
 void hpa_fused_pick_fp4(int M, int N, int K, int* out4);
+/* a W4A8 GEMM (w_dtype = HPA_FP4A8) at variant 0: out4 = {1, waves, row_blocks,
+ * col_tiles}, after profiles/r21/w_mx48.txt (s): 4 waves; (1, 1) below 8 row
+ * blocks at N <= 1024, (4, 2) from M = 512 at K >= 4096, else (2, 2) */
+void hpa_fused_pick_mx48(int M, int N, int K, int* out4);
 /* bf16 weights, A-resident kernel (variant 5: the workgroup's rows of A
  * LayerNorm'ed and rounded into LDS once, waves walking waves*rounds column
  * tiles over the whole K; col_tiles = rounds for this variant):

@@ -179,7 +179,15 @@ int  gpt2_decode_init_ex(GPT2* model, int B, int page_size, int max_ctx, int kv_
  * each, with one e8m0 power-of-two scale per 32 consecutive k of a row
  * (hpa_pack_frag_fp4); wte is stored and multiplied exactly as on an HPA_FP8
  * engine; otherwise as HPA_FP8: the bf16 mode's arithmetic on decode(code) *
- * 2^t, five launches per layer).  kv_dtype 3 is refused: fp4 is a weight format */
+ * 2^t, five launches per layer) or HPA_FP4A8 (4: W4A8 -- the same MXFP4 codes and
+ * scales in the mx4 layout (hpa_pack_frag_mx4), multiplied undecoded by the block-
+ * scaled MFMA against activations quantised once per layer GEMM to MXFP8
+ * (hpa_quant_mxfp8_rows, after the GEMM's LayerNorm): fp32 sums of exact products;
+ * wte, the embedding gather, attention and sampling as on an HPA_FP4 engine; five
+ * hpa_gemm_fused calls per layer, each layer GEMM a quantiser and a GEMM launch;
+ * C % 32 == 0; gpt2_decode_step_bytes counts it as HPA_FP4: approximate, without
+ * the K padding to 128, the scale-dword padding and the workspace traffic).
+ * kv_dtype 3 and 4 are refused: they are weight formats */
 int  gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dtype, int w_dtype);
 /* one decode step for every sequence: tokens[b] (host) at position pos[b];
  * tokens == NULL feeds back the previous step's greedy ids (device-resident).
@@ -743,7 +751,9 @@ int    gpt2_decode_weight_scales(GPT2* model, float* out);
 /* fp4 weights (w_dtype = HPA_FP4): the e8m0 group-scale bytes of the layer
  * matrices as the engine holds them, n = L * 12 C^2 / 32 bytes: per layer qkvw,
  * attprojw, fcw, fcprojw, each in the unit order of hpa_pack_frag_fp4
- * ([row block][64-deep step][16 rows][2]).  Nonzero on any other engine or n. */
+ * ([row block][64-deep step][16 rows][2]).  HPA_FP4A8: the same bytes as the scale
+ * dwords of hpa_pack_frag_mx4, n = L * the four matrices' hpa_frag_mx4_scale_bytes.
+ * Nonzero on any other engine or n. */
 int    gpt2_decode_weight_group_scales(GPT2* model, unsigned char* out, size_t n);
 /* K/V of positions [0, n) of sequence b at layer l, token-major [n][C] host
  * arrays (the reference page layout, block_manager.c:145-146); bf16 / fp8

@@ -900,7 +900,25 @@ static int gemm_fused_launch(const HpaFusedGemm* g, FG& p) {
         if (ntw == 2 && mt == 1) ntw = 1;
         return launch_f4w(p, g->w_gscale, g->epilogue, nw, mt, ntw);
     }
-    HPA_REQUIRE(g->w_dtype == HPA_F32, "gemm_fused: w_dtype must be HPA_F32, HPA_BF16, HPA_FP8 or HPA_FP4");
+    if (g->w_dtype == HPA_FP4A8) {  // MXFP4 weights x MXFP8 activations: hpa_gemm_mx48.hip
+        HPA_REQUIRE(g->epilogue == HPA_FEPI_QKV || g->epilogue == HPA_FEPI_RESID || g->epilogue == HPA_FEPI_GELU,
+                    "gemm_fused W4A8: epilogue QKV, RESID or GELU (the layer matrices); LOGITS and SCORE multiply "
+                    "wte, which is fp8 on a W4A8 engine");
+        HPA_REQUIRE(g->variant == 0 || g->variant == 1, "gemm_fused W4A8: variant 0 or 1 (looped)");
+        HPA_REQUIRE(!g->ln_fold_c1, "gemm_fused W4A8: ln_fold_c1 must be NULL (LN in the activation quantiser)");
+        HPA_REQUIRE(g->w_gscale, "gemm_fused W4A8: w_gscale is NULL");
+        HPA_REQUIRE(g->a_ws, "gemm_fused W4A8: a_ws (the activation workspace, hpa_mxfp8_workspace_bytes) is NULL");
+        HPA_REQUIRE(g->K % 32 == 0, "gemm_fused W4A8: K % 32 != 0");
+        int pk[4];
+        hpa_fused_pick_mx48(g->M, g->N, g->K, pk);
+        nw = g->waves ? g->waves : pk[1];
+        mt = g->row_blocks ? g->row_blocks : pk[2];
+        ntw = g->col_tiles ? g->col_tiles : pk[3];
+        while (mt > 1 && (p.Mp / 16) % mt) mt >>= 1;  // row blocks of this M
+        if (ntw == 2 && mt == 1) ntw = 1;
+        return launch_mx48(p, g->w_gscale, g->a_ws, g->epilogue, nw, mt, ntw);
+    }
+    HPA_REQUIRE(g->w_dtype == HPA_F32, "gemm_fused: w_dtype must be HPA_F32, HPA_BF16, HPA_FP8, HPA_FP4 or HPA_FP4A8");
     if (g->variant == 6) return launch_sk(p, g->epilogue);  // stream-K (hpa_gemm_sk.hip)
     HPA_REQUIRE(g->row_blocks == 0 || g->row_blocks == 1 || g->row_blocks == 2 || g->row_blocks == 4,
                 "gemm_fused: row_blocks must be 1, 2 or 4");

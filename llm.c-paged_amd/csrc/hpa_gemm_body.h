@@ -714,6 +714,10 @@ int launch_f8w(const FG& p, const float* w_scale, int epi, int nw, int mt, int n
 // Looped: the shapes of launch_b16; A-resident: those of launch_b16_ares
 int launch_f4w(const FG& p, const unsigned char* gscale, int epi, int nw, int mt, int ntw);
 int launch_f4w_ares(const FG& p, const unsigned char* gscale, int epi, int nw, int mt, int rounds);
+// W4A8 launch (hpa_gemm_mx48.hip): e2m1 codes and e8m0 scale dwords in the mx4
+// layout, a_ws the activation workspace; the quantiser (with the LN), then
+// the scaled-MFMA GEMM; QKV / RESID / GELU, the shapes of launch_b16
+int launch_mx48(const FG& p, const unsigned char* gscale, void* a_ws, int epi, int nw, int mt, int ntw);
 // A-resident bf16 variant (variant 5): waves 4/8, row_blocks (mt) 1/2/4 with
 // mt*K <= 3200; each workgroup takes waves*rounds column tiles
 int launch_b16_ares(const FG& p, int epi, int nw, int mt, int rounds);

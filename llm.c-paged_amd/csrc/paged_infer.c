@@ -652,14 +652,19 @@ struct GPT2Decode {
     int* ring_cnt;
     size_t ring_cnt_n;
     float* d_wpack;   /* packed qkvw, attprojw, fcw, fcprojw of every layer, then wte */
-    int w_dtype;      /* HPA_F32, HPA_BF16 (hpa_pack_frag_bf16), HPA_FP8 (hpa_pack_frag_fp8) or HPA_FP4
+    int w_dtype;      /* HPA_F32, HPA_BF16 (hpa_pack_frag_bf16), HPA_FP8 (hpa_pack_frag_fp8), HPA_FP4A8
+                         (hpa_pack_frag_mx4: as HPA_FP4 below, in the mx4 layout) or HPA_FP4
                          (hpa_pack_frag_fp4: the layer packs at half a byte per element, the wte pack
                          fp8 behind them): the packs' storage; offsets in elements of it */
     float* d_wscale;  /* fp8 weights: the scale of every output channel -- per layer qkv [3C],
                          attproj [C], fc [4C], fcproj [C], then wte [V padded to 16]; fp4 weights: wte's
                          alone; else NULL */
     unsigned char* d_wgscale; /* fp4 weights: the layer packs' e8m0 group scales, one byte per 32
-                         elements at the packs' element offsets / 32; else NULL */
+                         elements at the packs' element offsets / 32 (HPA_FP4A8: the mx4 scale dwords,
+                         hpa_frag_mx4_scale_bytes each); else NULL */
+    size_t wg_off[4], wg_layer; /* byte offsets of a layer's four scale blocks in d_wgscale, bytes per layer */
+    void *mx_ws, *pf_mx_ws; /* HPA_FP4A8: the activation workspaces (hpa_mxfp8_workspace_bytes at K = 4C) of
+                         the decode step's rows and of the dense pass's pf_cap rows; else NULL */
     size_t wpack_off[5]; /* per-layer offsets (0..3) and wte offset (4) */
     size_t wpack_layer;  /* elements of one layer's four packs */
     float* d_fold;    /* LN folded into qkvw / fcw (hpa_ln_fold_pack): per layer c1, c2 of
@@ -863,7 +868,8 @@ static void pool_view_release(void* ctx, int page, int kv, void* p) {
 }
 
 static void dec_prefill_free(GPT2Decode* d) {
-    hpa_free(d->pf_res); hpa_free(d->pf_res2); hpa_free(d->pf_att); hpa_free(d->pf_fch);
+    hpa_free(d->pf_res); hpa_free(d->pf_res2); hpa_free(d->pf_att); hpa_free(d->pf_fch); hpa_free(d->pf_mx_ws);
+    d->pf_mx_ws = NULL;
     hpa_free(d->pf_st1); hpa_free(d->pf_st2); hpa_free(d->pf_q);
     hpa_free(d->pf_tok); hpa_free(d->pf_pos); hpa_free(d->pf_seq); hpa_free(d->pf_start); hpa_free(d->pf_last);
     free(d->h_pf);
@@ -971,6 +977,7 @@ static void dec_free(GPT2Decode* d) {
     hpa_free(d->d_wpack);
     hpa_free(d->d_wscale);
     hpa_free(d->d_wgscale);
+    hpa_free(d->mx_ws);
     hpa_free(d->d_fold);
     hpa_free(d->d_attn_ws);
     hpa_free(d->d_sh); hpa_free(d->d_sh_ws);
@@ -1003,11 +1010,12 @@ void gpt2_decode_free(GPT2* model) {
 
 /* half-bytes per packed element of the layer matrices */
 static size_t wpack_elem_nibbles(const GPT2Decode* d) {
-    return d->w_dtype == HPA_FP4 ? 1 : d->w_dtype == HPA_FP8 ? 2 : d->w_dtype == HPA_BF16 ? 4 : 8;
+    return d->w_dtype == HPA_FP4 || d->w_dtype == HPA_FP4A8 ? 1 : d->w_dtype == HPA_FP8 ? 2 : d->w_dtype == HPA_BF16 ? 4 : 8;
 }
 
 /* the dtype of the wte pack: an fp4 engine keeps wte fp8 (only the layer matrices go to fp4) */
-static int wte_dtype(const GPT2Decode* d) { return d->w_dtype == HPA_FP4 ? HPA_FP8 : d->w_dtype; }
+static int w_is_fp4(const GPT2Decode* d) { return d->w_dtype == HPA_FP4 || d->w_dtype == HPA_FP4A8; }
+static int wte_dtype(const GPT2Decode* d) { return w_is_fp4(d) ? HPA_FP8 : d->w_dtype; }
 
 /* packed layer weights at element offset off (fp32, bf16, fp8 or fp4 pack; every offset is even) */
 static const float* wpack_at(const GPT2Decode* d, size_t off) {
@@ -1019,7 +1027,7 @@ static const float* wte_pack(const GPT2Decode* d) { return wpack_at(d, d->wpack_
 
 /* fp8 and fp4 weights: the scales of wte's rows (else NULL) */
 static const float* wte_scale(const GPT2Decode* d, const GPT2Config* c) {
-    if (d->w_dtype == HPA_FP4) return d->d_wscale;
+    if (w_is_fp4(d)) return d->d_wscale;
     return d->d_wscale ? d->d_wscale + (size_t)c->num_layers * 9 * c->channels : NULL;
 }
 
@@ -1048,11 +1056,11 @@ static DecLayerOps dec_layer_ops(const GPT2* model, const GPT2Decode* d, int l) 
     o.w_fc = wpack_at(d, d->wpack_layer * l + d->wpack_off[2]);
     o.w_fp = wpack_at(d, d->wpack_layer * l + d->wpack_off[3]);
     const float* sl = d->w_dtype == HPA_FP8 && d->d_wscale ? d->d_wscale + 9 * lc : NULL;
-    const unsigned char* gl = d->d_wgscale ? d->d_wgscale + d->wpack_layer * l / 32 : NULL;
+    const unsigned char* gl = d->d_wgscale ? d->d_wgscale + d->wg_layer * l : NULL;
     o.g_qkv = gl;
-    o.g_ap = gl ? gl + d->wpack_off[1] / 32 : NULL;
-    o.g_fc = gl ? gl + d->wpack_off[2] / 32 : NULL;
-    o.g_fp = gl ? gl + d->wpack_off[3] / 32 : NULL;
+    o.g_ap = gl ? gl + d->wg_off[1] : NULL;
+    o.g_fc = gl ? gl + d->wg_off[2] : NULL;
+    o.g_fp = gl ? gl + d->wg_off[3] : NULL;
     o.s_qkv = sl;
     o.s_ap = sl ? sl + 3 * C : NULL;
     o.s_fc = sl ? sl + 4 * C : NULL;
@@ -1079,8 +1087,17 @@ static int dec_init_weights(GPT2* model, GPT2Decode* d) {
     const GPT2Config c = model->config;
     const int B = d->B, C = c.channels, L = c.num_layers, V = c.vocab_size;
     const ParameterTensors* w = &model->params;
-    const size_t e_qkv = hpa_frag_elems(3 * C, C), e_ap = hpa_frag_elems(C, C);
-    const size_t e_fc = hpa_frag_elems(4 * C, C), e_fp = hpa_frag_elems(C, 4 * C);
+    /* W4A8: K padded to the scaled MFMA's 128-deep step (two codes a byte) */
+    const int a8 = d->w_dtype == HPA_FP4A8;
+    const size_t e_qkv = a8 ? 2 * hpa_frag_mx4_bytes(3 * C, C) : hpa_frag_elems(3 * C, C);
+    const size_t e_ap = a8 ? 2 * hpa_frag_mx4_bytes(C, C) : hpa_frag_elems(C, C);
+    const size_t e_fc = a8 ? 2 * hpa_frag_mx4_bytes(4 * C, C) : hpa_frag_elems(4 * C, C);
+    const size_t e_fp = a8 ? 2 * hpa_frag_mx4_bytes(C, 4 * C) : hpa_frag_elems(C, 4 * C);
+    d->wg_off[0] = 0;
+    d->wg_off[1] = a8 ? hpa_frag_mx4_scale_bytes(3 * C, C) : e_qkv / 32;
+    d->wg_off[2] = d->wg_off[1] + (a8 ? hpa_frag_mx4_scale_bytes(C, C) : e_ap / 32);
+    d->wg_off[3] = d->wg_off[2] + (a8 ? hpa_frag_mx4_scale_bytes(4 * C, C) : e_fc / 32);
+    d->wg_layer = d->wg_off[3] + (a8 ? hpa_frag_mx4_scale_bytes(C, 4 * C) : e_fp / 32);
     const size_t e_layer = d->wpack_layer = e_qkv + e_ap + e_fc + e_fp;
     d->wpack_off[0] = 0;
     d->wpack_off[1] = e_qkv;
@@ -1090,19 +1107,22 @@ static int dec_init_weights(GPT2* model, GPT2Decode* d) {
     const size_t wte_bytes = hpa_frag_elems(V, C) * (wte_dtype(d) == HPA_FP8 ? 1 : wte_dtype(d) == HPA_BF16 ? 2 : 4);
     d->d_wpack = (float*)hpa_malloc(d->wpack_off[4] * wpack_elem_nibbles(d) / 2 + wte_bytes);
     if (!d->d_wpack) return 1;
-    if (d->w_dtype == HPA_FP4) { /* fp4 weights: the layer packs at the same element offsets, half a
-                                  * byte each, their group scales at offset / 32; wte as on an fp8
-                                  * engine; LN on the operand path */
+    if (w_is_fp4(d)) { /* fp4 weights: the layer packs at the same element offsets, half a byte each,
+                        * their group scales at offset / 32; wte as on an fp8 engine; LN on the
+                        * operand path.  W4A8: the same codes and bytes in the mx4 layout, and the
+                        * decode rows' activation workspace */
+        int (*pack)(const float*, int, int, int, unsigned char*, unsigned char*) = a8 ? hpa_pack_frag_mx4 : hpa_pack_frag_fp4;
         d->d_wscale = (float*)hpa_malloc((size_t)(V + 15) / 16 * 16 * sizeof(float));
-        d->d_wgscale = (unsigned char*)hpa_malloc(d->wpack_off[4] / 32);
-        if (!d->d_wscale || !d->d_wgscale) return 1;
+        d->d_wgscale = (unsigned char*)hpa_malloc(d->wg_layer * L);
+        if (a8) d->mx_ws = hpa_malloc(hpa_mxfp8_workspace_bytes(B, 4 * C));
+        if (!d->d_wscale || !d->d_wgscale || (a8 && !d->mx_ws)) return 1;
         for (int l = 0; l < L; l++) {
             const DecLayerOps o = dec_layer_ops(model, d, l);
             const size_t lc = (size_t)l * C;
-            if (hpa_pack_frag_fp4(w->qkvw + lc * 3 * C, 3 * C, C, C, (unsigned char*)o.w_qkv, (unsigned char*)o.g_qkv) ||
-                hpa_pack_frag_fp4(w->attprojw + lc * C, C, C, C, (unsigned char*)o.w_ap, (unsigned char*)o.g_ap) ||
-                hpa_pack_frag_fp4(w->fcw + lc * 4 * C, 4 * C, C, C, (unsigned char*)o.w_fc, (unsigned char*)o.g_fc) ||
-                hpa_pack_frag_fp4(w->fcprojw + lc * 4 * C, C, 4 * C, 4 * C, (unsigned char*)o.w_fp, (unsigned char*)o.g_fp))
+            if (pack(w->qkvw + lc * 3 * C, 3 * C, C, C, (unsigned char*)o.w_qkv, (unsigned char*)o.g_qkv) ||
+                pack(w->attprojw + lc * C, C, C, C, (unsigned char*)o.w_ap, (unsigned char*)o.g_ap) ||
+                pack(w->fcw + lc * 4 * C, 4 * C, C, C, (unsigned char*)o.w_fc, (unsigned char*)o.g_fc) ||
+                pack(w->fcprojw + lc * 4 * C, C, 4 * C, 4 * C, (unsigned char*)o.w_fp, (unsigned char*)o.g_fp))
                 return 1;
         }
         if (hpa_pack_frag_fp8(w->wte, V, C, C, (unsigned char*)wte_pack(d), (float*)wte_scale(d, &c))) return 1;
@@ -1522,8 +1542,8 @@ int gpt2_decode_init_w(GPT2* model, int B, int page_size, int max_ctx, int kv_dt
         fprintf(stderr, "[paged_infer] kv dtype must be HPA_F32, HPA_BF16 or HPA_FP8 (HPA_FP4 is a weight format)\n");
         return 1;
     }
-    if (w_dtype != HPA_F32 && w_dtype != HPA_BF16 && w_dtype != HPA_FP8 && w_dtype != HPA_FP4) {
-        fprintf(stderr, "[paged_infer] weight dtype must be HPA_F32, HPA_BF16, HPA_FP8 or HPA_FP4\n");
+    if (w_dtype != HPA_F32 && w_dtype != HPA_BF16 && w_dtype != HPA_FP8 && w_dtype != HPA_FP4 && w_dtype != HPA_FP4A8) {
+        fprintf(stderr, "[paged_infer] weight dtype must be HPA_F32, HPA_BF16, HPA_FP8, HPA_FP4 or HPA_FP4A8\n");
         return 1;
     }
     if (!model->params_memory) { fprintf(stderr, "[paged_infer] model not built\n"); return 1; }
@@ -1840,6 +1860,7 @@ static void dec_gemm_desc(GPT2* model, int l, int which, HpaFusedGemm* g) {
     memset(g, 0, sizeof(*g));
     g->M = d->B;
     g->w_dtype = d->w_dtype;
+    g->a_ws = d->mx_ws;
     g->epilogue = which == G_QKV ? HPA_FEPI_QKV : which == G_FC ? HPA_FEPI_GELU
                 : which == G_LOGITS ? HPA_FEPI_LOGITS : HPA_FEPI_RESID;
     g->waves = d->fwaves[which];
@@ -2789,6 +2810,7 @@ static int dec_prefill_reserve(GPT2* model, int R) {
     d->pf_st1 = (float*)hpa_malloc(ct * Rp * 2 * 4);
     d->pf_st2 = (float*)hpa_malloc(ct * Rp * 2 * 4);
     d->pf_q = (float*)hpa_malloc(Rp * C * 4);
+    if (d->w_dtype == HPA_FP4A8) d->pf_mx_ws = hpa_malloc(hpa_mxfp8_workspace_bytes((int)Rp, 4 * (int)C));
     d->pf_tok = (int*)hpa_malloc(Rp * sizeof(int));
     d->pf_pos = (int*)hpa_malloc(Rp * sizeof(int));
     d->pf_seq = (int*)hpa_malloc(Rp * sizeof(int));
@@ -2796,7 +2818,8 @@ static int dec_prefill_reserve(GPT2* model, int R) {
     d->pf_last = (int*)hpa_malloc(d->B * sizeof(int));
     d->h_pf = (int*)malloc((3 * Rp + 4 * (size_t)d->B) * sizeof(int));
     if (!d->pf_res || !d->pf_res2 || !d->pf_att || !d->pf_fch || !d->pf_st1 || !d->pf_st2 || !d->pf_q ||
-        !d->pf_tok || !d->pf_pos || !d->pf_seq || !d->pf_start || !d->pf_last || !d->h_pf) {
+        !d->pf_tok || !d->pf_pos || !d->pf_seq || !d->pf_start || !d->pf_last || !d->h_pf ||
+        (d->w_dtype == HPA_FP4A8 && !d->pf_mx_ws)) {
         dec_prefill_free(d);
         return 1;
     }
@@ -2817,6 +2840,7 @@ static int prefill_gemm(GPT2* model, int l, int which, int R) {
     memset(&g, 0, sizeof(g));
     g.M = R;
     g.w_dtype = d->w_dtype;
+    g.a_ws = d->pf_mx_ws;
     /* many rows: reuse every activation fragment over 2 weight tiles and every
      * weight fragment over 4 row blocks (MFMA-bound at this M) */
     const int lib_shape = d->w_dtype != HPA_F32; /* bf16 / fp8 weights: the library's shapes by (M, N, K) */
@@ -4082,7 +4106,7 @@ int gpt2_decode_weight_scales(GPT2* model, float* out) {
     }
     const GPT2Config c = model->config;
     const size_t nl = (size_t)c.num_layers * 9 * c.channels, n = nl + c.vocab_size;
-    if (d->w_dtype == HPA_FP4) { /* the layer matrices carry group scales (gpt2_decode_weight_group_scales) */
+    if (w_is_fp4(d)) { /* the layer matrices carry group scales (gpt2_decode_weight_group_scales) */
         for (size_t i = 0; i < nl; i++) out[i] = 1.0f;
         return hpa_synchronize() || hpa_memcpy(out + nl, d->d_wscale, (size_t)c.vocab_size * sizeof(float));
     }
@@ -4091,9 +4115,9 @@ int gpt2_decode_weight_scales(GPT2* model, float* out) {
 
 int gpt2_decode_weight_group_scales(GPT2* model, unsigned char* out, size_t n) {
     GPT2Decode* d = model ? model->decode : NULL;
-    const size_t have = d && d->d_wgscale ? d->wpack_off[4] / 32 : 0;
+    const size_t have = d && d->d_wgscale ? d->wg_layer * (size_t)model->config.num_layers : 0;
     if (!have || !out || n != have) {
-        fprintf(stderr, "[paged_infer] gpt2_decode_weight_group_scales: needs an fp4-weight engine and n = L * 12 C^2 / 32\n");
+        fprintf(stderr, "[paged_infer] gpt2_decode_weight_group_scales: needs an fp4-weight engine and n = its scale bytes\n");
         return 1;
     }
     return hpa_synchronize() || hpa_memcpy(out, d->d_wgscale, n);
@@ -4305,7 +4329,7 @@ double gpt2_decode_step_bytes(GPT2* model, double* attn_bytes) {
     const double wm = (double)wpack_elem_nibbles(d) / 2; /* layer matrices: fp32, bf16, fp8 or fp4 */
     const double wt = wte_dtype(d) == HPA_FP8 ? 1.0 : wte_dtype(d) == HPA_BF16 ? 2.0 : 4.0; /* wte (fp4 engine: fp8) */
     /* fp8: one scale per output channel; fp4: one byte per 32 layer weights, and wte's fp8 scales */
-    const double wsc = d->w_dtype == HPA_FP8 ? (L * 9 * C + V) * w : d->w_dtype == HPA_FP4 ? L * 12 * C * C / 32 + V * w : 0.0;
+    const double wsc = d->w_dtype == HPA_FP8 ? (L * 9 * C + V) * w : w_is_fp4(d) ? L * 12 * C * C / 32 + V * w : 0.0;
     const double weights = L * 12 * C * C * wm + V * C * wt + wsc + (L * 13 * C + 2 * C) * w;
     double kv = 0.0;
     for (int b = 0; b < d->B; b++) kv += 2.0 * L * (d->h_pos[b] + 1) * C * wkv;

@@ -60,7 +60,8 @@ class HpaFusedGemm(ctypes.Structure):
                 ("row_blocks", ctypes.c_int), ("variant", ctypes.c_int), ("col_tiles", ctypes.c_int),
                 ("row_seq", _V), ("ln_fold_c1", _V), ("sk_slab", _V), ("sk_count", _V),
                 ("w_dtype", ctypes.c_int), ("pick_next", _V), ("pick_tokens", _V), ("pick_pos", _V),
-                ("pick_count", _V), ("score_target", _V), ("score_part", _V), ("w_scale", _V), ("w_gscale", _V)]
+                ("pick_count", _V), ("score_target", _V), ("score_part", _V), ("w_scale", _V), ("w_gscale", _V),
+                ("a_ws", _V)]
 
 
 class HpaChainB16Args(ctypes.Structure):
@@ -163,6 +164,33 @@ def from_frag_mx_scales(scales_u8, rows, K):
     """the group scales' unit order ([row block][64-deep step][16 rows][2]) -> [rows][K / 32] bytes"""
     m, g = np.meshgrid(np.arange(rows), np.arange(K // 32), indexing="ij")
     return np.asarray(scales_u8, np.uint8)[(((m >> 4) * (K >> 6) + (g >> 1)) * 16 + (m & 15)) * 2 + (g & 1)]
+
+
+def from_frag_mx4(codes_u8, rows, K):
+    """mx4 weight layout (hpa_pack_frag_mx4) -> [rows][K] e2m1 codes, one per element: lane m % 16 +
+    16 * ((k % 128) / 32) of unit (m / 16) * S + k / 128, byte (k % 32) / 2 of its 16, nibble k % 2"""
+    m, k = np.meshgrid(np.arange(rows), np.arange(K), indexing="ij")
+    S = (K + 127) // 128
+    byte = (((m >> 4) * S + (k >> 7)) * 64 + (m & 15) + 16 * ((k >> 5) & 3)) * 16 + ((k & 31) >> 1)
+    return (np.asarray(codes_u8, np.uint8)[byte] >> (4 * (k & 1))) & 15
+
+
+def from_frag_mx4_scales(scales_u8, rows, K):
+    """the mx4 scale dwords ([row block][S4][64 lanes][4 steps]) -> [rows][K / 32] bytes"""
+    m, g = np.meshgrid(np.arange(rows), np.arange(K // 32), indexing="ij")
+    S4 = ((K + 127) // 128 + 3) // 4
+    return np.asarray(scales_u8, np.uint8)[(((m >> 4) * S4 + (g >> 4)) * 64 + (m & 15) + 16 * (g & 3)) * 4 + ((g >> 2) & 3)]
+
+
+def from_mxfp8_workspace(ws_u8, M, K):
+    """the activation workspace of hpa_quant_mxfp8_rows -> (e4m3 codes [Mp][Kp], scale bytes [Mp][16 S4]),
+    padding included (the last scale dword's unused steps too): codes [row block][S][2 halves][64 lanes]
+    [16 B] (half h of lane l: k = 64 h + 16 (l / 16) + 0..15), then the scales in the mx4 order"""
+    Mp, S = (M + 15) // 16 * 16, (K + 127) // 128
+    ws = np.asarray(ws_u8, np.uint8)
+    m, k = np.meshgrid(np.arange(Mp), np.arange(S * 128), indexing="ij")
+    byte = ((((m >> 4) * S + (k >> 7)) * 2 + ((k >> 6) & 1)) * 64 + (m & 15) + 16 * ((k >> 4) & 3)) * 16 + (k & 15)
+    return ws[byte], from_frag_mx4_scales(ws[Mp * S * 128:], Mp, ((S + 3) // 4) * 512)
 
 
 GPT2_124M = dict(maxT=1024, V=50257, L=12, NH=12, C=768)
@@ -340,6 +368,12 @@ def lib():
     _sig(L, "hpa_frag_fp4_bytes", ctypes.c_size_t, [i, i])
     _sig(L, "hpa_frag_mx_scale_bytes", ctypes.c_size_t, [i, i])
     _sig(L, "hpa_fused_pick_fp4", None, [i, i, i, _I])
+    _sig(L, "hpa_pack_frag_mx4", i, [v, i, i, i, v, v])
+    _sig(L, "hpa_frag_mx4_bytes", ctypes.c_size_t, [i, i])
+    _sig(L, "hpa_frag_mx4_scale_bytes", ctypes.c_size_t, [i, i])
+    _sig(L, "hpa_mxfp8_workspace_bytes", ctypes.c_size_t, [i, i])
+    _sig(L, "hpa_quant_mxfp8_rows", i, [v, i, i, v, i, v, v, v])
+    _sig(L, "hpa_fused_pick_mx48", None, [i, i, i, _I])
     _sig(L, "gpt2_decode_prefill", i, [v, _I, i, _I])
     _sig(L, "gpt2_decode_prefill_ragged", i, [v, _I, _I, _I])
     _sig(L, "gpt2_decode_score", i, [v, _I, _I, _I, _F, _I, _I])
@@ -786,7 +820,25 @@ def quantize_mxfp4_rows(W):
     return codes, (t + 127).astype(np.uint8), deq
 
 
-HPA_F32, HPA_BF16, HPA_FP8, HPA_FP4 = 0, 1, 2, 3
+def quantize_mxfp8_rows(A):
+    """MXFP8 quantisation of activations A [M][K] (hpa_quant_mxfp8_rows' rule, restated): per row and
+    group of 32 consecutive k, t = the smallest integer with absmax / 2^t <= 448 (absmax = m 2^e with
+    m in [0.5, 1): e - 9 for m <= 0.875, else e - 8), clamped to [-64, 64], 0 for an all-zero group;
+    code = e4m3fn_rne(a 2^-t), subnormals kept, ties to even, clamped at 448 (reached only where t
+    was clamped).  Returns (codes uint8 [M][K]; e8m0 bytes t + 127 [M][K / 32]; decode(codes) * 2^t
+    as float64: exact there, and beyond fp32 only in groups that fp32 could not hold either)."""
+    A = np.ascontiguousarray(A, np.float32)
+    M, K = A.shape
+    G = A.reshape(M, K // 32, 32)
+    m, e = np.frexp(np.abs(G).max(axis=2))
+    t = np.clip(np.where(m <= 0.875, e - 9, e - 8), -64, 64)
+    t = np.where(m == 0, 0, t).astype(np.int32)
+    codes = to_fp8_bits(np.ldexp(G, -t[:, :, None]).astype(np.float32))
+    deq = np.ldexp(from_fp8_bits(codes).astype(np.float64), t[:, :, None]).reshape(M, K)
+    return codes.reshape(M, K), (t + 127).astype(np.uint8), deq
+
+
+HPA_F32, HPA_BF16, HPA_FP8, HPA_FP4, HPA_FP4A8 = 0, 1, 2, 3, 4
 
 
 class Pool:
@@ -1129,7 +1181,7 @@ class Model:
         max_ctx = max_ctx or self.cfg.max_seq_len
         check(lib().gpt2_decode_init_w(self.h, B, page_size, max_ctx, int(kv_dtype), int(w_dtype)),
               "gpt2_decode_init")
-        self.B = B
+        self.B, self.w_dtype = B, int(w_dtype)
 
     def set_graph(self, on):
         check(lib().gpt2_decode_set_graph(self.h, int(on)), "set_graph")
@@ -1293,14 +1345,17 @@ class Model:
         [3C][C/32], attprojw [C][C/32], fcw [4C][C/32], fcprojw [C][4C/32]
         (gpt2_decode_weight_group_scales, un-permuted from the engine's unit order)"""
         C, L = self.cfg.channels, self.cfg.num_layers
-        raw = np.zeros(L * 12 * C * C // 32, np.uint8)
+        mats = ((3 * C, C), (C, C), (4 * C, C), (C, 4 * C))
+        a8 = self.w_dtype == HPA_FP4A8  # W4A8: the mx4 scale dwords, K padded to 128 and four steps a dword
+        size = [int(lib().hpa_frag_mx4_scale_bytes(r, K)) if a8 else r * K // 32 for r, K in mats]
+        raw = np.zeros(L * sum(size), np.uint8)
         check(lib().gpt2_decode_weight_group_scales(self.h, raw.ctypes.data, raw.size), "weight_group_scales")
         out, at = [], 0
         for _ in range(L):
             out.append([])
-            for rows, K in ((3 * C, C), (C, C), (4 * C, C), (C, 4 * C)):
-                out[-1].append(from_frag_mx_scales(raw[at:at + rows * K // 32], rows, K))
-                at += rows * K // 32
+            for (rows, K), n in zip(mats, size):
+                out[-1].append((from_frag_mx4_scales if a8 else from_frag_mx_scales)(raw[at:at + n], rows, K))
+                at += n
         return out
 
     def shard(self, rows_per_rank, root=0):
