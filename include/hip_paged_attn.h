@@ -1133,6 +1133,31 @@ int hpa_verify_tree_accept(const int* tok, const int* top_id, const int* parents
 int hpa_pool_compact_path(const HpaKVPool* pool, const int* block_table, int bt_stride, const int* start,
                           const int* path, const int* n_accepted, int B);
 
+/* ---------------- speculation on bf16 / fp8 pools (hpa_verify_packed.hip) ----------------
+ * hpa_paged_attention_verify_packed: the few-row verify attention of
+ * hpa_paged_attention_verify (anc == NULL, the chain form) and of
+ * hpa_paged_attention_verify_tree (anc given) on HPA_BF16 pools of page size
+ * 8 / 16 / 32 / 64 and HPA_FP8 pools of page size 16 / 32 / 64: the same
+ * contract, work split, wave choice and fold, tile loops over the pools' 16-byte
+ * chunks of codes (64 / 32 VGPRs a tile), every code decoded exactly and every
+ * product and sum in fp32; an fp8 pool's scales are read on the device (the
+ * score takes qscale * k_scale, the finished output v_scale).  With chain masks
+ * the tree form's bits are the chain form's.  Head size 64, 1 <= T <=
+ * HPA_VERIFY_MAX_ROWS; anything else, an fp32 pool included, returns nonzero
+ * and launches nothing. */
+int hpa_paged_attention_verify_packed(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
+                                      int bt_stride, const int* start, const int* row0, const int* len,
+                                      const unsigned char* anc, int B, int T, float* out_frag);
+/* where the kernel above decodes a tile's codes, process-wide (timing tools):
+ * 1 inside each row's loop, 2 once per tile (chunk outermost, rows inside), 0
+ * (default) the form the library keeps per (dtype, rows).  Same bits each way. */
+int hpa_set_verify_packed_form(int form);
+/* hpa_pool_compact_path on a bf16 / fp8 pool: the same launch structure and
+ * invariants, the 16-byte lanes being the pools' K chunks and V row pieces.
+ * Bytes only.  An fp32 pool returns nonzero and launches nothing. */
+int hpa_pool_compact_path_packed(const HpaKVPool* pool, const int* block_table, int bt_stride, const int* start,
+                                 const int* path, const int* n_accepted, int B);
+
 /* rows[i] of a frag-layout [src_Mp][C] matrix and of its LN statistics
  * ([C/16][src_Mp][2]) -> row i of dst / dst_stats (n rows; prefill -> logits);
  * rows[i] < 0 leaves row i of dst as it is */

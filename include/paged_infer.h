@@ -264,11 +264,18 @@ int  gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int*
  * pure: 1 hpa_paged_attention_verify (the decode kernel's K/V streaming, every
  * tile used for all rows), 0 hpa_paged_attention_prefill_ragged.  request: 0
  * auto, 1 the prefill kernel, 2 the verify kernel -- still refused (0) where
- * it does not apply: bf16 and fp8 pools (their tile loops are not written:
- * the prefill kernel is correct there, and slower), head size != 64, a page
- * size other than 8, 16, 32 or 64, more than HPA_VERIFY_MAX_ROWS rows. */
+ * it does not apply: bf16 and fp8 pools (their few-row kernel is not used
+ * under these requests: the prefill kernel is correct there, and slower; see
+ * request 3), head size != 64, a page
+ * size other than 8, 16, 32 or 64, more than HPA_VERIFY_MAX_ROWS rows.
+ * request 3 (opt-in): the few-row kernel on every pool that has one -- as 2 on
+ * fp32 pools, and 1 on bf16 pools (page size 8, 16, 32, 64) and fp8 pools (16,
+ * 32, 64), whose kernel is hpa_paged_attention_verify_packed.  Requests 0, 1
+ * and 2 answer as they always did. */
 int  gpt2_decode_verify_plan(int max_rows, int kv_dtype, int page_size, int head_size, int request);
-/* the request gpt2_decode_verify passes to the plan (default 0) */
+/* the request the verify passes hand to the plan (default 0; 0 .. 3).  3 also
+ * opens gpt2_decode_verify_tree and gpt2_decode_verify_tree_sampled on bf16 and
+ * fp8 pools */
 int  gpt2_decode_set_verify_attention(GPT2* model, int request);
 /* Speculative sampling: gpt2_decode_verify under sampling mode 2 (per-sequence
  * temperature / top-k / top-p).  Arguments, row layout, page growth, eviction,
@@ -345,8 +352,10 @@ int  gpt2_ngram_draft(const int* history, int n, int max_ngram, int min_ngram, i
  * would leave, K/V slots included.  The slots past the new position hold
  * rejected nodes' rows, which nothing reads.
  * Limits: greedy (gpt2_decode_verify_tree_sampled is the pass for sampling
- * mode 2); fp32 KV pools (the
- * bf16 / fp8 pools' prefill kernel has no tree mask); at most
+ * mode 2); fp32 KV pools, and bf16 / fp8 pools once the engine's request is 3
+ * (gpt2_decode_set_verify_attention: hpa_paged_attention_verify_packed with the
+ * masks and hpa_pool_compact_path_packed; their prefill kernel has no tree
+ * mask); at most
  * HPA_VERIFY_MAX_ROWS nodes; no drafted-token log-probability output (a node
  * with several children has several targets and the SCORE epilogue takes one
  * per row).
@@ -355,7 +364,8 @@ int  gpt2_ngram_draft(const int* history, int n, int max_ngram, int min_ngram, i
  * processors on, n_draft or a draft id out of range, overflow of max_ctx, no
  * engine), a parent outside [0, j], two siblings (same parent) with the same
  * token, and an engine for which gpt2_decode_verify_plan(rows, kv_dtype,
- * page_size, head_size, 0) != 1. */
+ * page_size, head_size, request) != 1, request being 3 where the engine's is 3
+ * and 0 otherwise. */
 int  gpt2_decode_verify_tree(GPT2* model, const int* drafts, const int* parents, const int* n_draft,
                              int* n_accepted, int* out_tokens, int* accepted_nodes);
 /* n-gram tree drafter, host only (no device, allocation or I/O).  For g from

@@ -3105,7 +3105,8 @@ static int dec_trace_fits(GPT2* model, long R) {
  * pf_start: start, row0, len) through the embedding and every layer; T =
  * max(len).  verify_attn: 1 the few-row kernel (gpt2_decode_verify_plan) in
  * place of the MFMA prefill kernel; 2 its tree form over the masks of vt_anc
- * (gpt2_decode_verify_tree) */
+ * (gpt2_decode_verify_tree).  A bf16 / fp8 pool has the few-row kernel only
+ * under request 3 (hpa_paged_attention_verify_packed, both forms) */
 static int dec_prefill_layers(GPT2* model, int R, int T, int verify_attn) {
     GPT2Decode* d = model->decode;
     const int B = d->B, C = model->config.channels, L = model->config.num_layers;
@@ -3128,7 +3129,10 @@ static int dec_prefill_layers(GPT2* model, int R, int T, int verify_attn) {
     PF_TRACE(0);
     for (int l = 0; l < L && !rc; l++) {
         rc |= prefill_gemm(model, l, G_QKV, R);
-        rc |= verify_attn == 2
+        rc |= verify_attn && d->pool.dtype != HPA_F32
+                  ? hpa_paged_attention_verify_packed(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
+                                                      d_len, verify_attn == 2 ? d->vt_anc : NULL, B, T, d->pf_att)
+              : verify_attn == 2
                   ? hpa_paged_attention_verify_tree(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
                                                     d_len, d->vt_anc, B, T, d->pf_att)
               : verify_attn ? hpa_paged_attention_verify(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
@@ -3296,17 +3300,28 @@ int gpt2_decode_score_top(GPT2* model, const int* tokens, const int* lens, const
 int gpt2_decode_verify_plan(int max_rows, int kv_dtype, int page_size, int head_size, int request) {
     if (request == 1) return 0;
     if (max_rows < 1 || max_rows > HPA_VERIFY_MAX_ROWS) return 0;
-    if (kv_dtype != HPA_F32 || head_size != 64) return 0;
+    if (head_size != 64) return 0;
     if (page_size != 8 && page_size != 16 && page_size != 32 && page_size != 64) return 0;
-    return 1; /* auto (0) and an explicit request (2) */
+    /* request 3: the few-row kernel on every pool that has one (bf16 and fp8
+     * pools: hpa_paged_attention_verify_packed; no fp8 pages of 8) */
+    if (request == 3 && (kv_dtype == HPA_BF16 || (kv_dtype == HPA_FP8 && page_size != 8))) return 1;
+    if (kv_dtype != HPA_F32) return 0;
+    return 1; /* auto (0) and an explicit request (2, 3) */
 }
 
 int gpt2_decode_set_verify_attention(GPT2* model, int request) {
     GPT2Decode* d = model->decode;
     if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    if (request < 0 || request > 2) { fprintf(stderr, "[paged_infer] verify attention: request 0, 1 or 2\n"); return 1; }
+    if (request < 0 || request > 3) { fprintf(stderr, "[paged_infer] verify attention: request 0, 1, 2 or 3\n"); return 1; }
     d->vf_request = request;
     return 0;
+}
+
+/* the tree passes' K/V compaction, by the pool's dtype */
+static int dec_compact_path(GPT2Decode* d, const int* path, const int* n_accepted) {
+    return d->pool.dtype == HPA_F32
+               ? hpa_pool_compact_path(&d->pool, d->d_bt, d->bt_stride, d->pf_start, path, n_accepted, d->B)
+               : hpa_pool_compact_path_packed(&d->pool, d->d_bt, d->bt_stride, d->pf_start, path, n_accepted, d->B);
 }
 
 /* The dense route of the sampled verify passes: the packed rows hrows [ND]
@@ -3468,9 +3483,12 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
         for (int b = 0; b < B; b++) n_accepted[b] = -1;
         return 0;
     }
-    if (tree && gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, 0) != 1) {
+    /* a tree pass needs the few-row kernel whatever the request (the prefill kernel has no tree mask); a bf16 /
+     * fp8 pool has it under request 3 only */
+    if (tree && gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request == 3 ? 3 : 0) != 1) {
         fprintf(stderr, "[paged_infer] verify_tree: fp32 KV pool, head size 64, page size 8 / 16 / 32 / 64 only (the "
-                        "prefill kernel of the other pools has no tree mask)\n");
+                        "prefill kernel of the other pools has no tree mask); bf16 and fp8 pools after "
+                        "gpt2_decode_set_verify_attention(model, 3)\n");
         return 1;
     }
     if (dec_trace_fits(model, R)) return 1;
@@ -3566,7 +3584,7 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
         if (!rc && ND) rc = dec_spec_tree_rows(model, R, hr0, drafts, parents, n_draft);
         rc |= hpa_spec_tree_accept(d->sp_w, d->sp_w + (size_t)B * (MR - 1), v_drafts, t_par, v_d0, d->pf_start, d_row0,
                                    d_len, B, d->d_rng, v_acc, t_path, d->pf_last, sp_excl, sp_nexcl, d->d_pos);
-        rc |= hpa_pool_compact_path(&d->pool, d->d_bt, d->bt_stride, d->pf_start, t_path, v_acc, B);
+        rc |= dec_compact_path(d, t_path, v_acc);
     } else if (sampled) {
         if (!rc && ND) rc = dec_spec_rows(model, R, ND, hr0, hln, v_drafts);
         rc |= hpa_spec_accept(d->sp_w, d->sp_w + (size_t)B * (MR - 1), v_drafts, v_d0, d->pf_start, d_row0, d_len, B,
@@ -3577,7 +3595,7 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
         if (tree) {
             rc |= hpa_verify_tree_accept(d->pf_tok, v_top, t_par, v_d0, d->pf_start, d_row0, d_len, B, v_acc, t_path,
                                          d->pf_last, d->d_pos);
-            rc |= hpa_pool_compact_path(&d->pool, d->d_bt, d->bt_stride, d->pf_start, t_path, v_acc, B);
+            rc |= dec_compact_path(d, t_path, v_acc);
         } else {
             rc |= hpa_verify_accept(d->pf_tok, v_top, d->pf_start, d_row0, d_len, B, v_acc, d->pf_last, d->d_pos);
         }

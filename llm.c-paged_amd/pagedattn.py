@@ -435,6 +435,9 @@ def lib():
     _sig(L, "hpa_verify_tree_rows", i, [_I, _I, _I, _I, _I, _I, _I, i, _I, _I, _I, _I, _U8])
     _sig(L, "hpa_verify_tree_accept", i, [_I, _I, _I, _I, _I, _I, _I, i, _I, _I, _I, _I])
     _sig(L, "hpa_pool_compact_path", i, [P, _I, i, _I, _I, _I, i])
+    _sig(L, "hpa_paged_attention_verify_packed", i, [_F, v, i, _I, i, _I, _I, _I, _U8, i, i, _F])
+    _sig(L, "hpa_pool_compact_path_packed", i, [P, _I, i, _I, _I, _I, i])
+    _sig(L, "hpa_set_verify_packed_form", i, [i])
     _sig(L, "gpt2_decode_verify_tree", i, [v, _I, _I, _I, _I, _I, _I])
     _sig(L, "gpt2_ngram_draft_tree", i, [_I, i, i, i, i, i, i, _I, _I])
     _sig(L, "gpt2_decode_verify_tree_sampled", i, [v, _I, _I, _I, _I, _I, _I, _F])
@@ -576,8 +579,12 @@ TOP_LOGPROBS_MAX = 20  # HPA_TOP_LOGPROBS_MAX
 
 def verify_plan(max_rows, kv_dtype=0, page_size=16, head_size=64, request=0):
     """the attention kernel of a verify pass (gpt2_decode_verify_plan, pure): 1
-    hpa_paged_attention_verify, 0 hpa_paged_attention_prefill_ragged.  request:
-    0 auto, 1 the prefill kernel, 2 the verify kernel where it applies"""
+    the few-row kernel (hpa_paged_attention_verify; under request 3 on a bf16 /
+    fp8 pool hpa_paged_attention_verify_packed), 0
+    hpa_paged_attention_prefill_ragged.  request: 0 auto, 1 the prefill kernel,
+    2 the verify kernel where it applies (fp32 pools), 3 the few-row kernel on
+    every pool that has one (fp32; bf16 pages of 8 / 16 / 32 / 64; fp8 pages of
+    16 / 32 / 64)"""
     return int(lib().gpt2_decode_verify_plan(int(max_rows), int(kv_dtype), int(page_size), int(head_size),
                                              int(request)))
 
@@ -1548,7 +1555,9 @@ class Model:
 
     def set_verify_attention(self, request=0):
         """the attention kernel of verify(): 0 auto, 1 the prefill kernel, 2 the
-        few-row verify kernel where it applies (verify_plan)"""
+        few-row verify kernel where it applies (verify_plan), 3 the few-row
+        kernel on bf16 and fp8 pools too -- which also opens verify_tree() and
+        verify_tree_sampled() on those pools"""
         check(lib().gpt2_decode_set_verify_attention(self.h, int(request)), "set_verify_attention")
 
     def set_score_chunk(self, rows=0):
