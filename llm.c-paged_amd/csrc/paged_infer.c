@@ -20,6 +20,7 @@
 
 #include "block_manager.h"
 #include "hip_paged_attn.h"
+#include "verify_tables.h"
 
 /* K parts of the ring qkv / fc at C >= 1024 (dec_gemm, hpa_gemm_ring.hip) */
 #define DEC_RING_QKV_PARTS 3
@@ -618,6 +619,28 @@ typedef struct {
     int attn_launch; /* 1: the decode attention is its own launch before each layer launch */
 } DecPlan;
 
+/* the tables of the verify passes, device and host (h_*): one pointer per
+ * table of VERIFY_TABLES, carved out of the slabs by dec_verify_reserve for
+ * the kinds of pass (tree, sampled) seen so far; a table no such pass uses is
+ * NULL.  The layout is the union of those kinds: the first pass of a new kind
+ * frees every slab and lays them out again, so a chain pass after a tree pass
+ * finds its tables at other offsets than in a chain-only engine (same extents,
+ * same neighbours; nothing in them outlives a pass) */
+_Static_assert(VERIFY_MAX_ROWS == HPA_VERIFY_MAX_ROWS, "verify_tables.h");
+typedef struct {
+    int tree, sampled;
+    void* slab[VS_COUNT];
+#define VERIFY_TABLE_FIELD(type, name) type* name;
+    VERIFY_TABLES(VERIFY_TABLE_FIELD)
+#undef VERIFY_TABLE_FIELD
+} DecVerify;
+
+/* start, first packed row and row count of every sequence in a dense pass:
+ * the three [B] tables of pf_start */
+typedef struct {
+    const int *start, *row0, *len;
+} DecRowTables;
+
 struct GPT2Decode {
     int B, P, max_ctx, max_pages, Mp;
     HpaKVPool pool;
@@ -770,38 +793,13 @@ struct GPT2Decode {
     int* st_ids;
     void* st_ws;
     size_t st_ws_bytes;
-    /* speculative decoding (gpt2_decode_verify): the attention request
-     * (gpt2_decode_set_verify_attention) and the pass's device tables, allocated on
-     * first use: vf_int = drafts [B * 7], draft0 [B], accepted [B], then per row
-     * (B * HPA_VERIFY_MAX_ROWS) the SCORE targets and greedy ids; vf_lp the
-     * rows' log-probabilities; h_vf the host staging of the same */
+    /* speculative decoding (gpt2_decode_verify and its sampled / tree forms): the
+     * attention request (gpt2_decode_set_verify_attention) and the passes' tables
+     * (verify_tables.c has their extents and order; dec_verify_reserve allocates
+     * them on first use).  pf_slot: the rows' append slots while a tree pass runs
+     * its layers (prefill_gemm: the QKV GEMM's positions), NULL otherwise */
     int vf_request;
-    int* vf_int;
-    float* vf_lp;
-    int* h_vf;
-    /* speculative sampling (gpt2_decode_verify_sampled), allocated on first use,
-     * indexed by drafted row (draft0[b] + i): sp_w = w_target, w_total
-     * [2][B * (MR - 1)]; sp_i = the rows' sequences [B * (MR - 1)], then exclude
-     * [B]; h_sp_w the host copy of sp_w */
-    unsigned long long* sp_w;
-    int* sp_i;
-    unsigned long long* h_sp_w;
-    /* tree speculation (gpt2_decode_verify_tree), allocated on first use: vt_int =
-     * drafts [B * 7], parents [B * 7] (one upload), accepted [B], the accepted
-     * path [B * HPA_VERIFY_MAX_ROWS] (one download), the rows' K/V slots [B *
-     * HPA_VERIFY_MAX_ROWS]; vt_anc the rows' ancestor masks; h_vt the host
-     * staging of the upload, then of the download.  pf_slot: the rows' append slots while a tree pass runs its layers
-     * (prefill_gemm: the QKV GEMM's positions), NULL otherwise */
-    int* vt_int;
-    unsigned char* vt_anc;
-    int* h_vt;
-    /* sampled tree speculation (gpt2_decode_verify_tree_sampled), allocated on
-     * first use, BD = B * (MR - 1): ts_int = the dense route's tables (seq [BD],
-     * n_targets [BD], targets [BD * 7], dst [BD * 7]: gpt2_tree_dense_tables),
-     * then exclude [B * 7] and n_exclude [B]; h_ts = the internal nodes' packed
-     * rows [BD], then the host copy of the tables */
-    int* ts_int;
-    int* h_ts;
+    DecVerify vf;
     const int* pf_slot;
     /* logit processors (gpt2_decode_set_processors).  The settings' host
      * mirrors exist from gpt2_decode_init on (they may be set while off); the
@@ -897,18 +895,39 @@ static void dec_top_free(GPT2Decode* d) {
 }
 
 static void dec_verify_free(GPT2Decode* d) {
-    hpa_free(d->vf_int); hpa_free(d->vf_lp);
-    free(d->h_vf);
-    d->vf_int = NULL; d->vf_lp = NULL; d->h_vf = NULL;
-    hpa_free(d->sp_w); hpa_free(d->sp_i);
-    free(d->h_sp_w);
-    d->sp_w = NULL; d->sp_i = NULL; d->h_sp_w = NULL;
-    hpa_free(d->vt_int); hpa_free(d->vt_anc);
-    free(d->h_vt);
-    d->vt_int = NULL; d->vt_anc = NULL; d->h_vt = NULL;
-    hpa_free(d->ts_int);
-    free(d->h_ts);
-    d->ts_int = NULL; d->h_ts = NULL;
+    DecVerify* v = &d->vf;
+    for (int s = 0; s < VS_COUNT; s++)
+        if (s < VS_HOST) hpa_free(v->slab[s]);
+        else free(v->slab[s]);
+    memset(v, 0, sizeof(*v));
+}
+
+/* The verify tables for a pass of this kind: allocated on first use and again
+ * when a pass needs a kind the slabs do not hold yet (greedy chains never pay
+ * for the sampled or tree tables; nothing in them outlives a pass).  The only
+ * place that allocates and carves them.  The host slabs start zeroed: whole
+ * tables go up, used or not */
+static int dec_verify_reserve(GPT2Decode* d, int tree, int sampled) {
+    DecVerify* v = &d->vf;
+    tree |= v->tree;
+    sampled |= v->sampled;
+    if (v->slab[VS_INT] && tree == v->tree && sampled == v->sampled) return 0;
+    dec_verify_free(d);
+    VerifyLayout lay;
+    if (verify_tables_layout(d->B, tree, sampled, &lay)) return 1;
+    for (int s = 0; s < VS_COUNT; s++) {
+        const size_t bytes = lay.slab_n[s] * verify_slab_elem_bytes(s);
+        if (!bytes) continue;
+        v->slab[s] = s < VS_HOST ? hpa_malloc(bytes) : calloc(1, bytes);
+        if (!v->slab[s]) { dec_verify_free(d); return 1; }
+    }
+#define VERIFY_TABLE_CARVE(type, name) \
+    { const VerifyTable* t = &lay.t[VT_##name]; v->name = t->n ? (type*)v->slab[t->slab] + t->off : NULL; }
+    VERIFY_TABLES(VERIFY_TABLE_CARVE)
+#undef VERIFY_TABLE_CARVE
+    v->tree = tree;
+    v->sampled = sampled;
+    return 0;
 }
 
 static void dec_shard_free(GPT2Decode* d) {
@@ -1850,19 +1869,43 @@ static int dec_ensure_pages(GPT2Decode* d) {
 
 enum { G_QKV = 0, G_ATTPROJ = 1, G_FC = 2, G_FCPROJ = 3, G_LOGITS = 4 };
 
+/* The head GEMM LNf(x) . wte^T over M frag-layout rows with their 16-column
+ * statistics: what every caller shares (the decode step's logits, a dense
+ * pass's all-row logits, the SCORE chunks and the dense LOGITS chunks).  The
+ * caller adds its outputs */
+static void dec_head_gemm_desc(GPT2* model, int M, const float* x, const float* ln_stats, int epilogue,
+                               HpaFusedGemm* g) {
+    const GPT2Decode* d = model->decode;
+    memset(g, 0, sizeof(*g));
+    g->M = M;
+    g->w_dtype = wte_dtype(d);
+    g->epilogue = epilogue;
+    g->x = x;
+    g->K = model->config.channels;
+    g->ln_stats = ln_stats;
+    g->ln_ntiles = model->config.channels / 16;
+    g->ln_w = model->params.lnfw;
+    g->ln_b = model->params.lnfb;
+    g->w = wte_pack(d);
+    g->w_scale = wte_scale(d, &model->config);
+    g->N = model->config.vocab_size;
+}
+
 /* descriptor of fused GEMM `which` of layer l over the decode rows */
 static void dec_gemm_desc(GPT2* model, int l, int which, HpaFusedGemm* g) {
     GPT2Decode* d = model->decode;
     const GPT2Config c = model->config;
     const int C = c.channels, V = c.vocab_size, ct = C / 16;
-    const ParameterTensors* w = &model->params;
     const DecLayerOps o = dec_layer_ops(model, d, l);
-    memset(g, 0, sizeof(*g));
-    g->M = d->B;
-    g->w_dtype = d->w_dtype;
+    if (which == G_LOGITS) { /* logits = LNf(res) . wte^T, argmax partials */
+        dec_head_gemm_desc(model, d->B, d->res, d->st1, HPA_FEPI_LOGITS, g);
+    } else {
+        memset(g, 0, sizeof(*g));
+        g->M = d->B;
+        g->w_dtype = d->w_dtype;
+        g->epilogue = which == G_QKV ? HPA_FEPI_QKV : which == G_FC ? HPA_FEPI_GELU : HPA_FEPI_RESID;
+    }
     g->a_ws = d->mx_ws;
-    g->epilogue = which == G_QKV ? HPA_FEPI_QKV : which == G_FC ? HPA_FEPI_GELU
-                : which == G_LOGITS ? HPA_FEPI_LOGITS : HPA_FEPI_RESID;
     g->waves = d->fwaves[which];
     g->row_blocks = d->frb[which];
     g->col_tiles = d->fct[which];
@@ -1893,10 +1936,7 @@ static void dec_gemm_desc(GPT2* model, int l, int which, HpaFusedGemm* g) {
             g->bias = o.b_fp; g->out = d->res; g->res_in = d->res2;
             g->stats_out = d->d_fold && l + 1 < c.num_layers ? NULL : d->st1; /* LNf of logits: last layer */
             break;
-        default: /* logits = LNf(res) . wte^T, argmax partials */
-            g->x = d->res; g->K = C; g->ln_stats = d->st1; g->ln_ntiles = ct;
-            g->ln_w = w->lnfw; g->ln_b = w->lnfb; g->w = wte_pack(d); g->N = V;
-            g->w_scale = wte_scale(d, &c); g->w_dtype = wte_dtype(d);
+        default: /* G_LOGITS */
             g->out = d->d_logits; g->part_out = d->part; g->layer = 0;
             if (g->w_dtype == HPA_FP8) break; /* the fp8-weight kernel, shapes by hpa_fused_pick_fp8 */
             g->variant = 4; /* activation-resident kernel where the shape allows (hpa_logits.hip), */
@@ -2887,25 +2927,13 @@ static int prefill_gemm(GPT2* model, int l, int which, int R) {
  * bf16 kernels (any row count); its argmax partials go to a scratch buffer */
 static int prefill_all_logits(GPT2* model, int R, float* rows_out, const int* out_rows) {
     GPT2Decode* d = model->decode;
-    const GPT2Config c = model->config;
-    const int C = c.channels, V = c.vocab_size;
+    const int V = model->config.vocab_size;
     const size_t Rp = (size_t)(R + 15) / 16 * 16;
     float* part = (float*)hpa_malloc((size_t)(V + 15) / 16 * Rp * 2 * sizeof(float));
     if (!part) return 1;
     HpaFusedGemm g;
-    memset(&g, 0, sizeof(g));
-    g.M = R;
-    g.w_dtype = wte_dtype(d);
-    g.epilogue = HPA_FEPI_LOGITS;
-    g.x = d->pf_res;
-    g.K = C;
-    g.ln_stats = d->pf_st1; /* the last fcproj's 16-column statistics (prefill_gemm) */
-    g.ln_ntiles = C / 16;
-    g.ln_w = model->params.lnfw;
-    g.ln_b = model->params.lnfb;
-    g.w = wte_pack(d);
-    g.w_scale = wte_scale(d, &model->config);
-    g.N = V;
+    /* pf_st1: the last fcproj's 16-column statistics (prefill_gemm) */
+    dec_head_gemm_desc(model, R, d->pf_res, d->pf_st1, HPA_FEPI_LOGITS, &g);
     g.out = rows_out;
     g.row_seq = out_rows; /* LOGITS: GEMM row -> row of rows_out (NULL: the same) */
     g.part_out = part;
@@ -2961,14 +2989,25 @@ static int dec_score_reserve(GPT2* model, int rows) {
     return 0;
 }
 
+/* The chunk step of the head GEMM over rows of a dense pass of Rp padded rows:
+ * the chunk's n packed rows hrows (host) go up to sc_rows and are gathered,
+ * with their LNf statistics, out of pf_res into the chunk workspace
+ * (dec_score_reserve); g: the chunk's GEMM, ready for the caller's outputs */
+static int dec_head_chunk(GPT2* model, int Rp, const int* hrows, int n, int epilogue, HpaFusedGemm* g) {
+    GPT2Decode* d = model->decode;
+    const int np = (n + 15) / 16 * 16;
+    int rc = hpa_memcpy(d->sc_rows, hrows, n * sizeof(int));
+    rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->sc_rows, n, d->sc_x, d->sc_st, np, model->config.channels);
+    dec_head_gemm_desc(model, n, d->sc_x, d->sc_st, epilogue, g);
+    return rc;
+}
+
 /* every prefill row's log-probability and greedy id: LNf(res) . wte^T over the
- * R packed rows of pf_res in chunks, each chunk's rows gathered (with their
- * LNf statistics) into the chunk workspace, one SCORE GEMM (the log-softmax
- * epilogue: no logits stored) and one hpa_score_final */
+ * R packed rows of pf_res in chunks (dec_head_chunk), one SCORE GEMM (the
+ * log-softmax epilogue: no logits stored) and one hpa_score_final */
 static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
     GPT2Decode* d = model->decode;
-    const GPT2Config c = model->config;
-    const int C = c.channels, V = c.vocab_size;
+    const int V = model->config.vocab_size;
     const int Rp = (R + 15) / 16 * 16;
     int chunk = d->sc_chunk ? d->sc_chunk : DEC_SCORE_CHUNK;
     if (chunk > Rp) chunk = Rp;
@@ -2979,23 +3018,9 @@ static int dec_score_rows(GPT2* model, int R, const DecScore* sc) {
     for (int r0 = 0; r0 < R && !rc; r0 += chunk) {
         const int n = R - r0 < chunk ? R - r0 : chunk, np = (n + 15) / 16 * 16;
         for (int i = 0; i < n; i++) hrows[i] = r0 + i;
-        rc |= hpa_memcpy(d->sc_rows, hrows, n * sizeof(int));
-        rc |= hpa_memcpy(d->sc_tgt, (sc->d_targets ? sc->d_targets : sc->targets) + r0, n * sizeof(int));
-        rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->sc_rows, n, d->sc_x, d->sc_st, np, C);
         HpaFusedGemm g;
-        memset(&g, 0, sizeof(g));
-        g.M = n;
-        g.w_dtype = wte_dtype(d);
-        g.epilogue = HPA_FEPI_SCORE;
-        g.x = d->sc_x;
-        g.K = C;
-        g.ln_stats = d->sc_st;
-        g.ln_ntiles = C / 16;
-        g.ln_w = model->params.lnfw;
-        g.ln_b = model->params.lnfb;
-        g.w = wte_pack(d);
-        g.w_scale = wte_scale(d, &model->config);
-        g.N = V;
+        rc |= dec_head_chunk(model, Rp, hrows, n, HPA_FEPI_SCORE, &g);
+        rc |= hpa_memcpy(d->sc_tgt, (sc->d_targets ? sc->d_targets : sc->targets) + r0, n * sizeof(int));
         g.score_target = d->sc_tgt;
         g.score_part = d->sc_part;
         rc |= hpa_gemm_fused(&g);
@@ -3046,8 +3071,7 @@ static int dec_score_top_reserve(GPT2* model, int rows) {
  * from the selection kernel) and one hpa_top_logprobs with the chunk's targets */
 static int dec_score_top_rows(GPT2* model, int R, const DecScore* sc) {
     GPT2Decode* d = model->decode;
-    const GPT2Config c = model->config;
-    const int C = c.channels, V = c.vocab_size, k = sc->k;
+    const int V = model->config.vocab_size, k = sc->k;
     const int Rp = (R + 15) / 16 * 16;
     int chunk = d->sc_chunk ? d->sc_chunk : DEC_SCORE_TOP_CHUNK;
     if (chunk > Rp) chunk = Rp;
@@ -3056,25 +3080,11 @@ static int dec_score_top_rows(GPT2* model, int R, const DecScore* sc) {
     if (!hrows) return 1;
     int rc = 0;
     for (int r0 = 0; r0 < R && !rc; r0 += chunk) {
-        const int n = R - r0 < chunk ? R - r0 : chunk, np = (n + 15) / 16 * 16;
+        const int n = R - r0 < chunk ? R - r0 : chunk;
         for (int i = 0; i < n; i++) hrows[i] = r0 + i;
-        rc |= hpa_memcpy(d->sc_rows, hrows, n * sizeof(int));
-        rc |= hpa_memcpy(d->sc_tgt, sc->targets + r0, n * sizeof(int));
-        rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->sc_rows, n, d->sc_x, d->sc_st, np, C);
         HpaFusedGemm g;
-        memset(&g, 0, sizeof(g));
-        g.M = n;
-        g.w_dtype = wte_dtype(d);
-        g.epilogue = HPA_FEPI_LOGITS;
-        g.x = d->sc_x;
-        g.K = C;
-        g.ln_stats = d->sc_st;
-        g.ln_ntiles = C / 16;
-        g.ln_w = model->params.lnfw;
-        g.ln_b = model->params.lnfb;
-        g.w = wte_pack(d);
-        g.w_scale = wte_scale(d, &model->config);
-        g.N = V;
+        rc |= dec_head_chunk(model, Rp, hrows, n, HPA_FEPI_LOGITS, &g);
+        rc |= hpa_memcpy(d->sc_tgt, sc->targets + r0, n * sizeof(int));
         g.out = d->st_logits;
         g.part_out = d->sc_part; /* (V + 15) / 16 * np * 2 floats: half the SCORE partials' room */
         rc |= hpa_gemm_fused(&g);
@@ -3101,17 +3111,43 @@ static int dec_trace_fits(GPT2* model, long R) {
     return 1;
 }
 
+static inline DecRowTables dec_row_tables(const GPT2Decode* d) {
+    return (DecRowTables){d->pf_start, d->pf_start + d->B, d->pf_start + 2 * d->B};
+}
+
+/* The attention of a dense pass, decided once per pass: the MFMA prefill
+ * kernel; the few-row kernel of the verify passes (gpt2_decode_verify_plan);
+ * its tree form over the rows' ancestor masks (gpt2_decode_verify_tree).  A
+ * bf16 / fp8 pool has the few-row kernel only under request 3
+ * (hpa_paged_attention_verify_packed, both forms) */
+typedef enum { DENSE_ATTN_PREFILL = 0, DENSE_ATTN_FEW_ROWS = 1, DENSE_ATTN_FEW_ROWS_TREE = 2 } DenseAttn;
+
+static int dec_dense_attention(GPT2Decode* d, int l, int T, DenseAttn form) {
+    const DecRowTables rt = dec_row_tables(d);
+    const int f32 = d->pool.dtype == HPA_F32, B = d->B;
+    switch (form) {
+        case DENSE_ATTN_FEW_ROWS_TREE:
+            return f32 ? hpa_paged_attention_verify_tree(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
+                                                         rt.len, d->vf.anc, B, T, d->pf_att)
+                       : hpa_paged_attention_verify_packed(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
+                                                           rt.len, d->vf.anc, B, T, d->pf_att);
+        case DENSE_ATTN_FEW_ROWS:
+            return f32 ? hpa_paged_attention_verify(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0, rt.len,
+                                                    B, T, d->pf_att)
+                       : hpa_paged_attention_verify_packed(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
+                                                           rt.len, NULL, B, T, d->pf_att);
+        default:
+            return hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
+                                                      rt.len, B, T, d->pf_att);
+    }
+}
+
 /* the R packed rows of the uploaded row tables (pf_tok, pf_pos, pf_seq;
- * pf_start: start, row0, len) through the embedding and every layer; T =
- * max(len).  verify_attn: 1 the few-row kernel (gpt2_decode_verify_plan) in
- * place of the MFMA prefill kernel; 2 its tree form over the masks of vt_anc
- * (gpt2_decode_verify_tree).  A bf16 / fp8 pool has the few-row kernel only
- * under request 3 (hpa_paged_attention_verify_packed, both forms) */
-static int dec_prefill_layers(GPT2* model, int R, int T, int verify_attn) {
+ * pf_start: dec_row_tables) through the embedding and every layer; T =
+ * max(len) */
+static int dec_prefill_layers(GPT2* model, int R, int T, DenseAttn attn) {
     GPT2Decode* d = model->decode;
-    const int B = d->B, C = model->config.channels, L = model->config.num_layers;
-    const int* d_row0 = d->pf_start + B;
-    const int* d_len = d->pf_start + 2 * B;
+    const int C = model->config.channels, L = model->config.num_layers;
     const ParameterTensors* w = &model->params;
     int rc = hpa_embed_frag(d->pf_tok, d->pf_pos, w->wte, w->wpe, d->pf_res, d->pf_st1, R, C);
     /* gpt2_decode_trace_next_pass: the residual stream after the embedding and
@@ -3129,16 +3165,7 @@ static int dec_prefill_layers(GPT2* model, int R, int T, int verify_attn) {
     PF_TRACE(0);
     for (int l = 0; l < L && !rc; l++) {
         rc |= prefill_gemm(model, l, G_QKV, R);
-        rc |= verify_attn && d->pool.dtype != HPA_F32
-                  ? hpa_paged_attention_verify_packed(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
-                                                      d_len, verify_attn == 2 ? d->vt_anc : NULL, B, T, d->pf_att)
-              : verify_attn == 2
-                  ? hpa_paged_attention_verify_tree(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
-                                                    d_len, d->vt_anc, B, T, d->pf_att)
-              : verify_attn ? hpa_paged_attention_verify(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start, d_row0,
-                                                         d_len, B, T, d->pf_att)
-                            : hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, d->pf_start,
-                                                                 d_row0, d_len, B, T, d->pf_att);
+        rc |= dec_dense_attention(d, l, T, attn);
         rc |= prefill_gemm(model, l, G_ATTPROJ, R);
         rc |= prefill_gemm(model, l, G_FC, R);
         rc |= prefill_gemm(model, l, G_FCPROJ, R);
@@ -3204,12 +3231,11 @@ static int dec_prefill_rows_armed(GPT2* model, const int* tokens, const int* len
         hpa_memcpy(d->pf_seq, hs, R * sizeof(int)) || hpa_memcpy(d->pf_start, hst, 3 * (size_t)B * sizeof(int)) ||
         hpa_memcpy(d->pf_last, hl, B * sizeof(int)))
         return 1;
-    const int* d_len = d->pf_start + 2 * B;
     int rc = 0;
     if (d->proc)
         rc = hpa_token_record(d->pr_hist, d->max_ctx, d->pr_cnt, d->pr_V, B, d->pr_i, d->pf_seq, d->pf_pos, d->pf_tok,
                               (int)R);
-    rc |= dec_prefill_layers(model, (int)R, T, 0);
+    rc |= dec_prefill_layers(model, (int)R, T, DENSE_ATTN_PREFILL);
     if (all_logits && !rc) rc |= prefill_all_logits(model, (int)R, all_logits, all_rows);
     if (score && !rc) rc |= score->k ? dec_score_top_rows(model, (int)R, score) : dec_score_rows(model, (int)R, score);
     /* last row of every active sequence -> the decode rows, logits, pick; the
@@ -3218,7 +3244,7 @@ static int dec_prefill_rows_armed(GPT2* model, const int* tokens, const int* len
     rc |= hpa_memcpy(d->d_pos, hst, B * sizeof(int));
     rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->pf_last, B, d->res, d->st1, d->Mp, C);
     rc |= dec_gemm(model, 0, G_LOGITS);
-    rc |= dec_pick(model, d_len);
+    rc |= dec_pick(model, dec_row_tables(d).len);
     if (rc) return 1;
     for (int b = 0; b < B; b++) d->h_pos[b] += lens[b];
     dec_pr_note(d);
@@ -3324,114 +3350,103 @@ static int dec_compact_path(GPT2Decode* d, const int* path, const int* n_accepte
                : hpa_pool_compact_path_packed(&d->pool, d->d_bt, d->bt_stride, d->pf_start, path, n_accepted, d->B);
 }
 
-/* The dense route of the sampled verify passes: the packed rows hrows [ND]
- * (host) of the R-row pass through the route of dec_score_top_rows in chunks:
- * gather, one LOGITS GEMM into the [chunk][V] workspace, then the masses.
- * d_seq [ND] (device): the rows' sequences.  Chain (t_targets NULL): one
- * hpa_sample_filtered_prob per chunk with v_drafts as targets, masses by row.
- * Tree: one hpa_sample_filtered_prob_multi with the lists t_targets / t_n /
- * t_dst (device, gpt2_tree_dense_tables), masses scattered by draft. */
-static int dec_spec_dense(GPT2* model, int R, int ND, const int* hrows, const int* d_seq, const int* v_drafts,
-                          const int* t_targets, const int* t_n, const int* t_dst) {
+/* One verify pass: the caller's arrays, the kind of pass and, from
+ * verify_check on, its shape.  sampled: gpt2_decode_verify_sampled (draft_out:
+ * the drafts' probabilities); else gpt2_decode_verify (draft_out: their raw
+ * log-probabilities).  tree: gpt2_decode_verify_tree, and with sampled
+ * gpt2_decode_verify_tree_sampled (the internal nodes through the dense route,
+ * the multi-draft accept walk, the own token with the final node's rejected
+ * children taken out) -- the rows are tree nodes: depth positions, slot
+ * appends and ancestor masks in the layers, no SCORE targets, the accept walk,
+ * then the accepted path's K/V compacted into consecutive slots ahead of the
+ * tail; accepted_nodes (nullable): the path */
+typedef struct {
+    const int *drafts, *parents, *n_draft;
+    int *n_accepted, *out_tokens, *accepted_nodes;
+    float* draft_out;
+    int tree, sampled;
+    int R, T, ND;   /* rows, most rows of one sequence, drafts */
+    DenseAttn attn; /* the layers' attention, decided once (verify_check) */
+} VerifyPass;
+
+/* The dense route of the sampled verify passes: the n packed rows
+ * vf.h_dense_rows of the R-row pass through the route of dec_score_top_rows in
+ * chunks: gather, one LOGITS GEMM into the [chunk][V] workspace, then the
+ * masses.  vf.dense_seq [n]: the rows' sequences.  Chain: one
+ * hpa_sample_filtered_prob per chunk with the drafts as targets, masses by row.
+ * Tree: one hpa_sample_filtered_prob_multi with the lists dense_targets /
+ * dense_n / dense_dst (gpt2_tree_dense_tables), masses scattered by draft. */
+static int dec_spec_dense(GPT2* model, int R, int n_rows, int tree) {
     GPT2Decode* d = model->decode;
-    const GPT2Config c = model->config;
-    const int B = d->B, C = c.channels, V = c.vocab_size, NT = HPA_VERIFY_MAX_ROWS - 1;
-    const int Rp = (R + 15) / 16 * 16, NDp = (ND + 15) / 16 * 16;
+    const DecVerify* v = &d->vf;
+    const int V = model->config.vocab_size, NT = HPA_VERIFY_MAX_ROWS - 1;
+    const int Rp = (R + 15) / 16 * 16, NDp = (n_rows + 15) / 16 * 16;
     int chunk = d->sc_chunk ? d->sc_chunk : DEC_SCORE_TOP_CHUNK;
     if (chunk > NDp) chunk = NDp;
     if (dec_score_reserve(model, chunk) || dec_score_top_reserve(model, chunk)) return 1;
     int rc = 0;
-    unsigned long long *w_target = d->sp_w, *w_total = d->sp_w + (size_t)B * (HPA_VERIFY_MAX_ROWS - 1);
-    for (int r0 = 0; r0 < ND && !rc; r0 += chunk) {
-        const int n = ND - r0 < chunk ? ND - r0 : chunk, np = (n + 15) / 16 * 16;
-        rc |= hpa_memcpy(d->sc_rows, hrows + r0, n * sizeof(int));
-        rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->sc_rows, n, d->sc_x, d->sc_st, np, C);
+    for (int r0 = 0; r0 < n_rows && !rc; r0 += chunk) {
+        const int n = n_rows - r0 < chunk ? n_rows - r0 : chunk;
         HpaFusedGemm g;
-        memset(&g, 0, sizeof(g));
-        g.M = n;
-        g.w_dtype = wte_dtype(d);
-        g.epilogue = HPA_FEPI_LOGITS;
-        g.x = d->sc_x;
-        g.K = C;
-        g.ln_stats = d->sc_st;
-        g.ln_ntiles = C / 16;
-        g.ln_w = model->params.lnfw;
-        g.ln_b = model->params.lnfb;
-        g.w = wte_pack(d);
-        g.w_scale = wte_scale(d, &model->config);
-        g.N = V;
+        rc |= dec_head_chunk(model, Rp, &v->h_dense_rows[r0], n, HPA_FEPI_LOGITS, &g);
         g.out = d->st_logits;
         g.part_out = d->sc_part; /* not read (dec_score_top_rows) */
         rc |= hpa_gemm_fused(&g);
-        if (!rc && t_targets)
-            rc |= hpa_sample_filtered_prob_multi(d->st_logits, n, V, d_seq + r0, d->d_samp_t, d->d_samp_k, d->d_samp_p,
-                                                 t_targets + (size_t)r0 * NT, t_n + r0, t_dst + (size_t)r0 * NT, NULL,
-                                                 NULL, w_target, w_total);
+        if (!rc && tree)
+            rc |= hpa_sample_filtered_prob_multi(d->st_logits, n, V, &v->dense_seq[r0], d->d_samp_t, d->d_samp_k,
+                                                 d->d_samp_p, &v->dense_targets[(size_t)r0 * NT], &v->dense_n[r0],
+                                                 &v->dense_dst[(size_t)r0 * NT], NULL, NULL, v->w_target, v->w_total);
         else if (!rc)
-            rc |= hpa_sample_filtered_prob(d->st_logits, n, V, d_seq + r0, d->d_samp_t, d->d_samp_k, d->d_samp_p,
-                                           v_drafts + r0, NULL, NULL, w_target + r0, w_total + r0);
+            rc |= hpa_sample_filtered_prob(d->st_logits, n, V, &v->dense_seq[r0], d->d_samp_t, d->d_samp_k, d->d_samp_p,
+                                           &v->drafts[r0], NULL, NULL, &v->w_target[r0], &v->w_total[r0]);
     }
     return rc;
 }
 
 /* the drafted rows' masses under mode 2 (gpt2_decode_verify_sampled): the ND
  * drafted rows through the dense route.  Drafted row draft0[b] + i is packed
- * row row0[b] + i; hrow0 / hlen: the host row tables */
-static int dec_spec_rows(GPT2* model, int R, int ND, const int* hrow0, const int* hlen, const int* v_drafts) {
+ * row row0[b] + i */
+static int dec_spec_rows(GPT2* model, const VerifyPass* p) {
     GPT2Decode* d = model->decode;
-    const int B = d->B;
-    int* hrows = (int*)malloc(2 * (size_t)ND * sizeof(int));
-    if (!hrows) return 1;
-    int* hseq = hrows + ND;
+    const DecVerify* v = &d->vf;
     int nd = 0;
-    for (int b = 0; b < B; b++)
-        for (int i = 0; i + 1 < hlen[b]; i++, nd++) {
-            hrows[nd] = hrow0[b] + i;
-            hseq[nd] = b;
+    for (int b = 0; b < d->B; b++)
+        for (int i = 0; i + 1 < v->h_len[b]; i++, nd++) {
+            v->h_dense_rows[nd] = v->h_row0[b] + i;
+            v->h_dense_seq[nd] = b;
         }
-    int rc = hpa_memcpy(d->sp_i, hseq, (size_t)ND * sizeof(int));
-    if (!rc) rc = dec_spec_dense(model, R, ND, hrows, d->sp_i, v_drafts, NULL, NULL, NULL);
-    free(hrows);
-    return rc;
+    if (hpa_memcpy(v->dense_seq, v->h_dense_seq, (size_t)p->ND * sizeof(int))) return 1;
+    return dec_spec_dense(model, p->R, p->ND, 0);
 }
 
 /* the drafts' masses of a sampled tree pass (gpt2_decode_verify_tree_sampled):
  * the internal nodes, once each, through the dense route; every draft's mass
  * at its parent's row and that row's total land at the draft's packed index */
-static int dec_spec_tree_rows(GPT2* model, int R, const int* hrow0, const int* drafts, const int* parents,
-                              const int* n_draft) {
+static int dec_spec_tree_rows(GPT2* model, const VerifyPass* p) {
     GPT2Decode* d = model->decode;
+    const DecVerify* v = &d->vf;
     const size_t BD = (size_t)d->B * (HPA_VERIFY_MAX_ROWS - 1), NT = HPA_VERIFY_MAX_ROWS - 1;
-    int *hrows = d->h_ts, *hseq = hrows + BD, *hnt = hseq + BD, *htg = hnt + BD, *hdst = htg + NT * BD;
-    const int NI = gpt2_tree_dense_tables(drafts, parents, n_draft, d->B, hrow0, hrows, hseq, htg, hnt, hdst);
+    const int NI = gpt2_tree_dense_tables(p->drafts, p->parents, p->n_draft, d->B, v->h_row0, v->h_dense_rows,
+                                          v->h_dense_seq, v->h_dense_targets, v->h_dense_n, v->h_dense_dst);
     if (NI <= 0) return NI < 0;
-    int *t_seq = d->ts_int, *t_n = t_seq + BD, *t_tg = t_n + BD, *t_dst = t_tg + NT * BD;
-    if (hpa_memcpy(t_seq, hseq, (2 + 2 * NT) * BD * sizeof(int))) return 1;
-    return dec_spec_dense(model, R, NI, hrows, t_seq, NULL, t_tg, t_n, t_dst);
+    /* seq, n, targets, dst: neighbours on both sides, one copy */
+    if (hpa_memcpy(v->dense_seq, v->h_dense_seq, (2 + 2 * NT) * BD * sizeof(int))) return 1;
+    return dec_spec_dense(model, p->R, NI, 1);
 }
 
-/* sampled: gpt2_decode_verify_sampled (draft_out: the drafts' probabilities);
- * else gpt2_decode_verify (draft_out: their raw log-probabilities).
- * parents != NULL: gpt2_decode_verify_tree, and with sampled
- * gpt2_decode_verify_tree_sampled (the internal nodes through the dense route,
- * the multi-draft accept walk, the own token with the final node's rejected
- * children taken out) -- the rows are tree
- * nodes: depth positions, slot appends and ancestor masks in the layers, no
- * SCORE targets, the accept walk, then the accepted path's K/V compacted into
- * consecutive slots ahead of the tail; accepted_nodes (nullable): the path */
-static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, const int* n_draft, int* n_accepted,
-                            int* out_tokens, float* draft_logprobs, int sampled, int* accepted_nodes) {
-    GPT2Decode* d = model->decode;
-    if (!n_draft || !n_accepted || !out_tokens) return 1;
-    const int tree = parents != NULL;
-    if (sampled && d->sample != 2) {
+/* every refusal of a verify pass, made before anything changes; on success
+ * the pass's shape and attention are set (R = 0: nothing to run) */
+static int verify_check(GPT2* model, VerifyPass* p) {
+    const GPT2Decode* d = model->decode;
+    if (!p->n_draft || !p->n_accepted || !p->out_tokens) return 1;
+    if (p->sampled && d->sample != 2) {
         fprintf(stderr, "[paged_infer] verify_sampled: sampling mode 2 only (mode %d is on%s)\n", d->sample,
                 d->sample ? ": its float sampler has no integer masses"
-                : tree    ? ": gpt2_decode_verify_tree is the greedy pass"
+                : p->tree ? ": gpt2_decode_verify_tree is the greedy pass"
                           : ": gpt2_decode_verify is the greedy pass");
         return 1;
     }
-    if (!sampled && d->sample) {
+    if (!p->sampled && d->sample) {
         fprintf(stderr, "[paged_infer] verify: greedy decoding only (sampling mode %d is on)\n", d->sample);
         return 1;
     }
@@ -3440,235 +3455,225 @@ static int dec_verify_armed(GPT2* model, const int* drafts, const int* parents, 
                         "per-row counts)\n");
         return 1;
     }
-    const GPT2Config c = model->config;
-    const int B = d->B, C = c.channels, MR = HPA_VERIFY_MAX_ROWS;
-    int R = 0, T = 0, ND = 0;
-    for (int b = 0; b < B; b++) {
-        if (n_draft[b] < -1 || n_draft[b] > MR - 1) {
-            fprintf(stderr, "[paged_infer] verify: n_draft[%d] = %d is outside [-1, %d]\n", b, n_draft[b], MR - 1);
+    const int V = model->config.vocab_size;
+    VerifyDrafts e;
+    switch (verify_drafts_check(p->drafts, p->parents, p->n_draft, d->B, V, d->h_pos, d->max_ctx, &e)) {
+        case VERIFY_OK: break;
+        case VERIFY_BAD_N_DRAFT:
+            fprintf(stderr, "[paged_infer] verify: n_draft[%d] = %d is outside [-1, %d]\n", e.seq, e.value,
+                    HPA_VERIFY_MAX_ROWS - 1);
             return 1;
-        }
-        if (d->h_pos[b] + n_draft[b] + 1 > d->max_ctx) {
-            fprintf(stderr, "[paged_infer] verify: %d drafts overflow sequence %d\n", n_draft[b], b);
+        case VERIFY_OVERFLOW:
+            fprintf(stderr, "[paged_infer] verify: %d drafts overflow sequence %d\n", e.value, e.seq);
             return 1;
-        }
-        R += n_draft[b] + 1;
-        if (n_draft[b] > 0) ND += n_draft[b];
-        if (n_draft[b] + 1 > T) T = n_draft[b] + 1;
-    }
-    if (ND && !drafts) return 1;
-    for (int i = 0; i < ND; i++)
-        if (drafts[i] < 0 || drafts[i] >= c.vocab_size) {
-            fprintf(stderr, "[paged_infer] verify: draft %d (%d) is outside [0, %d)\n", i, drafts[i], c.vocab_size);
+        case VERIFY_BAD_DRAFT:
+            fprintf(stderr, "[paged_infer] verify: draft %d (%d) is outside [0, %d)\n", e.i, e.value, V);
             return 1;
-        }
-    if (tree) { /* draft j of a sequence is node j + 1: its parent a node in [0, j], no sibling with its token */
-        for (int b = 0, nd = 0; b < B; nd += n_draft[b] > 0 ? n_draft[b] : 0, b++)
-            for (int j = 0; j < n_draft[b]; j++) {
-                const int pj = parents[nd + j];
-                if (pj < 0 || pj > j) {
-                    fprintf(stderr, "[paged_infer] verify_tree: parent %d of draft %d of sequence %d is outside [0, %d]\n",
-                            pj, j, b, j);
-                    return 1;
-                }
-                for (int i = 0; i < j; i++)
-                    if (parents[nd + i] == pj && drafts[nd + i] == drafts[nd + j]) {
-                        fprintf(stderr, "[paged_infer] verify_tree: drafts %d and %d of sequence %d are siblings with the "
-                                        "same token\n", i, j, b);
-                        return 1;
-                    }
-            }
+        case VERIFY_BAD_PARENT:
+            fprintf(stderr, "[paged_infer] verify_tree: parent %d of draft %d of sequence %d is outside [0, %d]\n",
+                    e.value, e.j, e.seq, e.j);
+            return 1;
+        case VERIFY_SAME_SIBLINGS:
+            fprintf(stderr, "[paged_infer] verify_tree: drafts %d and %d of sequence %d are siblings with the same "
+                            "token\n", e.i, e.j, e.seq);
+            return 1;
+        default: return 1; /* VERIFY_NO_DRAFTS */
     }
-    if (R == 0) {
-        for (int b = 0; b < B; b++) n_accepted[b] = -1;
-        return 0;
-    }
+    p->R = e.R;
+    p->T = e.T;
+    p->ND = e.ND;
+    if (p->R == 0) return 0;
     /* a tree pass needs the few-row kernel whatever the request (the prefill kernel has no tree mask); a bf16 /
      * fp8 pool has it under request 3 only */
-    if (tree && gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request == 3 ? 3 : 0) != 1) {
+    if (p->tree &&
+        gpt2_decode_verify_plan(p->T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request == 3 ? 3 : 0) != 1) {
         fprintf(stderr, "[paged_infer] verify_tree: fp32 KV pool, head size 64, page size 8 / 16 / 32 / 64 only (the "
                         "prefill kernel of the other pools has no tree mask); bf16 and fp8 pools after "
                         "gpt2_decode_set_verify_attention(model, 3)\n");
         return 1;
     }
-    if (dec_trace_fits(model, R)) return 1;
-    /* tables: drafts [B * (MR - 1)], draft0 [B], accepted [B], targets [B * MR], greedy ids [B * MR] */
-    const size_t n_int = (size_t)B * (MR - 1) + 2 * (size_t)B + 2 * (size_t)B * MR;
-    if (!d->vf_int) {
-        d->vf_int = (int*)hpa_malloc(n_int * sizeof(int));
-        d->vf_lp = (float*)hpa_malloc((size_t)B * MR * sizeof(float));
-        d->h_vf = (int*)malloc((n_int + 4 * (size_t)B) * sizeof(int));
-        if (!d->vf_int || !d->vf_lp || !d->h_vf) { dec_verify_free(d); return 1; }
-    }
-    if (sampled && !d->sp_w) {
-        d->sp_w = (unsigned long long*)hpa_malloc(2 * (size_t)B * (MR - 1) * sizeof(unsigned long long));
-        d->sp_i = (int*)hpa_malloc(((size_t)B * (MR - 1) + B) * sizeof(int));
-        d->h_sp_w = (unsigned long long*)malloc(2 * (size_t)B * (MR - 1) * sizeof(unsigned long long));
-        if (!d->sp_w || !d->sp_i || !d->h_sp_w) { dec_verify_free(d); return 1; }
-    }
-    if (tree && sampled && !d->ts_int) {
-        const size_t BD = (size_t)B * (MR - 1);
-        d->ts_int = (int*)hpa_malloc(((2 + 2 * (MR - 1)) * BD + (size_t)B * (MR - 1) + B) * sizeof(int));
-        d->h_ts = (int*)calloc((3 + 2 * (MR - 1)) * BD, sizeof(int));
-        if (!d->ts_int || !d->h_ts) { dec_verify_free(d); return 1; }
-    }
-    if (tree && !d->vt_int) {
-        d->vt_int = (int*)hpa_malloc((2 * (size_t)B * (MR - 1) + B + 2 * (size_t)B * MR) * sizeof(int));
-        d->vt_anc = (unsigned char*)hpa_malloc((size_t)B * MR);
-        d->h_vt = (int*)malloc((2 * (size_t)B * (MR - 1) + B + (size_t)B * MR) * sizeof(int));
-        if (!d->vt_int || !d->vt_anc || !d->h_vt) { dec_verify_free(d); return 1; }
-    }
-    int* sp_excl = sampled ? d->sp_i + (size_t)B * (MR - 1) : NULL;
-    int* sp_nexcl = NULL; /* a sampled tree pass: the lists of hpa_spec_tree_accept */
-    if (sampled && tree) {
-        sp_excl = d->ts_int + (2 + 2 * (size_t)(MR - 1)) * B * (MR - 1);
-        sp_nexcl = sp_excl + (size_t)B * (MR - 1);
-    }
-    int *v_drafts = d->vf_int, *v_d0 = v_drafts + (size_t)B * (MR - 1), *v_acc = v_d0 + B, *v_tgt = v_acc + B,
-        *v_top = v_tgt + (size_t)B * MR;
-    int *hst = d->h_vf, *hr0 = hst + B, *hln = hr0 + B, *hd0 = hln + B, *hacc = hd0 + B;
-    float* hlp = (float*)(hacc + B); /* [B * MR]: fits the n_int tail */
-    /* a tree pass keeps drafts beside parents and the accepted counts beside the path: one copy each way */
-    int *t_par = NULL, *t_path = NULL, *t_slot = NULL, *h_tpath = NULL;
-    if (tree) {
-        v_drafts = d->vt_int;
-        t_par = v_drafts + (size_t)B * (MR - 1);
-        v_acc = t_par + (size_t)B * (MR - 1);
-        t_path = v_acc + B;
-        t_slot = t_path + (size_t)B * MR;
-        hacc = d->h_vt + 2 * (size_t)B * (MR - 1);
-        h_tpath = hacc + B;
-    }
-    for (int b = 0; b < B; b++) hln[b] = n_draft[b] + 1;
+    p->attn = p->tree ? DENSE_ATTN_FEW_ROWS_TREE
+            : gpt2_decode_verify_plan(p->T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request)
+                ? DENSE_ATTN_FEW_ROWS
+                : DENSE_ATTN_PREFILL;
+    return dec_trace_fits(model, p->R);
+}
+
+/* pages, workspaces and the pass's row tables on the device: the dense pass's
+ * (hpa_verify_rows / hpa_verify_tree_rows fill them from the drafts) and the
+ * verify tables' */
+static int verify_rows(GPT2* model, const VerifyPass* p) {
+    GPT2Decode* d = model->decode;
+    const int B = d->B, ND = p->ND;
+    if (dec_verify_reserve(d, p->tree, p->sampled)) return 1;
+    const DecVerify* v = &d->vf;
+    for (int b = 0; b < B; b++) v->h_len[b] = p->n_draft[b] + 1;
     for (int b = 0; b < B; b++)
-        if (hln[b] > 0 && dec_grow(d, b, hln[b], hln, NULL)) return 1;
+        if (v->h_len[b] > 0 && dec_grow(d, b, v->h_len[b], v->h_len, NULL)) return 1;
     if (dec_sync_block_table(d)) return 1;
-    if (dec_prefill_reserve(model, R)) return 1;
+    if (dec_prefill_reserve(model, p->R)) return 1;
     int r = 0, nd = 0;
     for (int b = 0; b < B; b++) {
-        hst[b] = d->h_pos[b];
-        hr0[b] = r;
-        hd0[b] = nd;
-        r += hln[b];
-        if (n_draft[b] > 0) nd += n_draft[b];
+        v->h_start[b] = d->h_pos[b];
+        v->h_row0[b] = r;
+        v->h_draft0[b] = nd;
+        r += v->h_len[b];
+        if (p->n_draft[b] > 0) nd += p->n_draft[b];
     }
-    if (hpa_memcpy(d->pf_start, hst, 3 * (size_t)B * sizeof(int)) || hpa_memcpy(v_d0, hd0, B * sizeof(int)) ||
-        (ND && !tree && hpa_memcpy(v_drafts, drafts, (size_t)ND * sizeof(int))))
+    /* h_start, h_row0, h_len are neighbours as start, row0, len of pf_start are */
+    if (hpa_memcpy(d->pf_start, v->h_start, 3 * (size_t)B * sizeof(int)) ||
+        hpa_memcpy(v->draft0, v->h_draft0, B * sizeof(int)) ||
+        (ND && !p->tree && hpa_memcpy(v->drafts, p->drafts, (size_t)ND * sizeof(int))))
         return 1;
-    if (tree && ND) { /* drafts [ND] and, from B * (MR - 1) on, parents [ND] */
-        memcpy(d->h_vt, drafts, (size_t)ND * sizeof(int));
-        memcpy(d->h_vt + (size_t)B * (MR - 1), parents, (size_t)ND * sizeof(int));
-        if (hpa_memcpy(v_drafts, d->h_vt, ((size_t)B * (MR - 1) + ND) * sizeof(int))) return 1;
+    if (p->tree && ND) { /* drafts beside parents on both sides: one copy, up to the last parent */
+        memcpy(v->h_drafts, p->drafts, (size_t)ND * sizeof(int));
+        memcpy(v->h_parents, p->parents, (size_t)ND * sizeof(int));
+        if (hpa_memcpy(v->drafts, v->h_drafts, ((size_t)B * (HPA_VERIFY_MAX_ROWS - 1) + ND) * sizeof(int))) return 1;
     }
-    const int* d_row0 = d->pf_start + B;
-    const int* d_len = d->pf_start + 2 * B;
-    const int Rp = (R + 15) / 16 * 16;
-    int rc;
-    if (tree) { /* no row has a single target: the SCORE GEMM (greedy) runs with -1 throughout */
-        rc = hpa_verify_tree_rows(d->d_next, v_drafts, t_par, v_d0, d->pf_start, d_row0, d_len, B, d->pf_tok, d->pf_pos,
-                                  d->pf_seq, t_slot, d->vt_anc) ||
-             (!sampled && hpa_memset_async(v_tgt, 0xFF, (size_t)R * sizeof(int)));
-        d->pf_slot = t_slot;
-        if (!rc) rc = dec_prefill_layers(model, R, T, 2);
-        d->pf_slot = NULL;
-    } else {
-        rc = hpa_verify_rows(d->d_next, v_drafts, v_d0, d->pf_start, d_row0, d_len, B, d->pf_tok, d->pf_pos, d->pf_seq,
-                             v_tgt);
-        if (!rc)
-            rc = dec_prefill_layers(model, R, T,
-                                    gpt2_decode_verify_plan(T, d->pool.dtype, d->P, d->pool.head_size, d->vf_request));
+    const DecRowTables rt = dec_row_tables(d);
+    if (!p->tree)
+        return hpa_verify_rows(d->d_next, v->drafts, v->draft0, rt.start, rt.row0, rt.len, B, d->pf_tok, d->pf_pos,
+                               d->pf_seq, v->targets);
+    /* no row of a tree has a single target: the SCORE GEMM (greedy) runs with -1 throughout */
+    return hpa_verify_tree_rows(d->d_next, v->drafts, v->parents, v->draft0, rt.start, rt.row0, rt.len, B, d->pf_tok,
+                                d->pf_pos, d->pf_seq, v->slot, v->anc) ||
+           (!p->sampled && hpa_memset_async(v->targets, 0xFF, (size_t)p->R * sizeof(int)));
+}
+
+static int verify_layers(GPT2* model, const VerifyPass* p) {
+    GPT2Decode* d = model->decode;
+    if (p->tree) d->pf_slot = d->vf.slot;
+    const int rc = dec_prefill_layers(model, p->R, p->T, p->attn);
+    d->pf_slot = NULL;
+    return rc;
+}
+
+/* the accept decision on the device: accepted [B] (a tree: and the path,
+ * compacted into consecutive K/V slots), the continuation rows pf_last, the
+ * positions; sampled: what the pick must leave out */
+static int verify_accept(GPT2* model, const VerifyPass* p) {
+    GPT2Decode* d = model->decode;
+    const DecVerify* v = &d->vf;
+    const DecRowTables rt = dec_row_tables(d);
+    const int B = d->B;
+    if (!p->sampled) { /* every row's greedy id: SCORE, no dense logits */
+        const DecScore sc = {NULL, NULL, NULL, v->targets, v->lp, v->top, 0, NULL, NULL};
+        if (dec_score_rows(model, p->R, &sc)) return 1;
     }
-    /* the accepted row of every live sequence -> the decode rows, logits, pick
-     * (which advances pos by one from start + accepted) */
-    if (sampled && tree) {
-        if (!rc && ND) rc = dec_spec_tree_rows(model, R, hr0, drafts, parents, n_draft);
-        rc |= hpa_spec_tree_accept(d->sp_w, d->sp_w + (size_t)B * (MR - 1), v_drafts, t_par, v_d0, d->pf_start, d_row0,
-                                   d_len, B, d->d_rng, v_acc, t_path, d->pf_last, sp_excl, sp_nexcl, d->d_pos);
-        rc |= dec_compact_path(d, t_path, v_acc);
-    } else if (sampled) {
-        if (!rc && ND) rc = dec_spec_rows(model, R, ND, hr0, hln, v_drafts);
-        rc |= hpa_spec_accept(d->sp_w, d->sp_w + (size_t)B * (MR - 1), v_drafts, v_d0, d->pf_start, d_row0, d_len, B,
-                              d->d_rng, v_acc, d->pf_last, sp_excl, d->d_pos);
-    } else {
-        const DecScore sc = {NULL, NULL, NULL, v_tgt, d->vf_lp, v_top, 0, NULL, NULL};
-        if (!rc) rc = dec_score_rows(model, R, &sc);
-        if (tree) {
-            rc |= hpa_verify_tree_accept(d->pf_tok, v_top, t_par, v_d0, d->pf_start, d_row0, d_len, B, v_acc, t_path,
-                                         d->pf_last, d->d_pos);
-            rc |= dec_compact_path(d, t_path, v_acc);
-        } else {
-            rc |= hpa_verify_accept(d->pf_tok, v_top, d->pf_start, d_row0, d_len, B, v_acc, d->pf_last, d->d_pos);
-        }
+    switch (2 * p->tree + p->sampled) {
+        case 0:
+            return hpa_verify_accept(d->pf_tok, v->top, rt.start, rt.row0, rt.len, B, v->accepted, d->pf_last, d->d_pos);
+        case 1:
+            if (p->ND && dec_spec_rows(model, p)) return 1;
+            return hpa_spec_accept(v->w_target, v->w_total, v->drafts, v->draft0, rt.start, rt.row0, rt.len, B, d->d_rng,
+                                   v->accepted, d->pf_last, v->exclude, d->d_pos);
+        case 2:
+            return hpa_verify_tree_accept(d->pf_tok, v->top, v->parents, v->draft0, rt.start, rt.row0, rt.len, B,
+                                          v->accepted, v->path, d->pf_last, d->d_pos) ||
+                   dec_compact_path(d, v->path, v->accepted);
+        default:
+            if (p->ND && dec_spec_tree_rows(model, p)) return 1;
+            return hpa_spec_tree_accept(v->w_target, v->w_total, v->drafts, v->parents, v->draft0, rt.start, rt.row0,
+                                        rt.len, B, d->d_rng, v->accepted, v->path, d->pf_last, v->exclude, v->n_exclude,
+                                        d->d_pos) ||
+                   dec_compact_path(d, v->path, v->accepted);
     }
-    rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->pf_last, B, d->res, d->st1, d->Mp, C);
+}
+
+/* the accepted row of every live sequence -> the decode rows, logits, pick
+ * (which advances pos by one from start + accepted) */
+static int verify_tail(GPT2* model, const VerifyPass* p) {
+    GPT2Decode* d = model->decode;
+    const int Rp = (p->R + 15) / 16 * 16;
+    int rc = hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->pf_last, d->B, d->res, d->st1, d->Mp,
+                                  model->config.channels);
     rc |= dec_gemm(model, 0, G_LOGITS);
-    rc |= dec_pick_ex(model, d_len, sp_excl, sp_nexcl);
-    if (rc) return 1;
-    if (hpa_memcpy(hacc, v_acc, (tree ? B + (size_t)B * MR : (size_t)B) * sizeof(int)) ||
+    rc |= dec_pick_ex(model, dec_row_tables(d).len, p->sampled ? d->vf.exclude : NULL,
+                      p->sampled && p->tree ? d->vf.n_exclude : NULL); /* a sampled tree: lists */
+    return rc;
+}
+
+/* the results down (accepted beside the path, w_target beside w_total: one
+ * copy each) and out to the caller; the host positions advance */
+static int verify_readback(GPT2* model, const VerifyPass* p) {
+    GPT2Decode* d = model->decode;
+    const DecVerify* v = &d->vf;
+    const int B = d->B, MR = HPA_VERIFY_MAX_ROWS;
+    if (hpa_memcpy(v->h_accepted, v->accepted, (p->tree ? B + (size_t)B * MR : (size_t)B) * sizeof(int)) ||
         hpa_memcpy(d->h_next, d->d_next, B * sizeof(int)) ||
-        (!sampled && draft_logprobs && hpa_memcpy(hlp, d->vf_lp, (size_t)R * sizeof(float))) ||
-        (sampled && draft_logprobs && ND &&
-         hpa_memcpy(d->h_sp_w, d->sp_w, 2 * (size_t)B * (MR - 1) * sizeof(unsigned long long))))
+        (!p->sampled && p->draft_out && hpa_memcpy(v->h_lp, v->lp, (size_t)p->R * sizeof(float))) ||
+        (p->sampled && p->draft_out && p->ND &&
+         hpa_memcpy(v->h_w_target, v->w_target, 2 * (size_t)B * (MR - 1) * sizeof(unsigned long long))))
         return 1;
     for (int b = 0; b < B; b++) {
-        n_accepted[b] = hacc[b];
-        if (hln[b] <= 0) continue;
-        const int a = hacc[b];
-        if (a < 0 || a > n_draft[b]) return 1;
+        p->n_accepted[b] = v->h_accepted[b];
+        if (v->h_len[b] <= 0) continue;
+        const int a = v->h_accepted[b], n = p->n_draft[b], d0 = v->h_draft0[b];
+        if (a < 0 || a > n) return 1;
         for (int i = 0; i < a; i++) {
-            const int node = tree ? h_tpath[b * MR + i] : i + 1; /* draft node - 1 */
-            if (node < 1 || node > n_draft[b]) return 1;
-            out_tokens[b * MR + i] = drafts[hd0[b] + node - 1];
-            if (accepted_nodes) accepted_nodes[b * MR + i] = node;
+            const int node = p->tree ? v->h_path[b * MR + i] : i + 1; /* draft node - 1 */
+            if (node < 1 || node > n) return 1;
+            p->out_tokens[b * MR + i] = p->drafts[d0 + node - 1];
+            if (p->accepted_nodes) p->accepted_nodes[b * MR + i] = node;
         }
-        out_tokens[b * MR + a] = d->h_next[b];
-        for (int i = 0; draft_logprobs && i < n_draft[b]; i++)
-            draft_logprobs[b * MR + i] =
-                sampled ? (float)((double)d->h_sp_w[hd0[b] + i] / (double)d->h_sp_w[(size_t)B * (MR - 1) + hd0[b] + i])
-                        : hlp[hr0[b] + i];
+        p->out_tokens[b * MR + a] = d->h_next[b];
+        for (int i = 0; p->draft_out && i < n; i++)
+            p->draft_out[b * MR + i] = p->sampled ? (float)((double)v->h_w_target[d0 + i] / (double)v->h_w_total[d0 + i])
+                                                  : v->h_lp[v->h_row0[b] + i];
         d->h_pos[b] += a + 1;
     }
     return hpa_synchronize();
 }
 
+static int dec_verify_armed(GPT2* model, VerifyPass* p) {
+    if (verify_check(model, p)) return 1;
+    if (p->R == 0) {
+        for (int b = 0; b < model->decode->B; b++) p->n_accepted[b] = -1;
+        return 0;
+    }
+    if (verify_rows(model, p) || verify_layers(model, p) || verify_accept(model, p) || verify_tail(model, p)) return 1;
+    return verify_readback(model, p);
+}
+
+/* the front of the four entry points; a tree call without a single draft
+ * needs no parents */
+static int dec_verify(GPT2* model, VerifyPass p) {
+    static const int no_parents[1] = {0};
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (p.tree && !p.parents) {
+        for (int b = 0; p.n_draft && b < d->B; b++)
+            if (p.n_draft[b] > 0) return dec_trace_disarm(d, 1);
+        p.parents = no_parents;
+    }
+    return dec_trace_disarm(d, dec_verify_armed(model, &p));
+}
+
 int gpt2_decode_verify(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
                        float* draft_logprobs) {
-    GPT2Decode* d = model->decode;
-    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    return dec_trace_disarm(d, dec_verify_armed(model, drafts, NULL, n_draft, n_accepted, out_tokens, draft_logprobs, 0,
-                                                NULL));
-}
-
-static const int no_parents[1] = {0}; /* a tree call without a single draft */
-
-int gpt2_decode_verify_tree(GPT2* model, const int* drafts, const int* parents, const int* n_draft, int* n_accepted,
-                            int* out_tokens, int* accepted_nodes) {
-    GPT2Decode* d = model ? model->decode : NULL;
-    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    int any = 0;
-    for (int b = 0; n_draft && b < d->B; b++) any |= n_draft[b] > 0;
-    if (any && !parents) return dec_trace_disarm(d, 1);
-    return dec_trace_disarm(d, dec_verify_armed(model, drafts, parents ? parents : no_parents, n_draft, n_accepted,
-                                                out_tokens, NULL, 0, accepted_nodes));
-}
-
-int gpt2_decode_verify_tree_sampled(GPT2* model, const int* drafts, const int* parents, const int* n_draft,
-                                    int* n_accepted, int* out_tokens, int* accepted_nodes, float* draft_probs) {
-    GPT2Decode* d = model ? model->decode : NULL;
-    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    int any = 0;
-    for (int b = 0; n_draft && b < d->B; b++) any |= n_draft[b] > 0;
-    if (any && !parents) return dec_trace_disarm(d, 1);
-    return dec_trace_disarm(d, dec_verify_armed(model, drafts, parents ? parents : no_parents, n_draft, n_accepted,
-                                                out_tokens, draft_probs, 1, accepted_nodes));
+    return dec_verify(model, (VerifyPass){.drafts = drafts, .n_draft = n_draft, .n_accepted = n_accepted,
+                                          .out_tokens = out_tokens, .draft_out = draft_logprobs});
 }
 
 int gpt2_decode_verify_sampled(GPT2* model, const int* drafts, const int* n_draft, int* n_accepted, int* out_tokens,
                                float* draft_probs) {
-    GPT2Decode* d = model ? model->decode : NULL;
-    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    return dec_trace_disarm(d, dec_verify_armed(model, drafts, NULL, n_draft, n_accepted, out_tokens, draft_probs, 1,
-                                                NULL));
+    return dec_verify(model, (VerifyPass){.drafts = drafts, .n_draft = n_draft, .n_accepted = n_accepted,
+                                          .out_tokens = out_tokens, .draft_out = draft_probs, .sampled = 1});
+}
+
+int gpt2_decode_verify_tree(GPT2* model, const int* drafts, const int* parents, const int* n_draft, int* n_accepted,
+                            int* out_tokens, int* accepted_nodes) {
+    return dec_verify(model, (VerifyPass){.drafts = drafts, .parents = parents, .n_draft = n_draft,
+                                          .n_accepted = n_accepted, .out_tokens = out_tokens,
+                                          .accepted_nodes = accepted_nodes, .tree = 1});
+}
+
+int gpt2_decode_verify_tree_sampled(GPT2* model, const int* drafts, const int* parents, const int* n_draft,
+                                    int* n_accepted, int* out_tokens, int* accepted_nodes, float* draft_probs) {
+    return dec_verify(model, (VerifyPass){.drafts = drafts, .parents = parents, .n_draft = n_draft,
+                                          .n_accepted = n_accepted, .out_tokens = out_tokens,
+                                          .accepted_nodes = accepted_nodes, .draft_out = draft_probs, .tree = 1,
+                                          .sampled = 1});
 }
 
 int gpt2_decode_release(GPT2* model, int seq) {
