@@ -82,6 +82,9 @@
  *     (gpt2_decode_unpark), where it continues as if it had never left: the
  *     text and the ids are those of the run without the flag, sampled runs
  *     included (the sampler state travels).  Not with --speculate.
+ *     --prefill-attention N (0 or 1): gpt2_decode_set_prefill_attention.  1 runs
+ *     the dense passes' attention on the bf16 matrix pipe where the KV pool is
+ *     bf16 or fp8 (gpt2_decode_prefill_plan); an fp32 pool runs as without it.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -131,6 +134,7 @@ int main(int argc, char** argv) {
     int B = 4, prompt_len = 32, new_tokens = 32, greedy = 0, quiet = 0, filtered = 0, top_k = 0;
     int perplexity = 0, logprobs = 0, speculate = 0, spec_sampled = 0, top_lp = 0;
     int spec_tree = 0, spec_chain = 0, tree_depth = 4, tree_branches = 3, tree_flags = 0, park_on = 0, park_at = 0;
+    int prefill_attention = 0;
     float temperature = 1.0f, top_p = 1.0f;
     int processors = 0, n_ban = 0, ban[HPA_LOGIT_BIAS_MAX];
     float repetition = 1.0f, presence = 0.0f, frequency = 0.0f, ban_value[HPA_LOGIT_BIAS_MAX];
@@ -161,6 +165,7 @@ int main(int argc, char** argv) {
             tree_flags += 2;
         }
         else if (!strcmp(a, "--park-at")) { park_at = atoi(v); park_on = 1; }
+        else if (!strcmp(a, "--prefill-attention")) prefill_attention = atoi(v);
         else if (!strcmp(a, "--tree-depth")) tree_depth = atoi(v);
         else if (!strcmp(a, "--tree-branches")) tree_branches = atoi(v);
         else if (!strcmp(a, "--top-logprobs")) {
@@ -233,6 +238,7 @@ int main(int argc, char** argv) {
     if (gpt2_decode_init(&model, B, page_size, total)) return 1;
     if (!greedy && gpt2_decode_set_sampling(&model, filtered ? 2 : 1, 1337ULL)) return 1; /* rng_state = 1337 (:975) */
     if (!greedy && filtered && gpt2_decode_set_sampling_params(&model, -1, temperature, top_k, top_p)) return 2;
+    if (prefill_attention && gpt2_decode_set_prefill_attention(&model, prefill_attention)) return 2;
     if (logprobs && gpt2_decode_set_logprobs(&model, 1)) return 1;
     if (top_lp && gpt2_decode_set_top_logprobs(&model, top_lp)) return 1;
     if (processors) { /* bad values are refused with a message by the setters */

@@ -1044,6 +1044,16 @@ int hpa_paged_attention_prefill(const float* q, const HpaKVPool* pool, int layer
 int hpa_paged_attention_prefill_ragged(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
                                        int bt_stride, const int* start, const int* row0, const int* len, int B,
                                        int T, float* out_frag);
+/* The ragged contract above for bf16 pools (page size 8, 16, 32, 64) and fp8
+ * pools (16, 32, 64) on the bf16 matrix pipe (hpa_prefill_packed.hip): K and V
+ * staged and multiplied as the bf16 values they are (an e4m3 code is one),
+ * 32-key tiles, q and P as three exact bf16 pieces each, so every product is
+ * exact and every sum fp32 as in the kernel above; the fp8 K scale is folded
+ * into q's, the V scale multiplies the output once.  Head size 64.  Anything
+ * else, fp32 pools included, returns nonzero and launches nothing. */
+int hpa_paged_attention_prefill_packed(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
+                                       int bt_stride, const int* start, const int* row0, const int* len, int B,
+                                       int T, float* out_frag);
 /* ---------------- speculative decoding (hpa_verify.hip) ----------------
  * The attention of a verify pass: the ragged contract above (q [rows][C]
  * row-major, row row0[b] + t at position start[b] + t sees keys 0 ..

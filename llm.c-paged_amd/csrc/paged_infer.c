@@ -799,6 +799,9 @@ struct GPT2Decode {
      * them on first use).  pf_slot: the rows' append slots while a tree pass runs
      * its layers (prefill_gemm: the QKV GEMM's positions), NULL otherwise */
     int vf_request;
+    /* gpt2_decode_set_prefill_attention: the request of the dense passes'
+     * attention (gpt2_decode_prefill_plan) */
+    int pf_attn_request;
     DecVerify vf;
     const int* pf_slot;
     /* logit processors (gpt2_decode_set_processors).  The settings' host
@@ -3119,7 +3122,9 @@ static inline DecRowTables dec_row_tables(const GPT2Decode* d) {
  * kernel; the few-row kernel of the verify passes (gpt2_decode_verify_plan);
  * its tree form over the rows' ancestor masks (gpt2_decode_verify_tree).  A
  * bf16 / fp8 pool has the few-row kernel only under request 3
- * (hpa_paged_attention_verify_packed, both forms) */
+ * (hpa_paged_attention_verify_packed, both forms).  The prefill kernel itself
+ * is gpt2_decode_prefill_plan's: under request 1 a bf16 / fp8 pool takes
+ * hpa_paged_attention_prefill_packed */
 typedef enum { DENSE_ATTN_PREFILL = 0, DENSE_ATTN_FEW_ROWS = 1, DENSE_ATTN_FEW_ROWS_TREE = 2 } DenseAttn;
 
 static int dec_dense_attention(GPT2Decode* d, int l, int T, DenseAttn form) {
@@ -3137,8 +3142,11 @@ static int dec_dense_attention(GPT2Decode* d, int l, int T, DenseAttn form) {
                        : hpa_paged_attention_verify_packed(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
                                                            rt.len, NULL, B, T, d->pf_att);
         default:
-            return hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
-                                                      rt.len, B, T, d->pf_att);
+            return gpt2_decode_prefill_plan(d->pool.dtype, d->P, d->pool.head_size, d->pf_attn_request)
+                       ? hpa_paged_attention_prefill_packed(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
+                                                            rt.len, B, T, d->pf_att)
+                       : hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
+                                                            rt.len, B, T, d->pf_att);
     }
 }
 
@@ -3305,6 +3313,24 @@ int gpt2_decode_score_top(GPT2* model, const int* tokens, const int* lens, const
     }
     const DecScore sc = {targets, logprobs, NULL, NULL, NULL, NULL, k, top_ids, top_lps};
     return dec_prefill_rows(model, tokens, lens, next_tokens, NULL, NULL, &sc);
+}
+
+/* The prefill-kernel route of the dense passes, pure: 1 the packed-pool kernel
+ * on the bf16 matrix pipe (hpa_paged_attention_prefill_packed), 0 the fp32 MFMA
+ * kernel.  Opt-in: request 0 never answers 1 */
+int gpt2_decode_prefill_plan(int kv_dtype, int page_size, int head_size, int request) {
+    if (request != 1 || head_size != 64) return 0;
+    if (kv_dtype == HPA_BF16) return page_size == 8 || page_size == 16 || page_size == 32 || page_size == 64;
+    if (kv_dtype == HPA_FP8) return page_size == 16 || page_size == 32 || page_size == 64;
+    return 0;
+}
+
+int gpt2_decode_set_prefill_attention(GPT2* model, int request) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (request != 0 && request != 1) { fprintf(stderr, "[paged_infer] prefill attention: request 0 or 1\n"); return 1; }
+    d->pf_attn_request = request;
+    return 0;
 }
 
 /* ---- speculative greedy decoding ----

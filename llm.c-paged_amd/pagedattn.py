@@ -412,6 +412,7 @@ def lib():
     _sig(L, "hpa_token_recount", i, [v, i, v, i, i, i, i])
     _sig(L, "hpa_paged_attention_prefill", i, [_F, v, i, _I, i, _I, i, i, _F])
     _sig(L, "hpa_paged_attention_prefill_ragged", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
+    _sig(L, "hpa_paged_attention_prefill_packed", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
     _sig(L, "hpa_gather_rows_frag", i, [_F, _F, i, _I, i, _F, _F, i, i])
     _sig(L, "hpa_attention_waves", i, [])
     _sig(L, "hpa_paged_attention_verify", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
@@ -421,6 +422,8 @@ def lib():
     _sig(L, "gpt2_decode_verify_sampled", i, [v, _I, _I, _I, _I, _F])
     _sig(L, "gpt2_decode_verify_plan", i, [i, i, i, i, i])
     _sig(L, "gpt2_decode_set_verify_attention", i, [v, i])
+    _sig(L, "gpt2_decode_prefill_plan", i, [i, i, i, i])
+    _sig(L, "gpt2_decode_set_prefill_attention", i, [v, i])
     _sig(L, "gpt2_attn_shared_plan", i, [_I, i, _I, i, i, i, i, i, _I, _I, _I])
     _sig(L, "gpt2_decode_set_shared_attention", i, [v, i])
     _sig(L, "gpt2_decode_shared_attention", i, [v])
@@ -587,6 +590,15 @@ def verify_plan(max_rows, kv_dtype=0, page_size=16, head_size=64, request=0):
     16 / 32 / 64)"""
     return int(lib().gpt2_decode_verify_plan(int(max_rows), int(kv_dtype), int(page_size), int(head_size),
                                              int(request)))
+
+
+def prefill_plan(kv_dtype=0, page_size=16, head_size=64, request=0):
+    """the prefill-route attention kernel of a dense pass
+    (gpt2_decode_prefill_plan, pure): 1 hpa_paged_attention_prefill_packed (the
+    bf16 matrix pipe), 0 hpa_paged_attention_prefill_ragged.  request 0: always
+    0; request 1: 1 on bf16 pools (pages of 8 / 16 / 32 / 64) and fp8 pools (16
+    / 32 / 64) of head size 64"""
+    return int(lib().gpt2_decode_prefill_plan(int(kv_dtype), int(page_size), int(head_size), int(request)))
 
 
 SHARED_MAX_ROWS = 8  # HPA_SHARED_MAX_ROWS
@@ -1559,6 +1571,13 @@ class Model:
         kernel on bf16 and fp8 pools too -- which also opens verify_tree() and
         verify_tree_sampled() on those pools"""
         check(lib().gpt2_decode_set_verify_attention(self.h, int(request)), "set_verify_attention")
+
+    def set_prefill_attention(self, request=1):
+        """the attention of prefill(), prefill_ragged(), score(), score_top(),
+        the window pass and the chain verify passes that take the prefill
+        kernel: 0 the fp32 MFMA kernel (the default), 1 the packed-pool kernel
+        on the bf16 matrix pipe where it applies (prefill_plan)"""
+        check(lib().gpt2_decode_set_prefill_attention(self.h, int(request)), "set_prefill_attention")
 
     def set_score_chunk(self, rows=0):
         """rows per SCORE GEMM of score(): 0 = the default, else a positive
