@@ -82,9 +82,10 @@
  *     (gpt2_decode_unpark), where it continues as if it had never left: the
  *     text and the ids are those of the run without the flag, sampled runs
  *     included (the sampler state travels).  Not with --speculate.
- *     --prefill-attention N (0 or 1): gpt2_decode_set_prefill_attention.  1 runs
- *     the dense passes' attention on the bf16 matrix pipe where the KV pool is
- *     bf16 or fp8 (gpt2_decode_prefill_plan); an fp32 pool runs as without it.
+ *     --prefill-attention N (0, 1 or 3): gpt2_decode_set_prefill_attention.  1
+ *     runs the dense passes' attention on the bf16 matrix pipe where the KV pool
+ *     is bf16 or fp8 (gpt2_decode_prefill_plan); an fp32 pool runs as without
+ *     it.  3 does so on an fp32 pool as well (split operands).
  */
 #include <stdio.h>
 #include <stdlib.h>

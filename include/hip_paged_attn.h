@@ -1054,6 +1054,17 @@ int hpa_paged_attention_prefill_ragged(const float* q, const HpaKVPool* pool, in
 int hpa_paged_attention_prefill_packed(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
                                        int bt_stride, const int* start, const int* row0, const int* len, int B,
                                        int T, float* out_frag);
+/* The ragged contract above for fp32 pools (page size 8, 16, 32, 64) on the
+ * bf16 matrix pipe (hpa_prefill_split.hip): the packed kernel's work split and
+ * 32-key tiles, with q * scale, K, P and V each cut into three exact bf16
+ * pieces (K and V once per tile, as they are staged) and every product a.b
+ * taken as the six piece products a_i.b_j with i + j <= 2, one MFMA each into
+ * the fp32 accumulator, smallest first.  The three products left out are below
+ * one fp32 rounding of a.b; every sum is fp32.  Head size 64.  Anything else,
+ * bf16 and fp8 pools included, returns nonzero and launches nothing. */
+int hpa_paged_attention_prefill_split(const float* q, const HpaKVPool* pool, int layer, const int* block_table,
+                                      int bt_stride, const int* start, const int* row0, const int* len, int B,
+                                      int T, float* out_frag);
 /* ---------------- speculative decoding (hpa_verify.hip) ----------------
  * The attention of a verify pass: the ragged contract above (q [rows][C]
  * row-major, row row0[b] + t at position start[b] + t sees keys 0 ..

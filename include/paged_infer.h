@@ -280,14 +280,18 @@ int  gpt2_decode_set_verify_attention(GPT2* model, int request);
 /* The attention kernel of a dense pass that does not take a few-row kernel
  * (prefill, prefill_ragged, score, score_top, gpt2_forward's window pass, and
  * the chain verify passes the verify plan sends to the prefill kernel), pure: 1
- * hpa_paged_attention_prefill_packed (the bf16 matrix pipe), 0
+ * hpa_paged_attention_prefill_packed (the bf16 matrix pipe), 2
+ * hpa_paged_attention_prefill_split (that pipe on split fp32 operands), 0
  * hpa_paged_attention_prefill_ragged.  request 0 (the default): always 0.
  * request 1 (opt-in): 1 exactly where the packed kernel applies -- head size 64
  * and a bf16 pool of page size 8, 16, 32 or 64 or an fp8 pool of 16, 32 or 64;
- * 0 on fp32 pools and everything else.  Any other request: 0. */
+ * 0 on fp32 pools and everything else.  request 3 (opt-in): the matrix-pipe
+ * kernel on every pool that has one -- as 1 on bf16 and fp8 pools, and 2 on an
+ * fp32 pool of page size 8, 16, 32 or 64 with head size 64.  Any other request:
+ * 0. */
 int  gpt2_decode_prefill_plan(int kv_dtype, int page_size, int head_size, int request);
-/* the request the dense passes hand to the plan: 0 or 1 (anything else, or no
- * engine: refused, nonzero).  An engine setting: not part of a parked handle */
+/* the request the dense passes hand to the plan: 0, 1 or 3 (anything else, or
+ * no engine: refused, nonzero).  An engine setting: not part of a parked handle */
 int  gpt2_decode_set_prefill_attention(GPT2* model, int request);
 /* Speculative sampling: gpt2_decode_verify under sampling mode 2 (per-sequence
  * temperature / top-k / top-p).  Arguments, row layout, page growth, eviction,

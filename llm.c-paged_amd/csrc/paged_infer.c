@@ -3124,7 +3124,8 @@ static inline DecRowTables dec_row_tables(const GPT2Decode* d) {
  * bf16 / fp8 pool has the few-row kernel only under request 3
  * (hpa_paged_attention_verify_packed, both forms).  The prefill kernel itself
  * is gpt2_decode_prefill_plan's: under request 1 a bf16 / fp8 pool takes
- * hpa_paged_attention_prefill_packed */
+ * hpa_paged_attention_prefill_packed; under request 3 an fp32 pool takes
+ * hpa_paged_attention_prefill_split as well */
 typedef enum { DENSE_ATTN_PREFILL = 0, DENSE_ATTN_FEW_ROWS = 1, DENSE_ATTN_FEW_ROWS_TREE = 2 } DenseAttn;
 
 static int dec_dense_attention(GPT2Decode* d, int l, int T, DenseAttn form) {
@@ -3142,11 +3143,17 @@ static int dec_dense_attention(GPT2Decode* d, int l, int T, DenseAttn form) {
                        : hpa_paged_attention_verify_packed(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
                                                            rt.len, NULL, B, T, d->pf_att);
         default:
-            return gpt2_decode_prefill_plan(d->pool.dtype, d->P, d->pool.head_size, d->pf_attn_request)
-                       ? hpa_paged_attention_prefill_packed(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
-                                                            rt.len, B, T, d->pf_att)
-                       : hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start, rt.row0,
-                                                            rt.len, B, T, d->pf_att);
+            switch (gpt2_decode_prefill_plan(d->pool.dtype, d->P, d->pool.head_size, d->pf_attn_request)) {
+                case 2:
+                    return hpa_paged_attention_prefill_split(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start,
+                                                             rt.row0, rt.len, B, T, d->pf_att);
+                case 1:
+                    return hpa_paged_attention_prefill_packed(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start,
+                                                              rt.row0, rt.len, B, T, d->pf_att);
+                default:
+                    return hpa_paged_attention_prefill_ragged(d->pf_q, &d->pool, l, d->d_bt, d->bt_stride, rt.start,
+                                                              rt.row0, rt.len, B, T, d->pf_att);
+            }
     }
 }
 
@@ -3316,19 +3323,27 @@ int gpt2_decode_score_top(GPT2* model, const int* tokens, const int* lens, const
 }
 
 /* The prefill-kernel route of the dense passes, pure: 1 the packed-pool kernel
- * on the bf16 matrix pipe (hpa_paged_attention_prefill_packed), 0 the fp32 MFMA
- * kernel.  Opt-in: request 0 never answers 1 */
+ * on the bf16 matrix pipe (hpa_paged_attention_prefill_packed), 2 the
+ * split-operand kernel of fp32 pools on that pipe
+ * (hpa_paged_attention_prefill_split), 0 the fp32 MFMA kernel.  Opt-in: request
+ * 1 asks for the packed kernel, request 3 for the matrix-pipe kernel of every
+ * pool that has one; any other request answers 0 */
 int gpt2_decode_prefill_plan(int kv_dtype, int page_size, int head_size, int request) {
-    if (request != 1 || head_size != 64) return 0;
-    if (kv_dtype == HPA_BF16) return page_size == 8 || page_size == 16 || page_size == 32 || page_size == 64;
-    if (kv_dtype == HPA_FP8) return page_size == 16 || page_size == 32 || page_size == 64;
+    if ((request != 1 && request != 3) || head_size != 64) return 0;
+    const int p16 = page_size == 16 || page_size == 32 || page_size == 64;
+    if (kv_dtype == HPA_BF16) return p16 || page_size == 8;
+    if (kv_dtype == HPA_FP8) return p16;
+    if (kv_dtype == HPA_F32 && request == 3) return p16 || page_size == 8 ? 2 : 0;
     return 0;
 }
 
 int gpt2_decode_set_prefill_attention(GPT2* model, int request) {
     GPT2Decode* d = model ? model->decode : NULL;
     if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
-    if (request != 0 && request != 1) { fprintf(stderr, "[paged_infer] prefill attention: request 0 or 1\n"); return 1; }
+    if (request != 0 && request != 1 && request != 3) {
+        fprintf(stderr, "[paged_infer] prefill attention: request 0, 1 or 3\n");
+        return 1;
+    }
     d->pf_attn_request = request;
     return 0;
 }

@@ -413,6 +413,7 @@ def lib():
     _sig(L, "hpa_paged_attention_prefill", i, [_F, v, i, _I, i, _I, i, i, _F])
     _sig(L, "hpa_paged_attention_prefill_ragged", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
     _sig(L, "hpa_paged_attention_prefill_packed", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
+    _sig(L, "hpa_paged_attention_prefill_split", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
     _sig(L, "hpa_gather_rows_frag", i, [_F, _F, i, _I, i, _F, _F, i, i])
     _sig(L, "hpa_attention_waves", i, [])
     _sig(L, "hpa_paged_attention_verify", i, [_F, v, i, _I, i, _I, _I, _I, i, i, _F])
@@ -595,9 +596,11 @@ def verify_plan(max_rows, kv_dtype=0, page_size=16, head_size=64, request=0):
 def prefill_plan(kv_dtype=0, page_size=16, head_size=64, request=0):
     """the prefill-route attention kernel of a dense pass
     (gpt2_decode_prefill_plan, pure): 1 hpa_paged_attention_prefill_packed (the
-    bf16 matrix pipe), 0 hpa_paged_attention_prefill_ragged.  request 0: always
+    bf16 matrix pipe), 2 hpa_paged_attention_prefill_split (that pipe on split
+    fp32 operands), 0 hpa_paged_attention_prefill_ragged.  request 0: always
     0; request 1: 1 on bf16 pools (pages of 8 / 16 / 32 / 64) and fp8 pools (16
-    / 32 / 64) of head size 64"""
+    / 32 / 64) of head size 64; request 3: the same, and 2 on fp32 pools (8 /
+    16 / 32 / 64) of head size 64"""
     return int(lib().gpt2_decode_prefill_plan(int(kv_dtype), int(page_size), int(head_size), int(request)))
 
 
@@ -1576,7 +1579,8 @@ class Model:
         """the attention of prefill(), prefill_ragged(), score(), score_top(),
         the window pass and the chain verify passes that take the prefill
         kernel: 0 the fp32 MFMA kernel (the default), 1 the packed-pool kernel
-        on the bf16 matrix pipe where it applies (prefill_plan)"""
+        on the bf16 matrix pipe where it applies, 3 that and the
+        split-operand kernel of fp32 pools on the same pipe (prefill_plan)"""
         check(lib().gpt2_decode_set_prefill_attention(self.h, int(request)), "set_prefill_attention")
 
     def set_score_chunk(self, rows=0):
