@@ -86,6 +86,10 @@
  *     runs the dense passes' attention on the bf16 matrix pipe where the KV pool
  *     is bf16 or fp8 (gpt2_decode_prefill_plan); an fp32 pool runs as without
  *     it.  3 does so on an fp32 pool as well (split operands).
+ *     --dense-gemm N (0 or 1): gpt2_decode_set_dense_gemm.  1 runs the dense
+ *     passes' layer and head GEMMs of an fp32-weight engine on the bf16 matrix
+ *     pipe (split operands, gpt2_decode_dense_gemm_plan); other weights run as
+ *     without it.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -136,6 +140,7 @@ int main(int argc, char** argv) {
     int perplexity = 0, logprobs = 0, speculate = 0, spec_sampled = 0, top_lp = 0;
     int spec_tree = 0, spec_chain = 0, tree_depth = 4, tree_branches = 3, tree_flags = 0, park_on = 0, park_at = 0;
     int prefill_attention = 0;
+    int dense_gemm = 0;
     float temperature = 1.0f, top_p = 1.0f;
     int processors = 0, n_ban = 0, ban[HPA_LOGIT_BIAS_MAX];
     float repetition = 1.0f, presence = 0.0f, frequency = 0.0f, ban_value[HPA_LOGIT_BIAS_MAX];
@@ -167,6 +172,7 @@ int main(int argc, char** argv) {
         }
         else if (!strcmp(a, "--park-at")) { park_at = atoi(v); park_on = 1; }
         else if (!strcmp(a, "--prefill-attention")) prefill_attention = atoi(v);
+        else if (!strcmp(a, "--dense-gemm")) dense_gemm = atoi(v);
         else if (!strcmp(a, "--tree-depth")) tree_depth = atoi(v);
         else if (!strcmp(a, "--tree-branches")) tree_branches = atoi(v);
         else if (!strcmp(a, "--top-logprobs")) {
@@ -240,6 +246,7 @@ int main(int argc, char** argv) {
     if (!greedy && gpt2_decode_set_sampling(&model, filtered ? 2 : 1, 1337ULL)) return 1; /* rng_state = 1337 (:975) */
     if (!greedy && filtered && gpt2_decode_set_sampling_params(&model, -1, temperature, top_k, top_p)) return 2;
     if (prefill_attention && gpt2_decode_set_prefill_attention(&model, prefill_attention)) return 2;
+    if (dense_gemm && gpt2_decode_set_dense_gemm(&model, dense_gemm)) return 2;
     if (logprobs && gpt2_decode_set_logprobs(&model, 1)) return 1;
     if (top_lp && gpt2_decode_set_top_logprobs(&model, top_lp)) return 1;
     if (processors) { /* bad values are refused with a message by the setters */

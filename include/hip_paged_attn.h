@@ -436,8 +436,20 @@ typedef struct {
                              the (32-column super-tile, k16) steps, all M rows at once;
                              tiles split between workgroups are summed in workgroup
                              order by the last to arrive (sk_slab / sk_count).  LN
-                             folded (ln_fold_c1) or applied on load (K <= 2048) */
-    int col_tiles;        /* 16-column tiles per workgroup: 1; 2 (waves 4/8, row_blocks
+                             folded (ln_fold_c1) or applied on load (K <= 2048);
+                             7 = fp32 weights only (w_dtype = HPA_F32, the fp32 frag
+                             layout as it stands): the looped work split on
+                             v_mfma_f32_16x16x32_bf16 by exact operand splitting
+                             (hpa_gemm_split.hip).  Both operands are cut in registers
+                             into three bf16 pieces, x = hi + mid + lo exactly, and the
+                             six piece products a_i w_j with i + j <= 2 are summed in
+                             fp32, smallest first; the three left out are below 2^-21
+                             |a||w|.  K % 32 == 0; every epilogue; LN on load (K <= 2048)
+                             or folded; waves 4 / 8, row_blocks and col_tiles 1 / 2 / 4
+                             ((4, 4): waves 4; at 8 col_tiles falls to 2), 0 = by shape
+                             (hpa_fused_pick_split).  A row's bits depend on the waves
+                             alone.  Never picked by variant 0 */
+    int col_tiles;       /* 16-column tiles per workgroup: 1; 2 (waves 4/8, row_blocks
                              2/4); 4 (waves 4, row_blocks 4); 0 = by shape.  A hint:
                              where M's row blocks or the waves cannot carry it, 1 */
     const int* row_seq;   /* QKV: block-table row of each GEMM row (NULL = the row
@@ -564,6 +576,12 @@ void hpa_fused_pick_fp4(int M, int N, int K, int* out4);
  * col_tiles}, after profiles/r21/w_mx48.txt (s): 4 waves; (1, 1) below 8 row
  * blocks at N <= 1024, (4, 2) from M = 512 at K >= 4096, else (2, 2) */
 void hpa_fused_pick_mx48(int M, int N, int K, int* out4);
+/* the split-operand kernel (variant 7) when waves / row_blocks / col_tiles are
+ * 0: out3 = {waves, row_blocks, col_tiles}; never by M (a row's bits follow the
+ * waves).  After the sweep of profiles/r25/dense_gemm_split.txt: {8, 4, 2} at
+ * K >= 3072 and for the head GEMM (N/16 >= 1024), else {4, 2, 4} from N = 4096
+ * and {4, 2, 2} below */
+void hpa_fused_pick_split(int M, int N, int K, int* out3);
 /* bf16 weights, A-resident kernel (variant 5: the workgroup's rows of A
  * LayerNorm'ed and rounded into LDS once, waves walking waves*rounds column
  * tiles over the whole K; col_tiles = rounds for this variant):

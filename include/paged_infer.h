@@ -293,6 +293,21 @@ int  gpt2_decode_prefill_plan(int kv_dtype, int page_size, int head_size, int re
 /* the request the dense passes hand to the plan: 0, 1 or 3 (anything else, or
  * no engine: refused, nonzero).  An engine setting: not part of a parked handle */
 int  gpt2_decode_set_prefill_attention(GPT2* model, int request);
+/* The kernel of a dense pass's GEMMs, pure: 1 the split-operand kernel
+ * (hpa_gemm_fused variant 7: fp32 weights as they stand, multiplied on the bf16
+ * matrix pipe as three exact bf16 pieces per operand; fp32 error class), 0 what
+ * the pass launches otherwise.  1 exactly when request == 1, w_dtype == HPA_F32
+ * and K % 32 == 0: a request, not a default, so no performance thresholds. */
+int  gpt2_decode_dense_gemm_plan(int w_dtype, int K, int request);
+/* the request the dense passes hand to that plan: 0 (the default) or 1
+ * (anything else, or no engine: refused, nonzero).  Under request 1 the four
+ * layer GEMMs of every dense pass (prefill, prefill_ragged, score, score_top,
+ * gpt2_forward's window pass, every verify pass) and the dense head GEMMs (the
+ * SCORE / LOGITS chunks, the all-row logits) take variant 7 at its by-shape
+ * launch parameters wherever the plan says 1.  The decode step, its captured
+ * graph, the persistent chains and a dense pass's tail GEMM (last-row logits
+ * and pick) never do.  An engine setting: not part of a parked handle */
+int  gpt2_decode_set_dense_gemm(GPT2* model, int request);
 /* Speculative sampling: gpt2_decode_verify under sampling mode 2 (per-sequence
  * temperature / top-k / top-p).  Arguments, row layout, page growth, eviction,
  * trace arming, out_tokens layout and position bookkeeping are

@@ -781,6 +781,25 @@ void hpa_fused_pick_bf16(int M, int N, int K, int* out3) {
     out3[2] = small ? 1 : 2;
 }
 
+// fp32 weights on the bf16 pipe (variant 7, hpa_gemm_split.hip).  Never by M
+// beyond the row blocks M has: a row's bits follow the waves alone.  The table
+// follows the sweep of profiles/r25/dense_gemm_split.txt (every (waves, row
+// blocks, column tiles) at M = 1024, the layer GEMMs of GPT-2 124M and XL):
+//  * 4 waves, 2 row blocks, 2 column tiles: first or within the spreads of the
+//    first at qkv / attproj / fc of 124M and attproj of XL;
+//  * 4 column tiles from N = 4096 (XL qkv 168 against 181 us, fc 213 against 231);
+//  * K >= 3072 (fcproj): 8 waves, 4 x 2 -- within the spreads of the first at
+//    both models, where 4 waves 2 x 2 lost 14 us at XL;
+//  * the head GEMM (N/16 >= 1024) keeps 8 waves 4 x 2, the one shape it was
+//    measured at.
+void hpa_fused_pick_split(int M, int N, int K, int* out3) {
+    (void)M;
+    const int big = K >= 3072 || (N + 15) / 16 >= 1024;
+    out3[0] = big ? 8 : 4;
+    out3[1] = big ? 4 : 2;
+    out3[2] = big ? 2 : N >= 4096 ? 4 : 2;
+}
+
 int hpa_fused_pick_waves(int M, int N, int K) {
     int p[3];
     hpa_fused_pick(M, N, K, p);
@@ -824,9 +843,28 @@ static int gemm_fused_launch(const HpaFusedGemm* g, FG& p) {
     int nw, mt, ntw;
     // SCORE lives in the looped fp32 kernel, the two bf16-weight kernels and the fp8-weight kernel only
     const bool score = g->epilogue == HPA_FEPI_SCORE;
-    HPA_REQUIRE(!score || g->variant == 0 || g->variant == 1 || (g->variant == 5 && g->w_dtype == HPA_BF16),
-                "gemm_fused SCORE: variant 0 or 1 (looped), or 5 on bf16 weights; not one-shot (2), ring (3), "
+    HPA_REQUIRE(!score || g->variant == 0 || g->variant == 1 || g->variant == 7 ||
+                    (g->variant == 5 && g->w_dtype == HPA_BF16),
+                "gemm_fused SCORE: variant 0 or 1 (looped), 7 (split), or 5 on bf16 weights; not one-shot (2), ring (3), "
                 "activation-resident (4) or stream-K (6)");
+    if (g->variant == 7) {  // fp32 weights on the bf16 matrix pipe, split operands: hpa_gemm_split.hip
+        HPA_REQUIRE(g->w_dtype == HPA_F32,
+                    "gemm_fused split (variant 7): w_dtype must be HPA_F32 (fp32 weights in the fp32 frag layout)");
+        HPA_REQUIRE(g->K % 32 == 0, "gemm_fused split (variant 7): K % 32 != 0");
+        HPA_REQUIRE(g->waves == 0 || g->waves == 4 || g->waves == 8, "gemm_fused split (variant 7): waves must be 4 or 8");
+        HPA_REQUIRE(g->row_blocks == 0 || g->row_blocks == 1 || g->row_blocks == 2 || g->row_blocks == 4,
+                    "gemm_fused split (variant 7): row_blocks must be 1, 2 or 4");
+        HPA_REQUIRE(g->col_tiles == 0 || g->col_tiles == 1 || g->col_tiles == 2 || g->col_tiles == 4,
+                    "gemm_fused split (variant 7): col_tiles must be 1, 2 or 4");
+        int pk[3];
+        hpa_fused_pick_split(g->M, g->N, g->K, pk);
+        nw = g->waves ? g->waves : pk[0];
+        mt = g->row_blocks ? g->row_blocks : pk[1];
+        ntw = g->col_tiles ? g->col_tiles : pk[2];
+        while (mt > 1 && (p.Mp / 16) % mt) mt >>= 1;  // row blocks of this M
+        if (nw == 8 && mt == 4 && ntw == 4) ntw = 2;    // a hint, as in the looped kernel: 4 x 4 is a 4-wave shape
+        return launch_split(p, g->epilogue, nw, mt, ntw);
+    }
     if (g->w_dtype == HPA_BF16) {  // bf16 weights: hpa_gemm_bf16.hip
         HPA_REQUIRE(g->K % 32 == 0 && !g->ln_fold_c1 &&
                         (g->variant == 0 || g->variant == 4 || g->variant == 5 || g->variant == 1),
@@ -923,7 +961,7 @@ static int gemm_fused_launch(const HpaFusedGemm* g, FG& p) {
     HPA_REQUIRE(g->row_blocks == 0 || g->row_blocks == 1 || g->row_blocks == 2 || g->row_blocks == 4,
                 "gemm_fused: row_blocks must be 1, 2 or 4");
     looped_shape(g, p.Mp, &nw, &mt, &ntw);
-    HPA_REQUIRE(g->variant >= 0 && g->variant <= 4, "gemm_fused: variant must be 0, 1, 2, 3 or 4");
+    HPA_REQUIRE(g->variant >= 0 && g->variant <= 4, "gemm_fused: variant must be 0, 1, 2, 3, 4, 6 or 7 (5: bf16 / fp4 weights)");
     if (g->variant == 3)  // loader / MFMA-wave ring (hpa_gemm_ring.hip); waves = K parts
         return launch_ring(p, g->epilogue, g->waves > 0 ? g->waves : 1);
     // (waves 16 / 12: the resident kernel's 16-wave or ring form; else by M)

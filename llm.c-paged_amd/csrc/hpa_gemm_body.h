@@ -718,6 +718,10 @@ int launch_f4w_ares(const FG& p, const unsigned char* gscale, int epi, int nw, i
 // layout, a_ws the activation workspace; the quantiser (with the LN), then
 // the scaled-MFMA GEMM; QKV / RESID / GELU, the shapes of launch_b16
 int launch_mx48(const FG& p, const unsigned char* gscale, void* a_ws, int epi, int nw, int mt, int ntw);
+// split-operand launch (hpa_gemm_split.hip, variant 7): fp32 weights in the
+// fp32 frag layout on the bf16 MFMA; waves 4/8, row_blocks and col_tiles 1/2/4
+// ((4, 4) at waves 4 only), every epilogue, K % 32 == 0
+int launch_split(const FG& p, int epi, int nw, int mt, int ntw);
 // A-resident bf16 variant (variant 5): waves 4/8, row_blocks (mt) 1/2/4 with
 // mt*K <= 3200; each workgroup takes waves*rounds column tiles
 int launch_b16_ares(const FG& p, int epi, int nw, int mt, int rounds);

@@ -39,6 +39,7 @@
 #include <math.h>
 
 #include "hpa_internal.h"
+#include "hpa_split3.h"
 
 namespace {
 
@@ -108,26 +109,12 @@ __device__ __forceinline__ void load_codes(const PackedArgs& a, const int* bt, i
     }
 }
 
-// x = hi + mid + lo exactly, each a bf16 (the top 16 bits of the returned words)
-__device__ __forceinline__ void split3(float x, unsigned& hi, unsigned& mid, unsigned& lo) {
-    hi = __float_as_uint(x) & 0xffff0000u;
-    const float r = x - __uint_as_float(hi);
-    mid = __float_as_uint(r) & 0xffff0000u;
-    lo = __float_as_uint(r - __uint_as_float(mid));
-}
-__device__ __forceinline__ unsigned pack_hi16(unsigned even, unsigned odd) { return (even >> 16) | (odd & 0xffff0000u); }
-
-// 8 fp32 values -> the three bf16x8 operands of their pieces (0 lo, 1 mid, 2 hi)
+// 8 fp32 values -> the three bf16x8 operands of their pieces (hpa_split3.h), here 0 lo, 1 mid, 2 hi
 __device__ __forceinline__ void split3x8(const float* x, bf16x8* piece) {
-    unsigned hi[8], mid[8], lo[8];
+    u32x4 pc[3];
+    hpa_split::split3x8(x, pc);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) split3(x[i], hi[i], mid[i], lo[i]);
-    piece[0] = __builtin_bit_cast(bf16x8, u32x4{pack_hi16(lo[0], lo[1]), pack_hi16(lo[2], lo[3]), pack_hi16(lo[4], lo[5]),
-                                                pack_hi16(lo[6], lo[7])});
-    piece[1] = __builtin_bit_cast(bf16x8, u32x4{pack_hi16(mid[0], mid[1]), pack_hi16(mid[2], mid[3]),
-                                                pack_hi16(mid[4], mid[5]), pack_hi16(mid[6], mid[7])});
-    piece[2] = __builtin_bit_cast(bf16x8, u32x4{pack_hi16(hi[0], hi[1]), pack_hi16(hi[2], hi[3]), pack_hi16(hi[4], hi[5]),
-                                                pack_hi16(hi[6], hi[7])});
+    for (int j = 0; j < 3; ++j) piece[2 - j] = __builtin_bit_cast(bf16x8, pc[j]);
 }
 
 template <bool FP8>

@@ -45,6 +45,7 @@
 #include <math.h>
 
 #include "hpa_internal.h"
+#include "hpa_split3.h"
 
 #ifndef HPA_SPLIT_TERMS
 #define HPA_SPLIT_TERMS 6
@@ -97,25 +98,9 @@ __device__ __forceinline__ void load_kv8(const SplitArgs& a, const int* bt, int 
     v[0] = v0.x, v[1] = v0.y, v[2] = v0.z, v[3] = v0.w, v[4] = v1.x, v[5] = v1.y, v[6] = v1.z, v[7] = v1.w;
 }
 
-// x = pc[0] + pc[1] + pc[2] exactly, each a bf16 (the top 16 bits of the words)
-__device__ __forceinline__ void split3(float x, unsigned* pc) {
-    pc[0] = __float_as_uint(x) & 0xffff0000u;
-    const float r = x - __uint_as_float(pc[0]);
-    pc[1] = __float_as_uint(r) & 0xffff0000u;
-    pc[2] = __float_as_uint(r - __uint_as_float(pc[1]));
-}
-__device__ __forceinline__ unsigned pack_hi16(unsigned even, unsigned odd) { return (even >> 16) | (odd & 0xffff0000u); }
-
-// 8 fp32 values -> the bf16x8 operands of their three pieces
-__device__ __forceinline__ void split3x8(const float* x, u32x4* piece) {
-    unsigned pc[8][3];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) split3(x[i], pc[i]);
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        piece[j] = u32x4{pack_hi16(pc[0][j], pc[1][j]), pack_hi16(pc[2][j], pc[3][j]), pack_hi16(pc[4][j], pc[5][j]),
-                         pack_hi16(pc[6][j], pc[7][j])};
-}
+using hpa_split::pack_hi16;  // the pieces: hpa_split3.h
+using hpa_split::split3;
+using hpa_split::split3x8;
 
 __device__ __forceinline__ f32x4 mfma_bf16(u32x4 a, u32x4 b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);

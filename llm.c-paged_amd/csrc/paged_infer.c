@@ -802,6 +802,9 @@ struct GPT2Decode {
     /* gpt2_decode_set_prefill_attention: the request of the dense passes'
      * attention (gpt2_decode_prefill_plan) */
     int pf_attn_request;
+    /* gpt2_decode_set_dense_gemm: the request of the dense passes' layer and head
+     * GEMMs (gpt2_decode_dense_gemm_plan) */
+    int pf_gemm_request;
     DecVerify vf;
     const int* pf_slot;
     /* logit processors (gpt2_decode_set_processors).  The settings' host
@@ -2874,6 +2877,33 @@ static int dec_prefill_reserve(GPT2* model, int R) {
     return 0;
 }
 
+/* The GEMM kernel of a dense pass's layer and head GEMMs, pure: 1 the
+ * split-operand kernel (hpa_gemm_fused variant 7: fp32 weights on the bf16 matrix
+ * pipe), 0 what the pass launches today.  Opt-in, a request and not a default:
+ * no performance thresholds */
+int gpt2_decode_dense_gemm_plan(int w_dtype, int K, int request) {
+    return request == 1 && w_dtype == HPA_F32 && K > 0 && K % 32 == 0;
+}
+
+int gpt2_decode_set_dense_gemm(GPT2* model, int request) {
+    GPT2Decode* d = model ? model->decode : NULL;
+    if (!d) { fprintf(stderr, "[paged_infer] gpt2_decode_init first\n"); return 1; }
+    if (request != 0 && request != 1) {
+        fprintf(stderr, "[paged_infer] dense gemm: request 0 or 1\n");
+        return 1;
+    }
+    d->pf_gemm_request = request;
+    return 0;
+}
+
+/* a dense pass's GEMM g, complete: where the plan says so, the split kernel at
+ * its by-shape launch parameters; else g as it stands */
+static void dec_dense_gemm_route(const GPT2Decode* d, HpaFusedGemm* g) {
+    if (!gpt2_decode_dense_gemm_plan(g->w_dtype, g->K, d->pf_gemm_request)) return;
+    g->variant = 7;
+    g->waves = g->row_blocks = g->col_tiles = 0;
+}
+
 static int prefill_gemm(GPT2* model, int l, int which, int R) {
     GPT2Decode* d = model->decode;
     const GPT2Config c = model->config;
@@ -2921,6 +2951,7 @@ static int prefill_gemm(GPT2* model, int l, int which, int R) {
             g.stats_out = d->d_fold && l + 1 < c.num_layers ? NULL : d->pf_st1;
             break;
     }
+    dec_dense_gemm_route(d, &g);
     return hpa_gemm_fused(&g);
 }
 
@@ -2940,6 +2971,7 @@ static int prefill_all_logits(GPT2* model, int R, float* rows_out, const int* ou
     g.out = rows_out;
     g.row_seq = out_rows; /* LOGITS: GEMM row -> row of rows_out (NULL: the same) */
     g.part_out = part;
+    dec_dense_gemm_route(d, &g);
     const int rc = hpa_gemm_fused(&g) || hpa_synchronize();
     hpa_free(part);
     return rc;
@@ -3002,6 +3034,7 @@ static int dec_head_chunk(GPT2* model, int Rp, const int* hrows, int n, int epil
     int rc = hpa_memcpy(d->sc_rows, hrows, n * sizeof(int));
     rc |= hpa_gather_rows_frag(d->pf_res, d->pf_st1, Rp, d->sc_rows, n, d->sc_x, d->sc_st, np, model->config.channels);
     dec_head_gemm_desc(model, n, d->sc_x, d->sc_st, epilogue, g);
+    dec_dense_gemm_route(d, g);
     return rc;
 }
 

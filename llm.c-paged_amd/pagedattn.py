@@ -374,6 +374,7 @@ def lib():
     _sig(L, "hpa_mxfp8_workspace_bytes", ctypes.c_size_t, [i, i])
     _sig(L, "hpa_quant_mxfp8_rows", i, [v, i, i, v, i, v, v, v])
     _sig(L, "hpa_fused_pick_mx48", None, [i, i, i, _I])
+    _sig(L, "hpa_fused_pick_split", None, [i, i, i, _I])
     _sig(L, "gpt2_decode_prefill", i, [v, _I, i, _I])
     _sig(L, "gpt2_decode_prefill_ragged", i, [v, _I, _I, _I])
     _sig(L, "gpt2_decode_score", i, [v, _I, _I, _I, _F, _I, _I])
@@ -425,6 +426,8 @@ def lib():
     _sig(L, "gpt2_decode_set_verify_attention", i, [v, i])
     _sig(L, "gpt2_decode_prefill_plan", i, [i, i, i, i])
     _sig(L, "gpt2_decode_set_prefill_attention", i, [v, i])
+    _sig(L, "gpt2_decode_dense_gemm_plan", i, [i, i, i])
+    _sig(L, "gpt2_decode_set_dense_gemm", i, [v, i])
     _sig(L, "gpt2_attn_shared_plan", i, [_I, i, _I, i, i, i, i, i, _I, _I, _I])
     _sig(L, "gpt2_decode_set_shared_attention", i, [v, i])
     _sig(L, "gpt2_decode_shared_attention", i, [v])
@@ -602,6 +605,14 @@ def prefill_plan(kv_dtype=0, page_size=16, head_size=64, request=0):
     / 32 / 64) of head size 64; request 3: the same, and 2 on fp32 pools (8 /
     16 / 32 / 64) of head size 64"""
     return int(lib().gpt2_decode_prefill_plan(int(kv_dtype), int(page_size), int(head_size), int(request)))
+
+
+def dense_gemm_plan(w_dtype=0, K=768, request=0):
+    """the kernel of a dense pass's GEMMs (gpt2_decode_dense_gemm_plan, pure): 1
+    hpa_gemm_fused variant 7 (fp32 weights on the bf16 matrix pipe, split
+    operands) exactly when request is 1, the weights are fp32 and K % 32 == 0;
+    else 0"""
+    return int(lib().gpt2_decode_dense_gemm_plan(int(w_dtype), int(K), int(request)))
 
 
 SHARED_MAX_ROWS = 8  # HPA_SHARED_MAX_ROWS
@@ -1582,6 +1593,14 @@ class Model:
         on the bf16 matrix pipe where it applies, 3 that and the
         split-operand kernel of fp32 pools on the same pipe (prefill_plan)"""
         check(lib().gpt2_decode_set_prefill_attention(self.h, int(request)), "set_prefill_attention")
+
+    def set_dense_gemm(self, request=1):
+        """the layer and head GEMMs of the dense passes (prefill(),
+        prefill_ragged(), score(), score_top(), the window pass, every verify
+        pass): 0 what they launch by default, 1 the split-operand kernel of fp32
+        weights on the bf16 matrix pipe where it applies (dense_gemm_plan).  The
+        decode step, the chains and a pass's tail GEMM are not touched"""
+        check(lib().gpt2_decode_set_dense_gemm(self.h, int(request)), "set_dense_gemm")
 
     def set_score_chunk(self, rows=0):
         """rows per SCORE GEMM of score(): 0 = the default, else a positive
